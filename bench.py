@@ -2,7 +2,15 @@
 """Headline benchmark: scored candidates/sec on MIND-large-shaped impressions.
 
     python bench.py [--gpus N --steps K --warmup W --pooler latent|final --dtype bf16|fp32
-                     --scaling strong|weak --backend nccl|gloo]
+                     --scaling strong|weak --backend nccl|gloo --dump-outputs DIR --full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if
+``--dump-outputs DIR`` is given (the scores of the last timed step as
+``DIR/scores.npy``, float32; per rank ``scores_rank<r>.npy`` at N > 1) and
+prints the result line with the headline figure (``value``, ``ms_per_step``).
+Everything else described below (roofline, CPU baseline, AUC gates, the other
+poolers / precisions / shapes, the multi-rank parity checks and extras) runs
+only with ``--full``, which prints the same line with those fields added.
 
 Workload (BASELINE.json configs[2] at N = 1, configs[3] at N > 1): synthetic
 MIND-large-dev-shaped impressions (N = 72,023 news, I = 376,471 impressions,
@@ -27,7 +35,7 @@ the extras add the same strong-scaling step on the MIND-large *test* shape
 reading (``--scaling weak``: every rank its own full MIND-large-dev-sized set,
 per-GPU work fixed as N grows, rank 0's set = the N = 1 set).
 
-Also reported in the same JSON line:
+With ``--full``, also reported in the same JSON line:
   roofline      the pool+score kernel (dominant; a random-row gather served by
                 HBM + Infinity Cache): algorithmic bytes per launch / its
                 HIP-event average duration, vs the 8 TB/s HBM spec and vs the
@@ -252,8 +260,30 @@ class Run:
         return acc / reps
 
 
-def timed(step, steps: int, warmup: int, world: int, dev, host_reduce: bool):
-    """Warmup, then `steps` steps bracketed by barrier + device sync; max over ranks."""
+DUMP_MAX_BYTES = 60_000_000  # per array; the headline's 13.9 M float32 scores fit whole
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """--dump-outputs: write what the timed path returned in its last step as
+    <name>.npy (float32).  An array above DUMP_MAX_BYTES is cut to a fixed
+    sample (sorted positions drawn once from seed 1234) so that two builds dump
+    the same elements.  Returns {name: elements written}."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        cap = DUMP_MAX_BYTES // 4
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(1234).choice(a.size, cap, replace=False))]
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = int(a.size)
+    return written
+
+
+def timed(step, steps: int, warmup: int, world: int, dev, host_reduce: bool, keep: list = None):
+    """Warmup, then `steps` steps bracketed by barrier + device sync; max over ranks.
+    `keep` (a list) receives what the last timed step returned."""
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -261,12 +291,15 @@ def timed(step, steps: int, warmup: int, world: int, dev, host_reduce: bool):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if keep is not None:
+        keep.append(last)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if host_reduce else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -850,6 +883,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: stage times and roofline, the other poolers / "
+                         "precisions / shapes, training and encoder legs, the CPU baseline and the AUC gates, the "
+                         "multi-rank parity checks (the --no-extra / --cpu-* / --no-auc-gate options trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's scores as DIR/scores.npy (float32; "
+                         "scores_rank<r>.npy per rank at N > 1)")
     ap.add_argument("--pooler", choices=["latent", "final"], default="latent")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
     ap.add_argument("--shape", default="mind_large_dev", choices=list(synthetic.SHAPES))
@@ -876,6 +916,8 @@ def main():
                     help="N > 1 launcher: kill the ranks when none changes phase for this many seconds")
     ap.add_argument("--wall-timeout", type=float, default=1800.0, help="N > 1 launcher: kill the ranks after this")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:], args.stall_timeout, args.wall_timeout))
@@ -929,7 +971,8 @@ def main():
 
     phase("headline")
     head = Run(args.pooler, args.dtype, imps, table, dev, rank, world)
-    dt = timed(head.step, args.steps, args.warmup, world, dev, host_reduce)
+    last = []
+    dt = timed(head.step, args.steps, args.warmup, world, dev, host_reduce, keep=last)
     phase("headline_done")
     ms = dt / args.steps * 1e3
     if total_cand is None:  # weak: every rank's own set
@@ -938,6 +981,42 @@ def main():
             dist.all_reduce(c)
         total_cand = int(c.item())
     value = total_cand / (dt / args.steps)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {"scores" if world == 1 else f"scores_rank{rank}": last[0][0]})
+    del last
+    line = {
+        "metric": "scored candidates/sec on MIND-large impressions; AUC parity vs CPU ref",
+        "value": round(value, 1),
+        "unit": "scored candidates/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms, 3),
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic (seeded MIND-large-dev-shaped impressions, N(0,1) news table, deterministic "
+                "random-init pooler weights)",
+        "config": {"workload": f"{args.shape} eval, {args.pooler} pooler: per-news transform + pool + "
+                               f"cosine score", "pooler": args.pooler, "n_news": n_news,
+                   "impressions": n_imp if args.scaling == "strong" else n_imp * world,
+                   "parallelism": f"impressions x{world} ({args.scaling}), news-table transform sharded + "
+                                  f"all-gather ({args.backend})"},
+        "full": args.full,
+    }
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "elements": dumped}
+    if not args.full:  # the headline only
+        log(f"[bench] {args.pooler}/{args.dtype} x{world}: {ms:.3f} ms/step, {value:.3e} cand/s")
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        phase("printed")
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     stages = head.stage_times()
     bytes_ps = ps_bytes(imps, args.pooler, es)
     achieved = bytes_ps / (stages[2] * 1e-3) / 1e9
@@ -1190,24 +1269,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "scored candidates/sec on MIND-large impressions; AUC parity vs CPU ref",
-            "value": round(value, 1),
-            "unit": "scored candidates/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms, 3),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic (seeded MIND-large-dev-shaped impressions, N(0,1) news table, deterministic "
-                    "random-init pooler weights)",
-            "config": {"workload": f"{args.shape} eval, {args.pooler} pooler: per-news transform + pool + "
-                                   f"cosine score", "pooler": args.pooler, "n_news": n_news,
-                       "impressions": n_imp if args.scaling == "strong" else n_imp * world,
-                       "parallelism": f"impressions x{world} ({args.scaling}), news-table transform sharded + "
-                                      f"all-gather ({args.backend})"},
+            **line,
             "roofline": {"bound": "hbm", "kernel": "pool_score_kernel",
                          "bound_detail": "random-row gather of ~150-300 MB tables (L2 miss, served by HBM + "
                                          "Infinity Cache); 8 TB/s is the HBM spec, the gather ceiling is the "

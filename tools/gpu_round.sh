@@ -25,10 +25,10 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
       rc=$?; echo "smoke rc=$rc" >> "$OUT/status.txt"; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 700 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+      timeout -k 10 700 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
       rc=$?; echo "bench rc=$rc" >> "$OUT/status.txt"; [ $rc -eq 0 ] || exit $rc ;;
     gloo2)
-      timeout -k 10 500 python -u bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
+      timeout -k 10 500 python -u bench.py --full --gpus 2 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
         > "$OUT/bench_gloo2.json" 2> "$OUT/bench_gloo2.err"
       rc=$?; echo "gloo2 rc=$rc" >> "$OUT/status.txt"; [ $rc -eq 0 ] || exit $rc ;;
     trainbench)

@@ -10,7 +10,7 @@ OUT=${1:-gpurun_out/prof_r2}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o bench --output-format csv -- \
-  python bench.py --steps 10 --warmup 3 --no-extra --cpu-seconds 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err" || exit 1
+  python bench.py --full --steps 10 --warmup 3 --no-extra --cpu-seconds 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err" || exit 1
 for cfg in "latent bf16" "final bf16" "latent fp32"; do
   set -- $cfg
   for ctr in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do

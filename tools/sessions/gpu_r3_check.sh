@@ -7,4 +7,4 @@ timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method threa
   tests/test_auc_gate.py tests/test_eval_multirank.py > "$OUT/pytest_new.log" 2>&1 && \
 timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu tests \
   > "$OUT/pytest_gpu.log" 2>&1 && \
-timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"

@@ -6,4 +6,4 @@ OUT=gpurun_out/${1:-r3lat3}
 mkdir -p "$OUT"
 timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests/test_latent_attention_autograd.py \
   tests/test_final_attention_autograd.py > "$OUT/pytest.log" 2>&1 && \
-timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"

@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
   "tests/test_gpu_parity.py::test_threads_on_their_own_streams_bit_identical" \
   "tests/test_gpu_parity.py::test_transform_rows_independent_of_the_cut" \
   "tests/test_gpu_parity.py::test_sharded_table_overlapped_rccl_single_rank" > "$OUT/pytest.log" 2>&1 && \
-timeout -k 10 600 python -u bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
+timeout -k 10 600 python -u bench.py --full --gpus 2 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
   > "$OUT/bench_gloo2.json" 2> "$OUT/bench_gloo2.err" && \
-timeout -k 10 600 python -u bench.py --gpus 4 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
+timeout -k 10 600 python -u bench.py --full --gpus 4 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
   > "$OUT/bench_gloo4.json" 2> "$OUT/bench_gloo4.err"

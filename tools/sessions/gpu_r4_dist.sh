@@ -4,5 +4,5 @@
 set -o pipefail
 OUT=gpurun_out/${1:-r4dist}
 mkdir -p "$OUT"
-timeout -k 10 600 python -u bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 > "$OUT/bench_gloo2.json" 2> "$OUT/bench_gloo2.err"
+timeout -k 10 600 python -u bench.py --full --gpus 2 --backend gloo --steps 3 --warmup 1 > "$OUT/bench_gloo2.json" 2> "$OUT/bench_gloo2.err"
 echo "gloo2 rc=$?" > "$OUT/status.txt"

@@ -10,7 +10,7 @@ echo "smoke ok" > "$OUT/status.txt"
 timeout -k 10 1000 python -u -m pytest -x -q --timeout 600 --timeout-method thread -m gpu tests \
   > "$OUT/pytest_gpu.log" 2>&1 || exit 2
 echo "pytest ok" >> "$OUT/status.txt"
-timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 3
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 3
 echo "bench ok" >> "$OUT/status.txt"
 timeout -k 10 300 python -u tools/gemm_ab.py --m 1030000 --libs new=news_recommendation_project_v2_amd/libnewsrec_hip.so \
   --rounds 3 --reps 5 --shapes final.l3,latent.ff2 > "$OUT/gemm_ab_m1030000.jsonl" 2> "$OUT/gemm_ab_m1030000.err" || exit 4

@@ -13,7 +13,7 @@ rc=$?
 echo "pytest rc=$rc" > "$OUT/status.txt"
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 && \
-timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" && \
-timeout -k 10 400 python -u bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" && \
+timeout -k 10 400 python -u bench.py --full --gpus 2 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
   > "$OUT/bench_gloo2.json" 2> "$OUT/bench_gloo2.err"
 echo "tail rc=$?" >> "$OUT/status.txt"

@@ -22,7 +22,7 @@ timeout -k 10 1000 python -u -m pytest -v --timeout 600 --timeout-method thread 
   --deselect tests/test_comm.py --deselect tests/test_residency.py tests/ > "$OUT/pytest_gpu.log" 2>&1
 rc=$?; echo "suite rc=$rc" >> "$OUT/status.txt"; ok $rc || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 && \
-timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" && \
-timeout -k 10 400 python -u bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" && \
+timeout -k 10 400 python -u bench.py --full --gpus 2 --backend gloo --steps 3 --warmup 1 --cpu-seconds 0 \
   > "$OUT/bench_gloo2.json" 2> "$OUT/bench_gloo2.err"
 echo "tail rc=$?" >> "$OUT/status.txt"
