@@ -19,10 +19,12 @@ INCLUDE = Path(__file__).resolve().parent.parent / "include"
 # translation units of libnewsrec_hip.so, in link order (also the hash order)
 HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip", "encoder.hip", "train.hip",
                "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip")
+# the headers they include (every object is rebuilt when one changes), hashed after the sources
+HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", INCLUDE / "newsrec.h")
 
 
 def hip_source_files() -> list:
-    return [CSRC / s for s in HIP_SOURCES] + [CSRC / "nr_common.h", INCLUDE / "newsrec.h"]
+    return [CSRC / s for s in HIP_SOURCES] + list(HIP_HEADERS)
 
 
 def source_hash(files: Sequence[Path]) -> Optional[str]:

@@ -102,7 +102,7 @@ constexpr int64_t kChunk = 262144;
 extern "C" int nr_version(void) { return 100; }
 
 // Hash of the sources this library was compiled from (_lib.source_hash over
-// csrc/*.hip + nr_common.h + include/newsrec.h, passed by the build as
+// csrc/*.hip + nr_common.h + nr_rows.h + include/newsrec.h, passed by the build as
 // -DNR_BUILD_HASH).  The tag is kept in the binary so the build can read it
 // without loading the library; _lib.load() refuses a mismatching library.
 #ifndef NR_BUILD_HASH

@@ -411,7 +411,6 @@ __global__ __launch_bounds__(256) void encoder_positions_kernel(int64_t n_seq, c
   if (flag && status) atomicOr(status, flag);
 }
 
-static int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 struct EncWs {  // workspace carve-up of nr_encoder_forward
   int64_t x, big, ctx, tmp, pos, cu32, qoff, cu64, total;

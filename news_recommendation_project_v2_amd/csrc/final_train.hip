@@ -38,6 +38,7 @@
 // on the exact-f32 MFMA tile kernels, with explicit transposes for the weight
 // grads.
 #include "nr_common.h"
+#include "nr_rows.h"
 
 namespace nr {
 namespace ft {
@@ -52,80 +53,7 @@ constexpr int kSplit = 8;
 constexpr int kSqTn = 512, kSqFold = (1024 / 64) * (4096 / 64), kSqBias = (3 * 4096 + 1024) / 64, kSqLn = 1024 / 64;
 constexpr int kSqParts = kSqTn + kSqFold + kSqBias + kSqLn;
 
-static int64_t pad64(int64_t n) { return n < 64 ? 64 : (n + 63) / 64 * 64; }
-static int64_t al(int64_t b) { return (b + 255) / 256 * 256; }
-
 // ------------------------------------------------------------------ small kernels
-template <typename T>
-__device__ __forceinline__ void ld4(const T* p, float v[4]) {
-  if constexpr (sizeof(T) == 4) {
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  } else {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    v[0] = bf16_lo(u.x); v[1] = bf16_hi(u.x); v[2] = bf16_lo(u.y); v[3] = bf16_hi(u.y);
-  }
-}
-template <typename T>
-__device__ __forceinline__ void st4(T* p, const float v[4]) {
-  if constexpr (sizeof(T) == 4) {
-    *reinterpret_cast<float4*>(p) = float4{v[0], v[1], v[2], v[3]};
-  } else {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<b4*>(p) = __builtin_convertvector(f4{v[0], v[1], v[2], v[3]}, b4);
-  }
-}
-
-// The token model's output row of news n (g_mlp_layernorm without its affine, eps
-// 1e-12: the arithmetic of gather_ln_kernel, rowops.hip, so the bits are those of
-// nr_gather_layernorm): lane's 4 x 4 columns 256 j + 4 lane .. +3 of xhat.  TT =
-// the token states' type (f32 / bf16 / f16).
-template <typename TT>
-__device__ __forceinline__ void tok_xhat(const TT* row, int lane, float (&v)[4][4]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const TT* p = row + j * 256 + lane * 4;
-    if constexpr (sizeof(TT) == 4) {
-      ld4<float>((const float*)p, v[j]);
-    } else if constexpr (std::is_same<TT, _Float16>::value) {
-      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-      const h4 h = *reinterpret_cast<const h4*>(p);
-      v[j][0] = (float)h[0]; v[j][1] = (float)h[1]; v[j][2] = (float)h[2]; v[j][3] = (float)h[3];
-    } else {
-      ld4<__bf16>((const __bf16*)p, v[j]);
-    }
-  }
-  float sm = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sm += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-  const float mean = wave_sum(sm) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const float d = v[j][t] - mean;
-      q = fmaf(d, d, q);
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + 1e-12f);
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) v[j][t] = (v[j][t] - mean) * rstd;
-}
-
-struct ZList {  // zero up to 8 f32 ranges in one launch
-  float* p[8];
-  int64_t len[8];
-  int n;
-};
-__global__ __launch_bounds__(256) void zero_kernel(ZList z) {
-  for (int i = 0; i < z.n; ++i)
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < z.len[i]; j += (int64_t)gridDim.x * 256)
-      z.p[i][j] = 0.f;
-}
-
 // Slot rows i < Hp: xhat = the token LN (no affine) of the last token of news
 // hist[i], computed here per slot from the token states (no [U][D] LN table:
 // Hs ~ U at the benchmark batch, and the token rows are half the bytes),
@@ -384,23 +312,19 @@ __global__ __launch_bounds__(256) void fixup_drelu_cs_kernel(int64_t cs_row0, in
   float y[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (r < rows) {
     float v[8], w[8], rv[8];
-    ld4<float>(P + r * N + c, v);
-    ld4<float>(P + r * N + c + 4, v + 4);
+    ld8<float>(P + r * N + c, v);
     for (int s = 1; s < parts; ++s) {
-      ld4<float>(P + ((int64_t)s * rows + r) * N + c, w);
-      ld4<float>(P + ((int64_t)s * rows + r) * N + c + 4, w + 4);
+      ld8<float>(P + ((int64_t)s * rows + r) * N + c, w);
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] += w[k];
     }
-    ld4<TA>(R + r * ldr + c, rv);
-    ld4<TA>(R + r * ldr + c + 4, rv + 4);
+    ld8<TA>(R + r * ldr + c, rv);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float x = v[k] + 0.f;  // (no bias: as the fixup's x + 0)
       y[k] = rv[k] > 0.f ? x * scale : 0.f;
     }
-    st4<TA>(C + r * ldc + c, y);
-    st4<TA>(C + r * ldc + c + 4, y + 4);
+    st8<TA>(C + r * ldc + c, y);
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) red[rg][8 * cl + k] = y[k];  // pre-rounding, as the persistent GEMM's CS epilogue
@@ -539,7 +463,7 @@ static Layout layout(int dtype, int64_t B, int64_t U, int64_t Hs, int ncu) {
   L.csr = L.mm < L.Hp ? L.mm / 128 + (L.Hp - L.mm + 31) / 32 : L.csr3;
   const int64_t Hp = L.Hp, es = L.es, Bp = pad64(B);
   int64_t o = 0;
-  auto take = [&](int64_t bytes) { const int64_t r = o; o += al(bytes); return r; };
+  auto take = [&](int64_t bytes) { const int64_t r = o; o += align256(bytes); return r; };
   L.xpair = take(2 * B * D * 4);
   L.S = take(Hp * D * es); L.XH = take(Hp * D * es); L.X1 = take(Hp * H * es); L.X2 = take(Hp * H * es); L.XP = take(Hp * 2 * D * es);
   L.Y = take(Hp * H * es);
@@ -631,8 +555,7 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
     const int64_t zn[4] = {H, H, D, H};
     zl.n = 4;
     for (int i = 0; i < zl.n; ++i) { zl.p[i] = zp[i]; zl.len[i] = zn[i]; }
-    hipLaunchKernelGGL(zero_kernel, dim3(64), dim3(256), 0, st, zl);
-    NR_CHECK_LAUNCH("nr_final_train_step (zero)");
+    NR_FT(zero_ranges(zl, 64, st));
   }
   // ---- forward
   // the slots' S and XH: the token LN of each slot's news (one kernel, no [U][D] table)
@@ -790,8 +713,7 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
       hipLaunchKernelGGL(sq_total_kernel, dim3(1), dim3(256), 0, st, (int64_t)kSqParts, sqp, a.sumsq);
       NR_CHECK_LAUNCH("nr_final_train_step (grad norm)");
     } else if (a.sumsq) {  // f32 mode: over the gradient arrays
-      hipLaunchKernelGGL(zero_kernel, dim3(1), dim3(256), 0, st, ZList{{a.sumsq}, {1}, 1});
-      NR_CHECK_LAUNCH("nr_final_train_step (zero)");
+      NR_FT(zero_ranges(ZList{1, {a.sumsq}, {1}}, 1, st));
       float* gs[11] = {a.g_tok_g, a.g_tok_b, a.g_W1, a.g_b1, a.g_W2, a.g_b2, a.g_W3, a.g_b3, a.g_W4, a.g_b4, a.g_W5};
       const int64_t gn[11] = {D, D, H * D, H, H * H, H, D * H, D, H * D, H, D * H};
       for (int i = 0; i < 11; ++i) NR_FT(nr_sumsq(gn[i], gs[i], a.sumsq, st));
@@ -829,7 +751,7 @@ extern "C" int nr_final_train_step(const nr_final_train_args* args, void* ws, in
   NR_CHECK_ARG(a.p >= 0.f && a.p < 1.f, "nr_final_train_step: dropout p outside [0, 1)");
   // bf16: the persistent GEMM (the column-sum epilogues have no other kernel) addresses
   // its [Hp][4096] operands through 32-bit buffer offsets; refuse before any launch
-  NR_CHECK_ARG(a.dtype != NR_BF16 || nr::ft::pad64(a.Hs) * nr::ft::H * 2 <= 0xFFFFFFFFll,
+  NR_CHECK_ARG(a.dtype != NR_BF16 || nr::pad64(a.Hs) * nr::ft::H * 2 <= 0xFFFFFFFFll,
                "nr_final_train_step: bf16 batch of %lld history slots exceeds the persistent GEMM's 4 GiB operand "
                "range (at most %lld)", (long long)a.Hs, 0xFFFFFFFFll / (2 * nr::ft::H) / 64 * 64);
   NR_CHECK_DEVICE("nr_final_train_step", a.tok_last, a.hist_idx, a.hist_off, a.pos, a.neg, a.tok_g, a.tok_b, a.W1,

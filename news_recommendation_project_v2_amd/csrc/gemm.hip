@@ -16,6 +16,7 @@
 // rows are bank-conflict free; global->register prefetch of tile k+1 overlaps
 // the MFMAs of tile k, one barrier per K tile.
 #include "nr_common.h"
+#include "nr_rows.h"
 
 #include <atomic>
 
@@ -919,12 +920,7 @@ __device__ __forceinline__ uint4 swap_pair16(uint2 a, uint2 b) {
   return uint4{sx[0], sy[0], sx[1], sy[1]};
 }
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {  // one v_cvt_pk_bf16_f32 (RNE)
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
 __device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {  // v_pk_max_i16 with 0
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(i16x2, v), i16x2{0, 0}));
 }

@@ -31,42 +31,12 @@
 // GEMMs: nr's MFMA kernels (gemm.hip: persistent bf16, grouped strided batches);
 // everything else here is HBM-bound row work (one wave per row, 16-B lanes).
 #include "nr_common.h"
+#include "nr_rows.h"
 
 namespace nr {
 namespace lt {
 
 constexpr int D = 1024, F = 4096, S = 512, NL = 64, HEADS = 8, DH = 512;
-
-template <typename T>
-__device__ __forceinline__ void ld4(const T* p, float v[4]) {
-  if constexpr (sizeof(T) == 4) {
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  } else {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    v[0] = bf16_lo(u.x); v[1] = bf16_hi(u.x); v[2] = bf16_lo(u.y); v[3] = bf16_hi(u.y);
-  }
-}
-
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{a, b}, b2));
-}
-
-template <typename T>
-__device__ __forceinline__ void st4(T* p, const float v[4]) {
-  if constexpr (sizeof(T) == 4) *reinterpret_cast<float4*>(p) = float4{v[0], v[1], v[2], v[3]};
-  else *reinterpret_cast<uint2*>(p) = uint2{pk2(v[0], v[1]), pk2(v[2], v[3])};
-}
-
-template <typename T>
-__device__ __forceinline__ void st4z(T* p) {
-  const float z[4] = {0.f, 0.f, 0.f, 0.f};
-  st4<T>(p, z);
-}
-
-__device__ __forceinline__ float gelu_x(float g) { return 0.5f * g * (1.0f + erff(g * 0.70710678118654752440f)); }
 
 // bf16 step only (the f32 step keeps erff / expf): for two values, h = erfc(|g| /
 // sqrt 2) / 2 and e = exp(-g^2 / 2) with one packed polynomial and v_exp_f32, no
@@ -93,28 +63,6 @@ __device__ __forceinline__ void erfc_half2(f32x2v g, f32x2v& h, f32x2v& e) {
   h = (f32x2v){__builtin_amdgcn_exp2f(w.x), __builtin_amdgcn_exp2f(w.y)};
 }
 
-template <typename T>
-__device__ __forceinline__ void ld8(const T* p, float v[8]) {
-  if constexpr (sizeof(T) == 4) {
-    ld4<float>(p, v);
-    ld4<float>(p + 4, v + 4);
-  } else {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    v[0] = bf16_lo(u.x); v[1] = bf16_hi(u.x); v[2] = bf16_lo(u.y); v[3] = bf16_hi(u.y);
-    v[4] = bf16_lo(u.z); v[5] = bf16_hi(u.z); v[6] = bf16_lo(u.w); v[7] = bf16_hi(u.w);
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void st8(T* p, const float v[8]) {
-  if constexpr (sizeof(T) == 4) {
-    st4<float>(p, v);
-    st4<float>(p + 4, v + 4);
-  } else {
-    *reinterpret_cast<uint4*>(p) = uint4{pk2(v[0], v[1]), pk2(v[2], v[3]), pk2(v[4], v[5]), pk2(v[6], v[7])};
-  }
-}
-
 // sum of v over the 256 threads of the block (4 waves), returned to every thread
 __device__ __forceinline__ float block_sum(float v, float* scratch /* [4] */) {
   v = wave_sum(v);
@@ -125,13 +73,6 @@ __device__ __forceinline__ float block_sum(float v, float* scratch /* [4] */) {
 }
 
 // ------------------------------------------------------------------ small helpers
-// zero up to 16 f32 ranges in one launch (the step's accumulated gradients)
-struct ZList {
-  int n;
-  float* p[17];
-  int64_t len[17];
-};
-
 // *out += sum over up to 8 f32 ranges of their squares (gradients a stream of the step
 // finished writing) or, for ranges added with square = false, of their values (the
 // per-workgroup sums of squares a weight-grad GEMM's epilogue left); 16-B lane
@@ -159,29 +100,7 @@ __global__ __launch_bounds__(256) void sq_list_kernel(SqList q, float* __restric
       for (int64_t k = t; k < n; k += gs) s += x[k];
       continue;
     }
-    const int64_t n4 = ((uintptr_t)x & 15) == 0 ? n / 4 : 0;
-    const float4* x4 = reinterpret_cast<const float4*>(x);
-    int64_t i = t;
-    for (; i + 3 * gs < n4; i += 4 * gs) {
-      float4 v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = x4[i + k * gs];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        s = fmaf(v[k].x, v[k].x, s);
-        s = fmaf(v[k].y, v[k].y, s);
-        s = fmaf(v[k].z, v[k].z, s);
-        s = fmaf(v[k].w, v[k].w, s);
-      }
-    }
-    for (; i < n4; i += gs) {
-      const float4 v = x4[i];
-      s = fmaf(v.x, v.x, s);
-      s = fmaf(v.y, v.y, s);
-      s = fmaf(v.z, v.z, s);
-      s = fmaf(v.w, v.w, s);
-    }
-    for (int64_t k = 4 * n4 + t; k < n; k += gs) s = fmaf(x[k], x[k], s);
+    s = sumsq_range(x, n, t, gs, s);
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
@@ -201,11 +120,6 @@ static int sq_list(const SqList& q, float* out, hipStream_t st) {
   hipLaunchKernelGGL(sq_list_kernel, dim3((unsigned)(g < 1 ? 1 : g < 1024 ? g : 1024)), dim3(256), 0, st, q, out);
   NR_CHECK_LAUNCH("nr_latent_train_step (grad sumsq)");
   return NR_OK;
-}
-__global__ __launch_bounds__(256) void zero_kernel(ZList z) {
-  for (int i = 0; i < z.n; ++i)
-    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < z.len[i]; k += (int64_t)gridDim.x * 256)
-      z.p[i][k] = 0.f;
 }
 
 // dst[i] = sum_p src[p * pstride + i] over n contiguous f32 (split-K partials).  Block =
@@ -248,42 +162,10 @@ static int sum_parts(const float* src, int parts, int64_t pstride, float* dst, i
 
 // ------------------------------------------------------------------ forward rows
 // E row of news r: the token LayerNorm (g_mlp_layernorm, eps 1e-12, affine tg / tb)
-// of its last token state (TT = f32 / bf16 / f16), the arithmetic of rowops.hip's
-// gather_ln_kernel (nr_gather_layernorm): lane's columns 256 j + 4 lane .. +3.  The
-// step never stores the [U][1024] E table: the slot gather, the head (pos / neg
-// rows) and the LN_q backward recompute the rows they read from the token states.
-template <typename TT>
-__device__ __forceinline__ void tok_xhat(const TT* __restrict__ row, int lane, float (&v)[4][4]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const TT* p = row + j * 256 + lane * 4;
-    if constexpr (std::is_same<TT, _Float16>::value) {
-      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-      const h4 h = *reinterpret_cast<const h4*>(p);
-      v[j][0] = (float)h[0]; v[j][1] = (float)h[1]; v[j][2] = (float)h[2]; v[j][3] = (float)h[3];
-    } else {
-      ld4<TT>(p, v[j]);
-    }
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const float d = v[j][t] - mean;
-      q = fmaf(d, d, q);
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + 1e-12f);
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) v[j][t] = (v[j][t] - mean) * rstd;
-}
-// the E row: xhat tg + tb (the module's affine after tok_xhat's normalisation)
+// of its last token state (TT = f32 / bf16 / f16): tok_xhat (nr_rows.h), then the
+// module's affine.  The step never stores the [U][1024] E table: the slot gather,
+// the head (pos / neg rows) and the LN_q backward recompute the rows they read
+// from the token states.
 template <typename TT>
 __device__ __forceinline__ void tok_ln(const TT* __restrict__ row, int lane, const float* __restrict__ tg,
                                        const float* __restrict__ tb, float (&v)[4][4]) {
@@ -342,16 +224,8 @@ __global__ __launch_bounds__(256) void gather_ln_kernel(int64_t n, int64_t nvali
     }
     float v[4][4];
     tok_ln<TT>(tok + (int64_t)r * D, lane, tg, tb, v);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { const float d = v[j][t] - mean; q = fmaf(d, d, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+    float mean, rstd;
+    row_stats4<4>(v, (float)D, eps, mean, rstd);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int c = j * 256 + lane * 4;
@@ -379,7 +253,7 @@ template <typename TA>
 __device__ __forceinline__ void geglu4(const float (&a)[4], const float (&g)[4], float (&z)[4]) {
   if constexpr (sizeof(TA) == 4) {
 #pragma unroll
-    for (int t = 0; t < 4; ++t) z[t] = a[t] * gelu_x(g[t]);
+    for (int t = 0; t < 4; ++t) z[t] = a[t] * gelu_exact(g[t]);
   } else {
     f32x2v g0 = {g[0], g[1]}, g1 = {g[2], g[3]};
     gelu_erf2x2(g0, g1);
@@ -726,16 +600,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int64_t n, int64_t nvalid, 
           v[j][t] = xt[j][t] * tg[e] + tb[e];
         }
     }
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sum += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-    const float mean = wave_sum(sum) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { const float d = v[j][t] - mean; q = fmaf(d, d, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+    float mean, rstd;
+    row_stats4<4>(v, (float)D, eps, mean, rstd);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -823,12 +689,10 @@ __global__ __launch_bounds__(256) void lnc_bwd_kernel(const float* __restrict__ 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = (int)blockIdx.x * 4 + wave;  // 16 blocks x 4 waves = the 64 latents
   float v[4][4], g[4][4], dy[4][4];
-  float sum = 0.f;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int c = j * 256 + lane * 4;
     ld4<float>(x + row * D + c, v[j]);
-    sum += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
 #pragma unroll
     for (int t = 0; t < 4; ++t) dy[j][t] = 0.f;
     for (int s = 0; s < ns; ++s) {
@@ -838,13 +702,8 @@ __global__ __launch_bounds__(256) void lnc_bwd_kernel(const float* __restrict__ 
       for (int t = 0; t < 4; ++t) dy[j][t] += p4[t];
     }
   }
-  const float mean = wave_sum(sum) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { const float d = v[j][t] - mean; q = fmaf(d, d, q); }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+  float mean, rstd;
+  row_stats4<4>(v, (float)D, eps, mean, rstd);
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -904,13 +763,13 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(TBatch tb) {
   const int64_t rows = tb.rows[p], rpad = tb.rows_pad[p], cols = tb.cols[p], lds = tb.lds[p], ldd = tb.ldd[p];
   const int np = tb.parts[p];
   const int64_t ps = tb.pstride[p];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  auto val = [&](int64_t r, int64_t c) {
+  auto val = [=](int64_t r, int64_t c) {
     float v = (float)src[r * lds + c];
     for (int q = 1; q < np; ++q) v += (float)src[q * ps + r * lds + c];
     return v;
   };
   if (!tb.transpose[p]) {
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
 #pragma unroll 4
     for (int k = 0; k < 16; ++k) {
       const int64_t r = r0 + ty + 4 * k, c = c0 + tx;
@@ -918,55 +777,20 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(TBatch tb) {
     }
     return;
   }
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int rr = ty + 4 * k;
-    const int64_t r = r0 + rr, c = c0 + tx;
-    tile[rr][tx] = (r < rows && c < cols) ? val(r, c) : 0.f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int cc = ty + 4 * k;
-    const int64_t c = c0 + cc, r = r0 + tx;
-    if (c < cols && r < rpad) dst[c * ldd + r] = (TO)tile[tx][cc];
-  }
+  transpose_tile<TO>(val, dst, ldd, rows, rpad, cols, r0, c0, tile);
 }
 
-// 16-bit -> 16-bit transposes with 16-B global accesses (train.hip's
-// transpose16_kernel, batched): rows_pad / cols / strides multiples of 8.
+// 16-bit -> 16-bit transposes with 16-B global accesses (transpose_tile16,
+// batched): rows_pad / cols / strides multiples of 8.
 __global__ __launch_bounds__(256) void transpose16_batched_kernel(TBatch tb) {
-  constexpr int P = 66;
-  __shared__ uint16_t tile[64 * P];
+  __shared__ uint16_t tile[64 * kT16Pitch];
   const int t = (int)blockIdx.x;
   int p = 0;
   while (p + 1 < tb.n && t >= tb.tile_end[p]) ++p;
   const int local = t - (p ? tb.tile_end[p - 1] : 0);
   const int64_t r0 = (int64_t)(local / tb.tiles_x[p]) * 64, c0 = (int64_t)(local % tb.tiles_x[p]) * 64;
-  const uint16_t* src = (const uint16_t*)tb.src[p];
-  uint16_t* dst = (uint16_t*)tb.dst[p];
-  const int64_t rows = tb.rows[p], rpad = tb.rows_pad[p], cols = tb.cols[p], lds = tb.lds[p], ldd = tb.ldd[p];
-  const int th = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int rr = (th >> 3) + 32 * k, ch = th & 7;
-    const int64_t r = r0 + rr, c = c0 + 8 * ch;
-    uint4 u = make_uint4(0, 0, 0, 0);
-    if (r < rows && c < cols) u = *reinterpret_cast<const uint4*>(src + r * lds + c);
-    uint32_t* d = reinterpret_cast<uint32_t*>(tile + rr * P + 8 * ch);
-    d[0] = u.x; d[1] = u.y; d[2] = u.z; d[3] = u.w;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int oc = (th >> 3) + 32 * k, rc = th & 7;
-    const int64_t c = c0 + oc, r = r0 + 8 * rc;
-    uint32_t w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      w[j] = (uint32_t)tile[(8 * rc + 2 * j) * P + oc] | ((uint32_t)tile[(8 * rc + 2 * j + 1) * P + oc] << 16);
-    if (c < cols && r < rpad) *reinterpret_cast<uint4*>(dst + c * ldd + r) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
+  transpose_tile16((const uint16_t*)tb.src[p], tb.lds[p], (uint16_t*)tb.dst[p], tb.ldd[p], tb.rows[p], tb.rows_pad[p],
+                   tb.cols[p], r0, c0, tile);
 }
 
 struct TList {
@@ -1087,9 +911,6 @@ int launch_sumconv(const SCList& l, hipStream_t s) {
   return NR_OK;
 }
 
-static int64_t pad64(int64_t n) { return n < 64 ? 64 : (n + 63) / 64 * 64; }
-static int64_t al(int64_t b) { return (b + 255) / 256 * 256; }
-
 constexpr int kKVParts = 4;    // split-K slices of KV = latn Wkv^T (K = 1024 -> 256)
 constexpr int kHParts = 16;    // split-K slices of the m GEMM (K = 4096 -> 256)
 constexpr int kZParts = 4;     // split-K slices of dZ = dmc W2 (K = 1024 -> 256)
@@ -1121,7 +942,7 @@ static Layout layout(int dtype, int64_t B, int64_t U, int64_t Hs) {
   L.es = dtype == NR_F32 ? 4 : 2;
   const int64_t Hp = L.Hp, Hpp = L.Hpp, Bp = L.Bp, es = L.es;
   int64_t o = 0;
-  auto take = [&](int64_t bytes) { const int64_t r = o; o += al(bytes); return r; };
+  auto take = [&](int64_t bytes) { const int64_t r = o; o += align256(bytes); return r; };
   L.E = take(2 * Bp * D * 4);  // Epn: E[pos] rows then E[neg] rows (no [U][D] E table)
   L.Xpn = take(2 * Bp * D * 4);  // the same rows' token-LN xhat
   // X, P, dH1, dS hold Hpp rows: the dA / dBt K-slices read them directly (bf16: TN
@@ -1246,8 +1067,7 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
     z.p[14] = (float*)(dS + Hp * S); z.len[14] = tail * S;
     z.n = 15;
     if (a.sumsq) { z.p[15] = a.sumsq; z.len[15] = 1; z.n = 16; }
-    hipLaunchKernelGGL(zero_kernel, dim3(1024), dim3(256), 0, st, z);
-    NR_LT_CHECK("zero");
+    if ((rc = zero_ranges(z, 1024, st))) return rc;
   }
   // (one box, interleaved, ms/step: all of this serial on one stream 1.195-1.215, every
   // weight transpose before the fold on the side stream 1.20, this layout 1.185 --

@@ -101,6 +101,19 @@ int gemm_group_tn_dispatch(int dtype_out, const GemmProblem* probs, int n, hipSt
 int inv_norm_dispatch(int dtype, int64_t rows, int64_t dim, const void* x, int64_t ldx, float eps,
                       float* out, hipStream_t s);
 
+// Zero up to 17 f32 ranges in one launch of `blocks` workgroups (train.hip): the
+// training steps' accumulated gradients.
+struct ZList {
+  int n;
+  float* p[17];
+  int64_t len[17];
+};
+int zero_ranges(const ZList& z, int blocks, hipStream_t s);
+
+// workspace sizes: row counts padded to whole 64-row tiles, byte counts to 256
+static inline int64_t pad64(int64_t n) { return n < 64 ? 64 : (n + 63) / 64 * 64; }
+static inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -3,66 +3,9 @@
 // whole row lives in registers, so every element is read from HBM once and
 // reductions are 64-lane butterflies (no LDS).
 #include "nr_common.h"
+#include "nr_rows.h"
 
 namespace nr {
-
-// Lane-local load of 4 consecutive elements at element offset `e` (f32 or bf16).
-template <typename T>
-__device__ __forceinline__ void load4(const T* p, float (&v)[4]) {
-  if constexpr (sizeof(T) == 4) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-  } else {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    v[0] = bf16_lo(u.x); v[1] = bf16_hi(u.x); v[2] = bf16_lo(u.y); v[3] = bf16_hi(u.y);
-  }
-}
-
-template <>
-__device__ __forceinline__ void load4<_Float16>(const _Float16* p, float (&v)[4]) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  const h4 h = *reinterpret_cast<const h4*>(p);
-  v[0] = (float)h[0]; v[1] = (float)h[1]; v[2] = (float)h[2]; v[3] = (float)h[3];
-}
-
-template <typename T>
-__device__ __forceinline__ void store4(T* p, const float (&v)[4]) {
-  if constexpr (sizeof(T) == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    __bf16 b[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-    *reinterpret_cast<uint2*>(p) = *reinterpret_cast<uint2*>(b);
-  }
-}
-
-// 16-byte lane vectors: E = 16 / sizeof(T) elements.
-template <typename T>
-__device__ __forceinline__ void load16(const T* p, float* v) {
-  const uint4 u = *reinterpret_cast<const uint4*>(p);
-  if constexpr (sizeof(T) == 4) {
-    v[0] = __uint_as_float(u.x); v[1] = __uint_as_float(u.y); v[2] = __uint_as_float(u.z); v[3] = __uint_as_float(u.w);
-  } else {
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { v[2 * q] = bf16_lo(w[q]); v[2 * q + 1] = bf16_hi(w[q]); }
-  }
-}
-
-template <typename TO, int E>
-__device__ __forceinline__ void storeE(TO* p, const float* v) {
-  if constexpr (sizeof(TO) == 4) {
-#pragma unroll
-    for (int q = 0; q < E; q += 4) *reinterpret_cast<float4*>(p + q) = make_float4(v[q], v[q + 1], v[q + 2], v[q + 3]);
-  } else {
-#pragma unroll
-    for (int q = 0; q < E; q += 8) {
-      __bf16 b8[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) b8[t] = (__bf16)v[q + t];
-      *reinterpret_cast<uint4*>(p + q) = *reinterpret_cast<const uint4*>(b8);
-    }
-  }
-}
 
 // torch.nn.LayerNorm semantics: biased variance, y = (x - mean) * rsqrt(var + eps) * g + b.
 // One wave per row, rows grid-strided over a bounded grid (tiny per-row work
@@ -97,7 +40,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(int64_t rows, const TI* 
     for (int j = 0; j < NJ; ++j) {
       const int c = j * 64 + lane;
       if (CH % 64 == 0 || c < CH) {
-        load16<TI>(x + row * ldx + c * E, v[j]);
+        if constexpr (E == 4) ld4<TI>(x + row * ldx + c * E, v[j]);
+        else ld8<TI>(x + row * ldx + c * E, v[j]);
 #pragma unroll
         for (int t = 0; t < E; ++t) s += v[j][t];
       }
@@ -123,7 +67,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(int64_t rows, const TI* 
         float o[E];
 #pragma unroll
         for (int t = 0; t < E; ++t) o[t] = (v[j][t] - mean) * rstd * gv[j][t] + bv[j][t];
-        storeE<TO, E>(y + row * ldy + c * E, o);
+        if constexpr (E == 4) st4<TO>(y + row * ldy + c * E, o);
+        else st8<TO>(y + row * ldy + c * E, o);
       }
     }
   }
@@ -163,7 +108,8 @@ __global__ __launch_bounds__(256) void row_stats_kernel(int64_t rows, const T* _
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      load16<T>(x + row * ldx + (j * 64 + lane) * E, v[j]);
+      if constexpr (E == 4) ld4<T>(x + row * ldx + (j * 64 + lane) * E, v[j]);
+      else ld8<T>(x + row * ldx + (j * 64 + lane) * E, v[j]);
 #pragma unroll
       for (int t = 0; t < E; ++t) s += v[j][t];
     }
@@ -193,7 +139,7 @@ __global__ __launch_bounds__(256) void inv_norm_kernel(int64_t rows, const T* __
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     float v[4];
-    load4<T>(x + row * ldx + j * 256 + lane * 4, v);
+    ld4<T>(x + row * ldx + j * 256 + lane * 4, v);
 #pragma unroll
     for (int t = 0; t < 4; ++t) q = fmaf(v[t], v[t], q);
   }
@@ -301,21 +247,10 @@ __global__ __launch_bounds__(256) void gather_ln_kernel(int64_t n, const TI* __r
   const int64_t row = row_idx ? row_idx[i] : i;
   float v[NJ][4];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) load4<TI>(x + row * ldx + j * 256 + lane * 4, v[j]);
+  for (int j = 0; j < NJ; ++j) ld4<TI>(x + row * ldx + j * 256 + lane * 4, v[j]);
   for (int l = 0; l < n_ln; ++l) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-    const float mean = wave_sum(s) / (float)DIM;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float d = v[j][t] - mean;
-        q = fmaf(d, d, q);
-      }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)DIM + eps);
+    float mean, rstd;
+    row_stats4<NJ>(v, (float)DIM, eps, mean, rstd);
     const float* gl = g ? g + (int64_t)l * DIM : nullptr;
     const float* bl = b ? b + (int64_t)l * DIM : nullptr;
 #pragma unroll
@@ -327,7 +262,7 @@ __global__ __launch_bounds__(256) void gather_ln_kernel(int64_t n, const TI* __r
       }
   }
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) store4<float>(y + i * ldy + j * 256 + lane * 4, v[j]);
+  for (int j = 0; j < NJ; ++j) st4<float>(y + i * ldy + j * 256 + lane * 4, v[j]);
 }
 
 int gather_ln_dispatch(int dti, int64_t n, int64_t dim, const void* x, int64_t ldx, const int64_t* row_idx,

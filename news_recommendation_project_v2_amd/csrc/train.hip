@@ -9,6 +9,7 @@
 // kernel; the weight-grad and data-grad operands are produced by the LDS
 // transpose below.  Everything here is HBM-bound row / reduction work.
 #include "nr_common.h"
+#include "nr_rows.h"
 
 namespace nr {
 
@@ -39,56 +40,17 @@ template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void transpose_kernel(int64_t rows, int64_t cols, const TI* __restrict__ src,
                                                         int64_t lds, TO* __restrict__ dst, int64_t ldd) {
   __shared__ float tile[64][65];
-  const int64_t r0 = (int64_t)blockIdx.y * 64, c0 = (int64_t)blockIdx.x * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int rr = ty + 4 * k;
-    const int64_t r = r0 + rr, c = c0 + tx;
-    tile[rr][tx] = (r < rows && c < cols) ? ldf<TI>(src + r * lds + c) : 0.f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int cc = ty + 4 * k;
-    const int64_t c = c0 + cc, r = r0 + tx;
-    if (c < cols && r < rows) stf<TO>(dst + c * ldd + r, tile[tx][cc]);
-  }
+  transpose_tile<TO>([=](int64_t r, int64_t c) { return ldf<TI>(src + r * lds + c); }, dst, ldd, rows, rows, cols,
+                     (int64_t)blockIdx.y * 64, (int64_t)blockIdx.x * 64, tile);
 }
 
-// 16-bit -> 16-bit transpose of a 64x64 tile with 16-B global accesses: each
-// lane loads 8 consecutive columns of a row (2 per lane), the tile sits in LDS
-// as u16 rows of pitch 66 (odd dword pitch: the column reads below are at most
-// 2-way), and each lane writes 8 consecutive source rows of one column as one
-// 16-B store (8 lanes = one 128-B output row segment).  Needs rows, cols,
-// strides multiple of 8 and 16-B aligned bases (checked by the caller).
+// 16-bit -> 16-bit transpose with 16-B global accesses (transpose_tile16): rows,
+// cols, strides multiple of 8 and 16-B aligned bases (checked by the caller).
 __global__ __launch_bounds__(256) void transpose16_kernel(int64_t rows, int64_t cols,
                                                           const uint16_t* __restrict__ src, int64_t lds,
                                                           uint16_t* __restrict__ dst, int64_t ldd) {
-  constexpr int P = 66;
-  __shared__ uint16_t tile[64 * P];
-  const int64_t r0 = (int64_t)blockIdx.y * 64, c0 = (int64_t)blockIdx.x * 64;
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int rr = (t >> 3) + 32 * k, ch = t & 7;
-    const int64_t r = r0 + rr, c = c0 + 8 * ch;
-    uint4 u = make_uint4(0, 0, 0, 0);
-    if (r < rows && c < cols) u = *reinterpret_cast<const uint4*>(src + r * lds + c);
-    uint32_t* d = reinterpret_cast<uint32_t*>(tile + rr * P + 8 * ch);  // 4-B aligned (P even)
-    d[0] = u.x; d[1] = u.y; d[2] = u.z; d[3] = u.w;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int oc = (t >> 3) + 32 * k, rc = t & 7;
-    const int64_t c = c0 + oc, r = r0 + 8 * rc;
-    uint32_t w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      w[j] = (uint32_t)tile[(8 * rc + 2 * j) * P + oc] | ((uint32_t)tile[(8 * rc + 2 * j + 1) * P + oc] << 16);
-    if (c < cols && r < rows) *reinterpret_cast<uint4*>(dst + c * ldd + r) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
+  __shared__ uint16_t tile[64 * kT16Pitch];
+  transpose_tile16(src, lds, dst, ldd, rows, rows, cols, (int64_t)blockIdx.y * 64, (int64_t)blockIdx.x * 64, tile);
 }
 
 // f32 -> bf16 transpose of a 64x64 tile with 16-B global accesses both ways
@@ -129,32 +91,6 @@ __global__ __launch_bounds__(256) void transpose_f32_bf16_kernel(int64_t rows, i
 }
 
 // ----------------------------------------------------------------- pooling fwd
-// FinalAttention pooling (modeling_utils.py:224-228) over consecutive slot rows:
-// xp row = [x | p] (p = exp(w)); u_d = sum x p / (sum p + 1e-10), z_d = sum p + 1e-10.
-// One workgroup (4 waves x 256 dims) per segment.
-// 4 consecutive elements as one 8-B (bf16) / 16-B (f32) access (host: 16-B aligned
-// base, row strides and column offsets multiples of 4 elements)
-template <typename T>
-__device__ __forceinline__ void ld4v(const T* p, float (&v)[4]) {
-  if constexpr (sizeof(T) == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    const uint2 q = *reinterpret_cast<const uint2*>(p);
-    v[0] = bf16_lo(q.x); v[1] = bf16_hi(q.x); v[2] = bf16_lo(q.y); v[3] = bf16_hi(q.y);
-  }
-}
-template <typename T>
-__device__ __forceinline__ void st4v(T* p, const float (&v)[4]) {
-  if constexpr (sizeof(T) == 4) {
-    *reinterpret_cast<float4*>(p) = float4{v[0], v[1], v[2], v[3]};
-  } else {
-    const __bf16 h[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-    *reinterpret_cast<uint2*>(p) = *reinterpret_cast<const uint2*>(h);
-  }
-}
-
-// ----------------------------------------------------------------- pooling fwd
 // u[b, d] = sum_i x[i, d] p[i, d] / (sum_i p[i, d] + 1e-10) over the rows of
 // segment b (FinalAttention's per-dimension softmax pooling, modeling_utils.py:224-228,
 // with p = exp(logit) from the GEMM epilogue); z = the denominator (saved for bwd).
@@ -179,8 +115,8 @@ __global__ __launch_bounds__(64 * kPoolWaves) void final_pool_fwd_kernel(int64_t
   for (int64_t i = off[b] + wave; i < off[b + 1]; i += kPoolWaves) {
     const T* row = xp + i * ld;
     float x[4], p[4];
-    ld4v<T>(row + d, x);
-    ld4v<T>(row + D + d, p);
+    ld4<T>(row + d, x);
+    ld4<T>(row + D + d, p);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       num[t] = fmaf(x[t], p[t], num[t]);
@@ -229,8 +165,8 @@ __global__ __launch_bounds__(256) void final_pool_bwd_kernel(int64_t n_seg, cons
     if (i >= n_rows) break;
     if (i >= nvalid) {
       const float zero[4] = {0.f, 0.f, 0.f, 0.f};
-      st4v<T>(dx + i * lddx + d, zero);
-      st4v<T>(dl + i * lddl + d, zero);
+      st4<T>(dx + i * lddx + d, zero);
+      st4<T>(dl + i * lddl + d, zero);
       continue;
     }
     if (i >= bend) {
@@ -254,15 +190,15 @@ __global__ __launch_bounds__(256) void final_pool_bwd_kernel(int64_t n_seg, cons
     }
     const T* row = xp + i * ld;
     float x[4], p[4], gx[4], gl[4];
-    ld4v<T>(row + d, x);
-    ld4v<T>(row + D + d, p);
+    ld4<T>(row + d, x);
+    ld4<T>(row + D + d, p);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       gx[t] = g[t] * p[t] * iz[t];
       gl[t] = gx[t] * (x[t] - u[t]);
     }
-    st4v<T>(dx + i * lddx + d, gx);
-    st4v<T>(dl + i * lddl + d, gl);
+    st4<T>(dx + i * lddx + d, gx);
+    st4<T>(dl + i * lddl + d, gl);
   }
 }
 
@@ -471,20 +407,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(int64_t n, const flo
   const int lane = threadIdx.x & 63;
   for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (int64_t)gridDim.x * 4) {
     float v[NJ][4], g[NJ][4];
-    float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const float4 a = *reinterpret_cast<const float4*>(x + row * ldx + j * 256 + lane * 4);
-      v[j][0] = a.x; v[j][1] = a.y; v[j][2] = a.z; v[j][3] = a.w;
-      s += (a.x + a.y) + (a.z + a.w);
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { const float d = v[j][t] - mean; q = fmaf(d, d, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+    for (int j = 0; j < NJ; ++j) ld4<float>(x + row * ldx + j * 256 + lane * 4, v[j]);
+    float mean, rstd;
+    row_stats4<NJ>(v, (float)D, eps, mean, rstd);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -531,18 +457,7 @@ __global__ __launch_bounds__(256) void softmax64_bwd_kernel(int64_t n_groups, in
   }
 }
 
-__device__ __forceinline__ float gelu_exact(float g) { return 0.5f * g * (1.0f + erff(g * 0.70710678118654752440f)); }
-
 // z[:, j] = a_j * gelu(g_j),  a = G[:, :F], g = G[:, F:]  (GEGLU, latent_attention.py:24-27)
-template <typename TO>
-__device__ __forceinline__ void st4(TO* p, float a, float b, float c, float d) {
-  if constexpr (sizeof(TO) == 4) {
-    *reinterpret_cast<float4*>(p) = float4{a, b, c, d};
-  } else {
-    p[0] = (TO)a; p[1] = (TO)b; p[2] = (TO)c; p[3] = (TO)d;
-  }
-}
-
 template <typename TO>
 __global__ __launch_bounds__(256) void geglu_fwd_kernel(int64_t rows, int64_t f, const float* __restrict__ G,
                                                         int64_t ldg, TO* __restrict__ z, int64_t ldz) {
@@ -551,8 +466,8 @@ __global__ __launch_bounds__(256) void geglu_fwd_kernel(int64_t rows, int64_t f,
     const int64_t r = i / f, c = i % f;  // f % 4 == 0: the 4 columns share a row
     const float4 a = *reinterpret_cast<const float4*>(G + r * ldg + c);
     const float4 g = *reinterpret_cast<const float4*>(G + r * ldg + f + c);
-    st4<TO>(z + r * ldz + c, a.x * gelu_exact(g.x), a.y * gelu_exact(g.y), a.z * gelu_exact(g.z),
-            a.w * gelu_exact(g.w));
+    const float o[4] = {a.x * gelu_exact(g.x), a.y * gelu_exact(g.y), a.z * gelu_exact(g.z), a.w * gelu_exact(g.w)};
+    st4<TO>(z + r * ldz + c, o);
   }
 }
 
@@ -577,8 +492,8 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(int64_t rows, int64_t f,
       da[t] = d[t] * g[t] * cdf;
       dg[t] = d[t] * a[t] * (cdf + g[t] * pdf);
     }
-    st4<TO>(dG + r * lddg + c, da[0], da[1], da[2], da[3]);
-    st4<TO>(dG + r * lddg + f + c, dg[0], dg[1], dg[2], dg[3]);
+    st4<TO>(dG + r * lddg + c, da);
+    st4<TO>(dG + r * lddg + f + c, dg);
   }
 }
 
@@ -588,34 +503,7 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(int64_t rows, int64_t f,
 // serialise at the memory side: MI355X_MICROARCH.md "Global float atomics").
 __global__ __launch_bounds__(256) void sumsq_kernel(int64_t n, const float* __restrict__ x, float* __restrict__ out) {
   __shared__ float part[4];
-  float s = 0.f;
-  const int64_t n4 = ((uintptr_t)x & 15) == 0 ? n / 4 : 0;
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  // four 16-B loads in flight per thread (one per iteration left the kernel
-  // latency-bound: 30 us for the latent step's 114 MB of gradients)
-  const int64_t gs = (int64_t)gridDim.x * 256;
-  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  for (; i + 3 * gs < n4; i += 4 * gs) {
-    float4 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = x4[i + k * gs];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      s = fmaf(v[k].x, v[k].x, s);
-      s = fmaf(v[k].y, v[k].y, s);
-      s = fmaf(v[k].z, v[k].z, s);
-      s = fmaf(v[k].w, v[k].w, s);
-    }
-  }
-  for (; i < n4; i += gs) {
-    const float4 v = x4[i];
-    s = fmaf(v.x, v.x, s);
-    s = fmaf(v.y, v.y, s);
-    s = fmaf(v.z, v.z, s);
-    s = fmaf(v.w, v.w, s);
-  }
-  for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    s = fmaf(x[i], x[i], s);
+  float s = sumsq_range(x, n, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256);
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -675,6 +563,18 @@ __global__ __launch_bounds__(256) void adamw_kernel(int64_t n, float* __restrict
 }
 
 static int grid_for(int64_t n) { const int64_t g = (n + 255) / 256; return (int)(g < 4096 ? g : 4096); }
+
+__global__ __launch_bounds__(256) void zero_kernel(ZList z) {
+  for (int i = 0; i < z.n; ++i)
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < z.len[i]; k += (int64_t)gridDim.x * 256)
+      z.p[i][k] = 0.f;
+}
+
+int zero_ranges(const ZList& z, int blocks, hipStream_t s) {
+  hipLaunchKernelGGL(zero_kernel, dim3((unsigned)blocks), dim3(256), 0, s, z);
+  NR_CHECK_LAUNCH("zero_ranges");
+  return NR_OK;
+}
 
 }  // namespace nr
 

@@ -347,6 +347,76 @@ def test_gpu_train_kernels_vector_paths(gpu_device):
     torch.testing.assert_close(c, a.float() @ w.float().T, rtol=2e-3, atol=2e-2)
 
 
+def _bf16_edge_values(n, device):
+    """n f32 values cycling through the cases a bf16 store can get wrong: -0.0,
+    +-inf, a subnormal, exact ties between two bf16 neighbours of both parities
+    (round to nearest even goes down from 0x3F808000, up from 0x3F818000), their
+    neighbours one f32 ulp off the tie, and the tie below inf that rounds to it."""
+    bits = [0x80000000, 0x7F800000, 0x00080000, 0x3F808000, 0x3F818000, 0xFF800000, 0xBF808000, 0xBF818000,
+            0x3F808001, 0x3F807FFF, 0x7F7F8000, 0x3FC00000]
+    b = torch.tensor([bits[i % len(bits)] for i in range(n)], dtype=torch.int64, device=device)
+    return torch.where(b >= 2 ** 31, b - 2 ** 32, b).to(torch.int32).view(torch.float32)
+
+
+def _assert_bf16_edges(out32):
+    """the f32 output really holds -0.0, an infinity, a subnormal and ties of both parities"""
+    b = out32.reshape(-1).view(torch.int32)
+    assert (b == -2 ** 31).any() and torch.isinf(out32).any()
+    assert ((b & 0x7F800000) == 0).logical_and((b & 0x007FFFFF) != 0).any()
+    assert (b == 0x3F808000).any() and (b == 0x3F818000).any()
+
+
+@pytest.mark.gpu
+def test_gpu_bf16_stores_round_as_torch(gpu_device):
+    """Every row op whose bf16 output goes through the shared packed store: the
+    bf16-output call equals the f32-output call rounded by torch, bit for bit,
+    on 5 rows (a partial block of 4 waves) of the narrowest width, with outputs
+    that hold -0.0, infinities, a subnormal and round-to-nearest-even ties."""
+    from news_recommendation_project_v2_amd import ops
+    dev, bf = gpu_device, torch.bfloat16
+    # LayerNorm: x constant per row, so y = 0 * gamma + beta = beta (gamma = 1; -1 where
+    # beta = -0.0, whose sum with +0 would be +0); f32 rows (8-B stores) and bf16 rows (16-B)
+    beta = _bf16_edge_values(256, dev)
+    gamma = torch.where(beta.view(torch.int32) == -2 ** 31, -1.0, 1.0).to(dev)
+    x = torch.arange(1, 6, dtype=torch.float32, device=dev)[:, None].expand(5, 256).contiguous()
+    for xi in (x, x.to(bf)):
+        y32 = ops.layernorm(xi, gamma, beta, 1e-5, out_dtype=torch.float32)
+        assert torch.equal(y32.view(torch.int32), beta.view(torch.int32).expand(5, 256))
+        _assert_bf16_edges(y32)
+        assert torch.equal(ops.layernorm(xi, gamma, beta, 1e-5, out_dtype=bf), y32.to(bf))
+    # GEGLU: gates of 8 have gelu = 8 and gelu' = 1 exactly in f32, so z = 8 a and dG = (8 dz, a dz)
+    v = _bf16_edge_values(20, dev).reshape(5, 4)
+    eight = torch.full((5, 4), 8.0, device=dev)
+    g = torch.cat([v / 8, eight], 1)
+    z32 = ops.geglu_fwd(g)
+    _assert_bf16_edges(z32)
+    assert torch.equal(ops.geglu_fwd(g, out_dtype=bf), z32.to(bf))
+    g = torch.cat([eight, eight], 1)
+    d32 = ops.geglu_bwd(g, v / 8)
+    _assert_bf16_edges(d32[:, :4])
+    _assert_bf16_edges(d32[:, 4:])
+    assert torch.equal(ops.geglu_bwd(g, v / 8, out_dtype=bf), d32.to(bf))
+    # transpose, one column
+    t = _bf16_edge_values(5, dev).reshape(5, 1)
+    t32 = ops.transpose(t)
+    _assert_bf16_edges(t32)
+    assert torch.equal(ops.transpose(t, out_dtype=bf), t32.to(bf))
+    # FinalAttention pool backward: x = p = z = 1, u = 0, so dx = dlogit = du; segments of 3 and 1
+    # rows and one padding row (zeros)
+    off = torch.tensor([0, 3, 4], dtype=torch.int64, device=dev)
+    du = torch.stack([_bf16_edge_values(1024, dev), _bf16_edge_values(1027, dev)[3:]])
+    users, zz = torch.zeros(2, 1024, device=dev), torch.ones(2, 1024, device=dev)
+    outs = {}
+    for dt in (torch.float32, bf):
+        xp = torch.ones(5, 2048, dtype=dt, device=dev)
+        outs[dt] = (torch.empty(5, 1024, dtype=dt, device=dev), torch.empty(5, 1024, dtype=dt, device=dev))
+        ops.final_pool_bwd(xp, off, users, zz, du, *outs[dt])
+    for o32, o16 in zip(outs[torch.float32], outs[bf]):
+        _assert_bf16_edges(o32)
+        assert not o32[4].any()
+        assert torch.equal(o16, o32.to(bf))
+
+
 @pytest.mark.gpu
 def test_gpu_gemm_grouped(gpu_device):
     """nr_gemm_grouped: mixed shapes (64-tile and 256-tile problems, a ragged M,
