@@ -125,7 +125,8 @@ int nr_is_device_pointer(const void* p);
  *   FinalAttention.forward        modeling_utils.py:218-222
  *   LatentAttentionModel blocks   latent_attention.py:34-36, 59-61, 162-163
  * dtype_in NR_F32: exact-f32 MFMA (v_mfma_f32_32x32x2_f32);
- * dtype_in NR_BF16: bf16 MFMA (v_mfma_f32_32x32x16_bf16), f32 accumulate.
+ * dtype_in NR_BF16: bf16 MFMA (v_mfma_f32_16x16x32_bf16 on 256x256 tiles,
+ * v_mfma_f32_32x32x16_bf16 on 128x128 tiles), f32 accumulate.
  * A and W share dtype_in; C is dtype_out; bias and R are f32 (bias nullable,
  * R only for NR_EPI_RESADD, R has dtype_out).  Requires N % 128 == 0,
  * K % 32 == 0 (f32) or K % 64 == 0 (bf16); M arbitrary.

@@ -1,4 +1,4 @@
-// MFMA GEMMs with fused epilogues for the per-news pooler transforms (gfx950).
+// MFMA GEMMs with fused epilogues (gfx950): pooler transforms, encoder, training.
 //
 //   C[M, N] = epilogue(A[M, K] · W[N, K]ᵀ)     (W in torch nn.Linear layout)
 //
@@ -6,20 +6,46 @@
 //   FinalAttention.forward        modeling_utils.py:218-222
 //   LatentAttentionModel blocks   latent_attention.py:34-36, 59-61, 162-163
 //
-// Two main loops share one tiling and one epilogue:
-//   f32 : v_mfma_f32_32x32x2_f32  (exact f32 fmaf chain; the parity config)
-//   bf16: v_mfma_f32_32x32x16_bf16 (bf16 operands, f32 accumulate)
-// Block tile 128x128, 256 threads = 4 waves in a 2x2 grid, each wave owns a
-// 64x64 output = 2x2 MFMA 32x32 accumulators (64 acc registers).  K is staged
-// through LDS in 128-byte row slices (BK = 32 f32 / 64 bf16) with a 16-byte
-// row pad (144-byte rows) so the ds_read_b128 fragment reads of 32 distinct
-// rows are bank-conflict free; global->register prefetch of tile k+1 overlaps
-// the MFMAs of tile k, one barrier per K tile.
+// Three kernels, f32 accumulation in all of them:
+// gemm_kernel: 128x128 block tile, register-staged.  256 threads = 4 waves in
+//   a 2x2 grid, each wave 64x64 = 2x2 accumulators of 32x32.
+//     f32 : v_mfma_f32_32x32x2_f32  (exact f32 fmaf chain; the parity config)
+//     bf16: v_mfma_f32_32x32x16_bf16
+//   K is staged through LDS in 128-byte row slices (BK = 32 f32 / 64 bf16) with
+//   a 16-byte row pad (144-byte rows) so the ds_read_b128 fragment reads of 32
+//   distinct rows are bank-conflict free; global->register prefetch of tile
+//   k+1 overlaps the MFMAs of tile k, one barrier per K tile.
+// gemm256p_kernel: 256x256 block tile, LDS-DMA pipelined (gemm256p_body), one
+//   tile per workgroup.  512 threads = 8 waves (2 x 4), each wave 128x64.
+//     f32 : v_mfma_f32_32x32x2_f32,  4x2 accumulators of 32x32
+//     bf16: v_mfma_f32_16x16x32_bf16, 8x4 accumulators of 16x16
+//   Operands go global -> LDS by DMA into a 2-stage ring, each K tile runs in
+//   4 MFMA phases between raw barriers, and the epilogue is staged through LDS
+//   (gemm256_store).  gemm256p_group_kernel runs up to kGroupMax independent
+//   problems (strided batches, split-K slices) in one grid; its TN form reads
+//   both operands with the reduction index as the row (bf16; the weight grads).
+// gemm256t_kernel: persistent 256x256, bf16 in and out.  One workgroup per CU
+//   walks its share of the tiles with one operand stream across tile
+//   boundaries; v_mfma_f32_16x16x32_bf16 with the operands swapped, so the
+//   epilogue leaves straight from registers; the last partial round runs as
+//   half tiles.  LNF folds a LayerNorm into the epilogue, CS adds column sums.
+//
+// Routing.  nr_gemm needs N % 128 == 0 and K % 32 (f32) or K % 64 (bf16).
+// gemm_dispatch_ex sends a call to the 256x256 kernels when N % 256 == 0 and
+// the output rows (for RESADD / DRELU also the residual rows) are 16-byte
+// aligned, and to gemm_kernel otherwise; SOFTMAX64 has no 128x128 form and is
+// refused there.  Among the 256x256 calls (launch_gemm256), bf16 -> bf16 with
+// K % 128 == 0 and A and W below 4 GiB each (persistent_takes) runs on
+// gemm256t_kernel, with an A past 4 GiB in row chunks of it; every other call
+// (an f32 side, an odd count of 64-deep K steps) runs on gemm256p_kernel.
+// SOFTMAX64_BWD and the column sums exist on gemm256t_kernel only and are
+// refused where it cannot run.  nr_gemm_grouped and nr_gemm_grouped_tn always
+// run gemm256p_group_kernel, the LayerNorm-folded launch gemm256t_kernel<LNF>.
 #include "nr_common.h"
 #include "nr_rows.h"
 
 #include <atomic>
-
+#include <type_traits>
 
 namespace nr {
 
@@ -241,38 +267,31 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(int64_t M, int64_t N, int6
 }
 
 // ---------------------------------------------------------------------------
-// bf16, 256x256 block tile, 512 threads = 8 waves (2 along M x 4 along N),
-// each wave 128x64 = 4x2 accumulators of 32x32 (128 acc VGPRs).  K tiles of
-// 64 are staged global -> LDS directly with global_load_lds_dwordx4 (no VGPR
-// round trip) into a 2-stage ring (2 x 64 KiB); the prefetch of tile k+1 is in
-// flight while the MFMAs of tile k run, one barrier per K tile.  LDS image of
-// an operand stage: row r (0..255) = 8 chunks of 16 B, chunk c stored at
-// position c ^ ((r >> 1) & 7): each 16-lane ds_read_b128 group then hits 16
-// distinct 16-B bank slots (T2 swizzle, applied on the glds SOURCE address
-// because the DMA writes LDS lane-linearly).
+// The 256x256 kernels.  K tiles of 128 B per row are staged global -> LDS by
+// DMA (no VGPR round trip) into a 2-stage ring (2 x 64 KiB).  LDS image of an
+// operand stage: row r (0..255) = 8 chunks of 16 B, chunk c stored at position
+// c ^ ((r >> 1) & 7): each 16-lane ds_read_b128 group then hits 16 distinct
+// 16-B bank slots (T2 swizzle, applied on the DMA's SOURCE address because
+// the DMA writes LDS lane-linearly).
 constexpr int G2BM = 256, G2BN = 256;
 constexpr int G2_STAGE = (G2BM + G2BN) * 128;  // bytes per stage (A + B, 128-B row slices) = 64 KiB
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void g_void;
 
-// Epilogue of the 256x256 kernels (acc[4][2] per wave: rows wm*128 + 32 mi,
-// cols wn*64 + 32 ni), staged through the kernel's LDS (caller has finished
-// with the operand stages and passed a barrier).
-template <bool MF16>
-struct Acc256 {  // per-wave 128x64 accumulators: 4x2 tiles of 32x32, or 8x4 tiles of 16x16
-  typedef f32x16 type[4][2];
-};
-template <>
-struct Acc256<true> {
-  typedef f32x4 type[8][4];
-};
+// Per-wave 128x64 accumulators (rows wm*128.., cols wn*64..): f32 operands 4x2
+// tiles of 32x32 (32x32x2), bf16 operands 8x4 tiles of 16x16 (16x16x32).
+template <typename TI> struct Acc256 { typedef f32x16 type[4][2]; };
+template <> struct Acc256<__bf16> { typedef f32x4 type[8][4]; };
 
-template <int EPI, typename TO, bool MF16 = false>
-__device__ __forceinline__ void gemm256_store(const typename Acc256<MF16>::type& acc, unsigned char* smem, int wave, int lane,
-                                              int wm, int wn, int64_t m0, int64_t n0, int64_t M, int64_t N,
+// Epilogue of gemm256p_body, staged through the kernel's LDS (the caller has
+// finished with the operand stages).
+template <typename TI, int EPI, typename TO>
+__device__ __forceinline__ void gemm256_store(const typename Acc256<TI>::type& acc, unsigned char* smem, int wave,
+                                              int lane, int wm, int wn, int64_t m0, int64_t n0, int64_t M, int64_t N,
                                               const float* __restrict__ bias, const TO* R, int64_t ldr, TO* C,
                                               int64_t ldc, const EpiArgs& ea) {
+  constexpr bool B16 = sizeof(TI) == 2;  // 16x16 accumulator tiles (bf16 operands), else 32x32 (f32)
   // Epilogue, staged through LDS so global stores are whole 16-byte row
   // segments (the 32x32 C/D map would give 2-4-byte scattered stores).  Two
   // passes of 64 rows per wave; bias and activation are applied in registers,
@@ -295,7 +314,7 @@ __device__ __forceinline__ void gemm256_store(const typename Acc256<MF16>::type&
   const int64_t ocol0 = (EPI == NR_EPI_GEGLU) ? wcol / 2 : wcol;
   float ba = 0.f, bg = 0.f;
   float b16[4] = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (MF16) {
+  if constexpr (B16) {
     if (bias) {
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) b16[ni] = bias[wcol + 16 * ni + (lane & 15)];
@@ -306,7 +325,7 @@ __device__ __forceinline__ void gemm256_store(const typename Acc256<MF16>::type&
   }
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
-    if constexpr (MF16) {
+    if constexpr (B16) {
       // 16x16 C/D map: col = lane & 15, row = 4 * (lane >> 4) + r
       const int c16 = lane & 15, r16 = 4 * (lane >> 4);
 #pragma unroll
@@ -318,7 +337,8 @@ __device__ __forceinline__ void gemm256_store(const typename Acc256<MF16>::type&
           if constexpr (EPI == NR_EPI_GEGLU) {
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
-              slab[lr * COLS + 16 * ni + c16] = (acc[mi][ni][r] + b16[ni]) * gelu_erf(acc[mi][ni + 2][r] + b16[ni + 2]);
+              slab[lr * COLS + 16 * ni + c16] =
+                  (acc[mi][ni][r] + b16[ni]) * gelu_erf(acc[mi][ni + 2][r] + b16[ni + 2]);
           } else {
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
@@ -440,7 +460,7 @@ __device__ __forceinline__ void gemm256_store(const typename Acc256<MF16>::type&
 }
 
 // ---------------------------------------------------------------------------
-// Pipelined 256x256 variant: each K tile is computed in 4 phases, one output
+// Main loop of the 256x256 tile kernels: each K tile is computed in 4 phases, one output
 // quadrant (64 rows x 32 cols per wave) each, with the half-tile LDS-DMA
 // prefetches spread over the phases and kept in flight ACROSS raw s_barriers
 // (counted vmcnt, never a drained queue in steady state):
@@ -481,7 +501,7 @@ __device__ __forceinline__ void tile_of(int wg, int nx, int ny, int gm, int& mt,
   nt = loc / gsz;
 }
 
-// TN = true (bf16, 16x16x32 only): both operands are stored with the reduction
+// TN = true (bf16 only): both operands are stored with the reduction
 // index as the ROW, A as [K][M] and W as [K][N] (lda / ldw = their row strides):
 // C[m][n] = sum_k A[k][m] W[k][n], i.e. the weight-grad GEMM dW = dOut^T X of a
 // training step read straight from the row-major activations dOut [slots][out]
@@ -499,12 +519,26 @@ __device__ __forceinline__ void tile_of(int wg, int nx, int ny, int gm, int& mt,
 __device__ __forceinline__ int tn_hsw(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-template <typename TI, int EPI, typename TO, bool MF16, bool TN = false>
+// One phase of the 4-phase main loops (gemm256p_body and gemm256t_kernel): the
+// phase's fragment reads retire, then the MFMA quadrant runs between two raw
+// barriers at raised priority.  Uses the enclosing scope's mma() and a
+// constexpr bool IDLE (true: this wave keeps the barriers and skips the MFMAs).
+#define NR_PHASE_SYNC_MMA(QM, NI, FB)                   \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
+  __builtin_amdgcn_sched_barrier(0);                   \
+  __builtin_amdgcn_s_barrier();                        \
+  __builtin_amdgcn_s_setprio(1);                       \
+  if constexpr (!IDLE) mma(QM, NI, FB);               \
+  __builtin_amdgcn_s_setprio(0);                       \
+  __builtin_amdgcn_s_barrier();
+
+template <typename TI, int EPI, typename TO, bool TN = false>
 __device__ __forceinline__ void gemm256p_body(unsigned char* smem, int64_t m0, int64_t n0, int64_t M, int64_t N,
                                               int64_t K, const TI* __restrict__ A, int64_t lda,
                                               const TI* __restrict__ W, int64_t ldw, const float* __restrict__ bias,
                                               const TO* R, int64_t ldr, TO* C, int64_t ldc, const EpiArgs& ea) {
-  static_assert(!TN || (MF16 && sizeof(TI) == 2), "TN operands: bf16 16x16x32 only");
+  static_assert(!TN || sizeof(TI) == 2, "TN operands: bf16 only");
+  constexpr bool B16 = sizeof(TI) == 2;  // bf16: 16x16x32 MFMA tiles; f32: 32x32x2
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
 
@@ -547,8 +581,8 @@ __device__ __forceinline__ void gemm256p_body(unsigned char* smem, int64_t m0, i
       __builtin_amdgcn_global_load_lds((g_void*)(bsrc[h][j] + kt * bstep), (lds_void*)(sb + hoff[h][j]), 16, 0, 0);
   };
 
-  typename Acc256<MF16>::type acc;
-  if constexpr (MF16) {
+  typename Acc256<TI>::type acc;
+  if constexpr (B16) {
 #pragma unroll
     for (int mi = 0; mi < 8; ++mi)
 #pragma unroll
@@ -565,10 +599,10 @@ __device__ __forceinline__ void gemm256p_body(unsigned char* smem, int64_t m0, i
   }
 
   const int fr = lane & 31, fh = lane >> 5;
-  // 32x32 operand tiles (MF16 = false): 4 A tiles of 32 rows, 2 B tiles of 32 columns
-  // 16x16 operand tiles (MF16 = true):  8 A tiles of 16 rows, 4 B tiles of 16 columns
-  constexpr int TA = MF16 ? 8 : 4, TB = MF16 ? 4 : 2, TR = MF16 ? 16 : 32;
-  const int lr_ = MF16 ? (lane & 15) : fr;
+  // 32x32 operand tiles (f32):  4 A tiles of 32 rows, 2 B tiles of 32 columns
+  // 16x16 operand tiles (bf16): 8 A tiles of 16 rows, 4 B tiles of 16 columns
+  constexpr int TA = B16 ? 8 : 4, TB = B16 ? 4 : 2, TR = B16 ? 16 : 32;
+  const int lr_ = B16 ? (lane & 15) : fr;
   int aoff[TA], boff[TB], asw[TA], bsw[TB];
 #pragma unroll
   for (int mi = 0; mi < TA; ++mi) {
@@ -583,17 +617,16 @@ __device__ __forceinline__ void gemm256p_body(unsigned char* smem, int64_t m0, i
     bsw[ni] = (row >> 1) & 7;
   }
   // fragment f of a 128-byte row slice:
-  //   bf16 32x32x16 k-step f (4 per tile) -> chunk 2f + (lane >> 5)
   //   bf16 16x16x32 k-step f (2 per tile) -> chunk 4f + (lane >> 4)
   //   f32  32x32x2 group f (4 k-steps)    -> chunk 4 (lane >> 5) + f
   auto chunk_of = [&](int f) {
-    if constexpr (MF16) return 4 * f + (lane >> 4);
-    else return sizeof(TI) == 2 ? 2 * f + fh : 4 * fh + f;
+    if constexpr (B16) return 4 * f + (lane >> 4);
+    else return 4 * fh + f;
   };
   typedef f32x4 frag_t;  // 16 bytes: 8 bf16 or 4 f32
-  constexpr int QA = MF16 ? 4 : 2;   // A tiles per 64-row quadrant
-  constexpr int QB = MF16 ? 2 : 1;   // B tiles per 32-column quadrant
-  constexpr int NF = MF16 ? 2 : 4;   // fragments (k-steps or groups) per tile per K tile
+  constexpr int QA = B16 ? 4 : 2;   // A tiles per 64-row quadrant
+  constexpr int QB = B16 ? 2 : 1;   // B tiles per 32-column quadrant
+  constexpr int NF = B16 ? 2 : 4;   // fragments (k-steps or groups) per tile per K tile
   frag_t fa[QA][NF], fb0[QB][NF], fb1[QB][NF];
   // TN: per-tile lane offsets of the transposed reads (K-half f adds 8192, e = 1 adds 1024)
   int taoff[TA], tboff[TB];
@@ -620,7 +653,8 @@ __device__ __forceinline__ void gemm256p_body(unsigned char* smem, int64_t m0, i
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         if constexpr (TN) fa[i][f] = tr_frag(s + taoff[QA * qm + i] + f * 8192);
-        else fa[i][f] = *reinterpret_cast<const frag_t*>(s + aoff[QA * qm + i] + ((chunk_of(f) ^ asw[QA * qm + i]) << 4));
+        else
+          fa[i][f] = *reinterpret_cast<const frag_t*>(s + aoff[QA * qm + i] + ((chunk_of(f) ^ asw[QA * qm + i]) << 4));
       }
   };
   auto readB = [&](int stage, int qn, frag_t (&fb)[QB][NF]) {
@@ -630,7 +664,8 @@ __device__ __forceinline__ void gemm256p_body(unsigned char* smem, int64_t m0, i
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         if constexpr (TN) fb[j][f] = tr_frag(s + tboff[QB * qn + j] + f * 8192);
-        else fb[j][f] = *reinterpret_cast<const frag_t*>(s + boff[QB * qn + j] + ((chunk_of(f) ^ bsw[QB * qn + j]) << 4));
+        else
+          fb[j][f] = *reinterpret_cast<const frag_t*>(s + boff[QB * qn + j] + ((chunk_of(f) ^ bsw[QB * qn + j]) << 4));
       }
   };
   auto mma = [&](int qm, int qn, const frag_t (&fb)[QB][NF]) {
@@ -640,31 +675,19 @@ __device__ __forceinline__ void gemm256p_body(unsigned char* smem, int64_t m0, i
       for (int i = 0; i < QA; ++i)
 #pragma unroll
         for (int j = 0; j < QB; ++j) {
-          if constexpr (MF16) {
+          if constexpr (B16) {
             acc[QA * qm + i][QB * qn + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                __builtin_bit_cast(bf16x8, fa[i][f]), __builtin_bit_cast(bf16x8, fb[j][f]), acc[QA * qm + i][QB * qn + j],
-                0, 0, 0);
-          } else if constexpr (sizeof(TI) == 2) {
-            acc[QA * qm + i][QB * qn + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                __builtin_bit_cast(bf16x8, fa[i][f]), __builtin_bit_cast(bf16x8, fb[j][f]), acc[QA * qm + i][QB * qn + j],
-                0, 0, 0);
+                __builtin_bit_cast(bf16x8, fa[i][f]), __builtin_bit_cast(bf16x8, fb[j][f]),
+                acc[QA * qm + i][QB * qn + j], 0, 0, 0);
           } else {
 #pragma unroll
             for (int t = 0; t < 4; ++t)
-              acc[QA * qm + i][QB * qn + j] =
-                  __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][f][t], fb[j][f][t], acc[QA * qm + i][QB * qn + j], 0, 0, 0);
+              acc[QA * qm + i][QB * qn + j] = __builtin_amdgcn_mfma_f32_32x32x2f32(
+                  fa[i][f][t], fb[j][f][t], acc[QA * qm + i][QB * qn + j], 0, 0, 0);
           }
         }
   };
-#define NR_PHASE_SYNC_MMA(QM, NI, FB)                   \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_s_setprio(1);                       \
-  mma(QM, NI, FB);                                     \
-  __builtin_amdgcn_s_setprio(0);                       \
-  __builtin_amdgcn_s_barrier();
-
+  constexpr bool IDLE = false;  // NR_PHASE_SYNC_MMA: every wave computes
   // The two wave groups (wm = 0: waves 0-3, wm = 1: waves 4-7; one of each per
   // SIMD) run one barrier apart, so one group's MFMA cluster overlaps the
   // other's fragment reads.  Hazard bookkeeping for that stagger: reads are
@@ -714,11 +737,10 @@ __device__ __forceinline__ void gemm256p_body(unsigned char* smem, int64_t m0, i
     __builtin_amdgcn_s_barrier();
   }
   if (wmu == 0) __builtin_amdgcn_s_barrier();  // re-align the groups
-#undef NR_PHASE_SYNC_MMA
-  gemm256_store<EPI, TO, MF16>(acc, smem, wave, lane, wm, wn, m0, n0, M, N, bias, R, ldr, C, ldc, ea);
+  gemm256_store<TI, EPI, TO>(acc, smem, wave, lane, wm, wn, m0, n0, M, N, bias, R, ldr, C, ldc, ea);
 }
 
-template <typename TI, int EPI, typename TO, bool MF16 = false>
+template <typename TI, int EPI, typename TO>
 __global__ __launch_bounds__(512, 2) void gemm256p_kernel(int64_t M, int64_t N, int64_t K,
                                                           const TI* __restrict__ A, int64_t lda,
                                                           const TI* __restrict__ W, int64_t ldw,
@@ -729,8 +751,8 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(int64_t M, int64_t N, 
   const int wg = xcd_remap((int)blockIdx.y * nx + (int)blockIdx.x, nx * (int)gridDim.y);
   int mt, nt;
   tile_of(wg, nx, (int)gridDim.y, ea.group_m, mt, nt);
-  gemm256p_body<TI, EPI, TO, MF16>(smem, (int64_t)mt * G2BM, (int64_t)nt * G2BN, M, N, K, A, lda, W,
-                                   ldw, bias, R, ldr, C, ldc, ea);
+  gemm256p_body<TI, EPI, TO>(smem, (int64_t)mt * G2BM, (int64_t)nt * G2BN, M, N, K, A, lda, W, ldw, bias, R, ldr, C,
+                             ldc, ea);
 }
 
 // Grouped launch of up to kGroupMax independent problems with one dtype pair
@@ -758,7 +780,7 @@ struct GemmGroup {
   bool sq[kGroupMax];    // which problems' tiles count in it
 };
 
-template <typename TI, typename TO, bool MF16, bool TN = false>
+template <typename TI, typename TO, bool TN = false>
 __global__ __launch_bounds__(512, 2) void gemm256p_group_kernel(GemmGroup g) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * G2_STAGE];
   const int t = xcd_remap((int)blockIdx.x, (int)gridDim.x);
@@ -774,10 +796,73 @@ __global__ __launch_bounds__(512, 2) void gemm256p_group_kernel(GemmGroup g) {
   // (tile_of), so its L2 holds 12 operand panels per K step, not 2 + 16
   int mt, nt;
   tile_of(lt, nx, (int)((g.M[p] + G2BM - 1) / G2BM), 4, mt, nt);
-  gemm256p_body<TI, NR_EPI_NONE, TO, MF16, TN>(smem, (int64_t)mt * G2BM, (int64_t)nt * G2BN, g.M[p],
-                                               g.N[p], g.K[p], (const TI*)g.A[p] + b * g.sA[p], g.lda[p],
-                                               (const TI*)g.W[p] + b * g.sW[p], g.ldw[p], nullptr, nullptr, 0,
-                                               (TO*)g.C[p] + b * g.sC[p], g.ldc[p], ea);
+  gemm256p_body<TI, NR_EPI_NONE, TO, TN>(smem, (int64_t)mt * G2BM, (int64_t)nt * G2BN, g.M[p], g.N[p], g.K[p],
+                                         (const TI*)g.A[p] + b * g.sA[p], g.lda[p], (const TI*)g.W[p] + b * g.sW[p],
+                                         g.ldw[p], nullptr, nullptr, 0, (TO*)g.C[p] + b * g.sC[p], g.ldc[p], ea);
+}
+
+// ---------------------------------------------------------------------------
+// Host side: from runtime codes to template arguments.
+template <typename T> struct TypeTag { using type = T; };
+
+// f(TypeTag<TI>, TypeTag<TO>) for a validated (dtype_in, dtype_out) pair.
+template <typename F>
+static int with_dtypes(int dtype_in, int dtype_out, F&& f) {
+  if (dtype_in == NR_F32)
+    return dtype_out == NR_F32 ? f(TypeTag<float>{}, TypeTag<float>{}) : f(TypeTag<float>{}, TypeTag<__bf16>{});
+  return dtype_out == NR_F32 ? f(TypeTag<__bf16>{}, TypeTag<float>{}) : f(TypeTag<__bf16>{}, TypeTag<__bf16>{});
+}
+
+static int bad_epilogue(int epi) {
+  set_error("nr_gemm: bad epilogue %d", epi);
+  return NR_ERR_INVALID;
+}
+
+// f(std::integral_constant<int, E>) for the runtime epilogue code.  A kernel
+// family instantiates its kernels under `if constexpr (<family>_has(E))`:
+constexpr bool tile128_has(int e) { return e >= NR_EPI_NONE && e <= NR_EPI_DRELU; }
+constexpr bool tile256_has(int e) { return e >= NR_EPI_NONE && e <= NR_EPI_SOFTMAX64; }
+constexpr bool persistent_has(int e) { return e >= NR_EPI_NONE && e <= NR_EPI_SOFTMAX64_BWD; }
+constexpr bool persistent_colsum_has(int e) { return e == NR_EPI_NONE || e == NR_EPI_RESADD || e == NR_EPI_DRELU; }
+
+template <typename F>
+static int with_epilogue(int epi, F&& f) {
+  switch (epi) {
+#define NR_EPI_CASE(E) case E: return f(std::integral_constant<int, E>{});
+    NR_EPI_CASE(NR_EPI_NONE)
+    NR_EPI_CASE(NR_EPI_RELU)
+    NR_EPI_CASE(NR_EPI_EXP)
+    NR_EPI_CASE(NR_EPI_GEGLU)
+    NR_EPI_CASE(NR_EPI_RESADD)
+    NR_EPI_CASE(NR_EPI_GELU)
+    NR_EPI_CASE(NR_EPI_RELU_DROPOUT)
+    NR_EPI_CASE(NR_EPI_DRELU)
+    NR_EPI_CASE(NR_EPI_SOFTMAX64)
+    NR_EPI_CASE(NR_EPI_SOFTMAX64_BWD)
+#undef NR_EPI_CASE
+    default: return bad_epilogue(epi);
+  }
+}
+
+// Appends the validated problem q to the group and advances the running tile
+// count; false when the tile ids would leave the int range.
+static bool group_push(GemmGroup& g, const GemmProblem& q, bool sq, int64_t* tiles) {
+  const int j = g.n;
+  g.M[j] = q.M; g.N[j] = q.N; g.K[j] = q.K;
+  g.A[j] = q.A; g.W[j] = q.W; g.C[j] = q.C;
+  g.lda[j] = q.lda; g.ldw[j] = q.ldw; g.ldc[j] = q.ldc;
+  g.sA[j] = q.sA; g.sW[j] = q.sW; g.sC[j] = q.sC;
+  g.alpha[j] = q.alpha;
+  g.sq[j] = sq;
+  g.ntn[j] = (int)(q.N / G2BN);
+  const int64_t tpb = ((q.M + G2BM - 1) / G2BM) * g.ntn[j];
+  if (tpb > 0x7fffffff) return false;
+  g.tpb[j] = (int)tpb;
+  *tiles += tpb * q.batch;
+  if (*tiles > 0x7fffffff) return false;
+  g.tile_end[j] = (int)*tiles;
+  g.n = j + 1;
+  return true;
 }
 
 int gemm_group_dispatch(int dtype_in, int dtype_out, const GemmProblem* probs, int n, hipStream_t s, float* sq_part,
@@ -786,7 +871,6 @@ int gemm_group_dispatch(int dtype_in, int dtype_out, const GemmProblem* probs, i
   NR_CHECK_ARG(dtype_out == NR_F32 || dtype_out == NR_BF16, "gemm_group: bad dtype_out %d", dtype_out);
   NR_CHECK_ARG(n >= 0 && n <= kGroupMax, "gemm_group: n=%d outside [0, %d]", n, kGroupMax);
   GemmGroup g{};
-  g.n = 0;
   int64_t tiles = 0;
   const int64_t bk = dtype_in == NR_F32 ? 32 : 64, e16 = dtype_in == NR_F32 ? 4 : 8;
   const int64_t vo = dtype_out == NR_F32 ? 4 : 8;
@@ -801,36 +885,20 @@ int gemm_group_dispatch(int dtype_in, int dtype_out, const GemmProblem* probs, i
                      q.ldc % vo == 0 && ((uintptr_t)q.A & 15) == 0 && ((uintptr_t)q.W & 15) == 0 &&
                      ((uintptr_t)q.C & 15) == 0 && q.sA % e16 == 0 && q.sW % e16 == 0 && q.sC % vo == 0,
                  "gemm_group: problem %d operands must be 16-byte aligned with 16-byte row / batch strides", i);
-    const int j = g.n++;
-    g.M[j] = q.M; g.N[j] = q.N; g.K[j] = q.K;
-    g.A[j] = q.A; g.W[j] = q.W; g.C[j] = q.C;
-    g.lda[j] = q.lda; g.ldw[j] = q.ldw; g.ldc[j] = q.ldc;
-    g.sA[j] = q.sA; g.sW[j] = q.sW; g.sC[j] = q.sC;
-    g.alpha[j] = q.alpha;
-    g.sq[j] = sq ? sq[i] : false;
-    g.ntn[j] = (int)(q.N / G2BN);
-    const int64_t tpb = ((q.M + G2BM - 1) / G2BM) * g.ntn[j];
-    NR_CHECK_ARG(tpb <= 0x7fffffff, "gemm_group: too many tiles");
-    g.tpb[j] = (int)tpb;
-    tiles += tpb * q.batch;
-    NR_CHECK_ARG(tiles <= 0x7fffffff, "gemm_group: too many tiles");
-    g.tile_end[j] = (int)tiles;
+    NR_CHECK_ARG(group_push(g, q, sq && sq[i], &tiles), "gemm_group: too many tiles");
   }
   if (n_tiles) *n_tiles = (int)tiles;
   if (g.n == 0) return NR_OK;
   NR_CHECK_ARG(!sq_part || tiles <= sq_cap, "gemm_group: %lld workgroups exceed the %d sum-of-squares slots",
                (long long)tiles, sq_cap);
   g.sq_part = sq_part;
-  if (dtype_in == NR_F32 && dtype_out == NR_F32)
-    hipLaunchKernelGGL((gemm256p_group_kernel<float, float, false>), dim3((unsigned)tiles), dim3(512), 0, s, g);
-  else if (dtype_in == NR_F32)
-    hipLaunchKernelGGL((gemm256p_group_kernel<float, __bf16, false>), dim3((unsigned)tiles), dim3(512), 0, s, g);
-  else if (dtype_out == NR_F32)
-    hipLaunchKernelGGL((gemm256p_group_kernel<__bf16, float, true>), dim3((unsigned)tiles), dim3(512), 0, s, g);
-  else
-    hipLaunchKernelGGL((gemm256p_group_kernel<__bf16, __bf16, true>), dim3((unsigned)tiles), dim3(512), 0, s, g);
-  NR_CHECK_LAUNCH("gemm_group");
-  return NR_OK;
+  return with_dtypes(dtype_in, dtype_out, [&](auto ti, auto to) -> int {
+    using TI = typename decltype(ti)::type;
+    using TO = typename decltype(to)::type;
+    hipLaunchKernelGGL((gemm256p_group_kernel<TI, TO>), dim3((unsigned)tiles), dim3(512), 0, s, g);
+    NR_CHECK_LAUNCH("gemm_group");
+    return NR_OK;
+  });
 }
 
 // Grouped TN launch (gemm256p_body TN): problem i computes C = alpha A^T W with A
@@ -857,19 +925,7 @@ int gemm_group_tn_dispatch(int dtype_out, const GemmProblem* probs, int n, hipSt
                      q.ldc % vo == 0 && ((uintptr_t)q.A & 15) == 0 && ((uintptr_t)q.W & 15) == 0 &&
                      ((uintptr_t)q.C & 15) == 0 && q.sA % 8 == 0 && q.sW % 8 == 0 && q.sC % vo == 0,
                  "gemm_group_tn: problem %d operands must be 16-byte aligned with 16-byte row / batch strides", i);
-    const int j = g.n++;
-    g.M[j] = q.M; g.N[j] = q.N; g.K[j] = q.K;
-    g.A[j] = q.A; g.W[j] = q.W; g.C[j] = q.C;
-    g.lda[j] = q.lda; g.ldw[j] = q.ldw; g.ldc[j] = q.ldc;
-    g.sA[j] = q.sA; g.sW[j] = q.sW; g.sC[j] = q.sC;
-    g.alpha[j] = q.alpha;
-    g.sq[j] = sq ? sq[i] : false;
-    g.ntn[j] = (int)(q.N / G2BN);
-    const int64_t tpb = (q.M / G2BM) * g.ntn[j];
-    g.tpb[j] = (int)tpb;
-    tiles += tpb * q.batch;
-    NR_CHECK_ARG(tiles <= 0x7fffffff, "gemm_group_tn: too many tiles");
-    g.tile_end[j] = (int)tiles;
+    NR_CHECK_ARG(group_push(g, q, sq && sq[i], &tiles), "gemm_group_tn: too many tiles");
   }
   if (n_tiles) *n_tiles = (int)tiles;
   if (g.n == 0) return NR_OK;
@@ -877,9 +933,9 @@ int gemm_group_tn_dispatch(int dtype_out, const GemmProblem* probs, int n, hipSt
                (long long)tiles, sq_cap);
   g.sq_part = sq_part;
   if (dtype_out == NR_F32)
-    hipLaunchKernelGGL((gemm256p_group_kernel<__bf16, float, true, true>), dim3((unsigned)tiles), dim3(512), 0, s, g);
+    hipLaunchKernelGGL((gemm256p_group_kernel<__bf16, float, true>), dim3((unsigned)tiles), dim3(512), 0, s, g);
   else
-    hipLaunchKernelGGL((gemm256p_group_kernel<__bf16, __bf16, true, true>), dim3((unsigned)tiles), dim3(512), 0, s, g);
+    hipLaunchKernelGGL((gemm256p_group_kernel<__bf16, __bf16, true>), dim3((unsigned)tiles), dim3(512), 0, s, g);
   NR_CHECK_LAUNCH("gemm_group_tn");
   return NR_OK;
 }
@@ -930,7 +986,8 @@ __device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {  // v_pk_max_i16 w
 // not inline asm, so the compiler's own wait insertion sees them: it then knows
 // the older stores have retired and keeps its waits for the epilogue's
 // residual loads counted instead of vmcnt(0).
-constexpr unsigned kVmcnt0 = 0x0F70, kVmcnt4 = 0x0F74, kVmcnt8 = 0x0F78, kVmcnt6 = 0x0F76, kVmcnt9 = 0x0F79;  // lgkmcnt/expcnt left at max
+// (lgkmcnt / expcnt left at max)
+constexpr unsigned kVmcnt0 = 0x0F70, kVmcnt4 = 0x0F74, kVmcnt8 = 0x0F78, kVmcnt6 = 0x0F76, kVmcnt9 = 0x0F79;
 
 // LNF (LayerNorm folded into the epilogue): per tile, every wave's (u, c)
 // column slices (2 x 256 B) and the tile's 256 row stats (2 KiB), in two
@@ -1115,14 +1172,6 @@ __global__ __launch_bounds__(512, 2) void gemm256t_kernel(int64_t M, int64_t N, 
               __builtin_bit_cast(bf16x8, fb[j][f]), __builtin_bit_cast(bf16x8, fa[i][f]), acc[4 * qm + i][2 * qn + j],
               0, 0, 0);
   };
-#define NR_PHASE_SYNC_MMA(QM, NI, FB)                   \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_s_setprio(1);                       \
-  if constexpr (!IDLE) mma(QM, NI, FB);               \
-  __builtin_amdgcn_s_setprio(0);                       \
-  __builtin_amdgcn_s_barrier();
   // K step kt of the current tile (stage st).  Step kt + 2 is prefetched into
   // this stage, each quarter at least one phase after its last read (both
   // wave groups' reads of phase p retire before the barrier instance the
@@ -1187,7 +1236,8 @@ __global__ __launch_bounds__(512, 2) void gemm256t_kernel(int64_t M, int64_t N, 
     }
     a1p = pf;
     a1k = kf;
-    __builtin_amdgcn_sched_barrier(0);  // the B0 reads stay ahead of the MFMA cluster (not waited for: P4's MFMAs do not use them)
+    // the B0 reads stay ahead of the MFMA cluster (not waited for: P4's MFMAs do not use them)
+    __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_s_setprio(1);
     if constexpr (!IDLE) mma(1, 0, fb0);
@@ -1281,6 +1331,20 @@ __global__ __launch_bounds__(512, 2) void gemm256t_kernel(int64_t M, int64_t N, 
       for (int p = 0; p < 2; ++p) rq[mi & 3][p] = *reinterpret_cast<const uint4*>(R + row * ldr + col0 + 32 * p + qo);
       __builtin_amdgcn_sched_barrier(0);  // issue order = use order: counted waits, not vmcnt(0)
     };
+    // row group mi's residual from the store layout to the accumulator layout
+    // (y[ni][r] beside acc[mi][ni][r]) by the same, involutive, swap
+    auto unpack_r = [&](int mi, float(&y)[4][4]) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const uint4 q = rq[mi & 3][p];
+        const uint4 s = swap_pair16(uint2{q.x, q.y}, uint2{q.z, q.w});
+        const uint32_t w[2][2] = {{s.x, s.y}, {s.z, s.w}};  // tile 2p, tile 2p + 1
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) y[2 * p + h][r] = (r & 1) ? bf16_hi(w[h][r >> 1]) : bf16_lo(w[h][r >> 1]);
+      }
+    };
     constexpr bool kRes = EPI == NR_EPI_RESADD || EPI == NR_EPI_SOFTMAX64_BWD || EPI == NR_EPI_DRELU;
     if constexpr (kRes) {
 #pragma unroll
@@ -1323,73 +1387,42 @@ __global__ __launch_bounds__(512, 2) void gemm256t_kernel(int64_t M, int64_t N, 
         if (live) *reinterpret_cast<uint4*>(C + row * ldc + col0 / 2 + qo) = v;
         __builtin_amdgcn_sched_barrier(0);  // one row group at a time: bounds the erf temporaries' live ranges
       } else {
-        if constexpr (EPI == NR_EPI_RESADD) {
-          // the residual to the accumulator layout by the same (involutive) swap
+        // RESADD: the residual; DRELU: the forward output, dZ = dY * (y > 0 ? 1 / (1 - p) : 0);
+        // SOFTMAX64_BWD: the softmax output P
+        float y[4][4];
+        if constexpr (kRes) unpack_r(mi, y);
+        if constexpr (EPI == NR_EPI_RESADD || EPI == NR_EPI_DRELU) {
 #pragma unroll
-          for (int p = 0; p < 2; ++p) {
-            const uint4 s = swap_pair16(uint2{rq[mi & 3][p].x, rq[mi & 3][p].y}, uint2{rq[mi & 3][p].z, rq[mi & 3][p].w});
-            const uint32_t w[2][2] = {{s.x, s.y}, {s.z, s.w}};  // tile 2p, tile 2p + 1
+          for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const uint32_t u = w[h][r >> 1];
-                acc[mi][2 * p + h][r] += (r & 1) ? bf16_hi(u) : bf16_lo(u);
-              }
-          }
-        }
-        if constexpr (EPI == NR_EPI_DRELU) {
-          // relu / dropout backward: dZ = dY * (y > 0 ? 1 / (1 - p) : 0), y = the
-          // forward output (R) in the accumulator layout by the same swap
-#pragma unroll
-          for (int p = 0; p < 2; ++p) {
-            const uint4 s = swap_pair16(uint2{rq[mi & 3][p].x, rq[mi & 3][p].y}, uint2{rq[mi & 3][p].z, rq[mi & 3][p].w});
-            const uint32_t w[2][2] = {{s.x, s.y}, {s.z, s.w}};
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const uint32_t u = w[h][r >> 1];
-                const float y = (r & 1) ? bf16_hi(u) : bf16_lo(u);
-                acc[mi][2 * p + h][r] = y > 0.f ? acc[mi][2 * p + h][r] * ea.scale : 0.f;
-              }
-          }
+            for (int r = 0; r < 4; ++r) {
+              if constexpr (EPI == NR_EPI_RESADD) acc[mi][ni][r] += y[ni][r];
+              else acc[mi][ni][r] = y[ni][r] > 0.f ? acc[mi][ni][r] * ea.scale : 0.f;
+            }
         }
         float v[4][4];
         if constexpr (EPI == NR_EPI_SOFTMAX64_BWD) {
-          // dS = P (dP - sum_group P dP): acc = dP, P from R in the accumulator layout;
-          // the wave's 64 columns are one softmax group (lanes l, l ^ 16, l ^ 32, l ^ 48)
-          float pv[4][4];
-#pragma unroll
-          for (int p = 0; p < 2; ++p) {
-            const uint4 sw = swap_pair16(uint2{rq[mi & 3][p].x, rq[mi & 3][p].y}, uint2{rq[mi & 3][p].z, rq[mi & 3][p].w});
-            const uint32_t w[2][2] = {{sw.x, sw.y}, {sw.z, sw.w}};
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const uint32_t u = w[h][r >> 1];
-                pv[2 * p + h][r] = (r & 1) ? bf16_hi(u) : bf16_lo(u);
-              }
-          }
+          // dS = P (dP - sum_group P dP): acc = dP, P = y; the wave's 64 columns are one
+          // softmax group (lanes l, l ^ 16, l ^ 32, l ^ 48)
           float dot = 0.f;
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) dot = fmaf(pv[ni][r], acc[mi][ni][r], dot);
+            for (int r = 0; r < 4; ++r) dot = fmaf(y[ni][r], acc[mi][ni][r], dot);
           dot += __shfl_xor(dot, 16, 64);
           dot += __shfl_xor(dot, 32, 64);
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[mi][ni][r] = pv[ni][r] * (acc[mi][ni][r] - dot);
+            for (int r = 0; r < 4; ++r) acc[mi][ni][r] = y[ni][r] * (acc[mi][ni][r] - dot);
         }
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           // the lane's 4 consecutive columns col0 + 16 ni + 4 q4 .. +3 are one group
           // of the dropout stream: one hash for the four
           uint64_t dh = 0;
-          if constexpr (EPI == NR_EPI_RELU_DROPOUT) dh = drop_hash4(ea.seed, (uint64_t)(row * N + col0 + 16 * ni + 4 * q4) >> 2);
+          if constexpr (EPI == NR_EPI_RELU_DROPOUT)
+            dh = drop_hash4(ea.seed, (uint64_t)(row * N + col0 + 16 * ni + 4 * q4) >> 2);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float x = acc[mi][ni][r];
@@ -1556,101 +1589,98 @@ static bool persistent_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t 
   return K >= 128 && K % 128 == 0 && M * lda * 2 <= kMax && N * ldw * 2 <= kMax;
 }
 
+// "This nr_gemm problem (N % 256 == 0, 16-byte aligned output) runs on the
+// persistent kernel": bf16 in and out, an operand stream it can walk, and for
+// DRELU a forward output R it can read in the epilogue's 16-byte residual
+// window (RESADD's R is covered by the output alignment check of the caller).
+static bool persistent_takes(bool bf16_io, int epi, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                             const void* R, int64_t ldr) {
+  return bf16_io && persistent_ok(M, N, K, lda, ldw) &&
+         (epi != NR_EPI_DRELU || (((uintptr_t)R & 15) == 0 && ldr % 8 == 0));
+}
+
+// Set-up of a persistent launch: the tile grid and its schedule.
+struct PersistentGrid {
+  int ntn, ntm, nt, nh;  // N tiles, M tiles, full tiles, half units (persistent_schedule)
+  unsigned wgs;
+};
+static bool persistent_grid(int64_t M, int64_t N, PersistentGrid* p) {  // false: too many tiles
+  p->ntn = (int)(N / G2BN);
+  const int64_t ntm = (M + G2BM - 1) / G2BM;
+  const int64_t tiles = ntm * p->ntn;
+  if (tiles > (1ll << 30)) return false;
+  p->ntm = (int)ntm;
+  p->wgs = (unsigned)persistent_schedule(tiles, &p->nt, &p->nh);
+  return true;
+}
+template <int EPI, bool LNF = false, bool CS = false>
+static void persistent_launch(const PersistentGrid& p, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
+                              const void* W, int64_t ldw, const float* bias, const void* R, int64_t ldr, void* C,
+                              int64_t ldc, const EpiArgs& ea, hipStream_t s) {
+  hipLaunchKernelGGL((gemm256t_kernel<EPI, LNF, CS>), dim3(p.wgs), dim3(512), 0, s, M, N, K, (const __bf16*)A, lda,
+                     (const __bf16*)W, ldw, bias, (const __bf16*)R, ldr, (__bf16*)C, ldc, ea, p.ntn, p.ntm, p.nt, p.nh);
+}
+
+// One launcher per kernel family.  Each turns the runtime epilogue into a
+// template argument (with_epilogue) and instantiates only its family's set.
 static int launch_gemm256_t(int epi, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* W,
                             int64_t ldw, const float* bias, const void* R, int64_t ldr, void* C, int64_t ldc,
                             const EpiArgs& ea, hipStream_t s) {
-  const int ntn = (int)(N / G2BN);
-  const int64_t ntm = (M + G2BM - 1) / G2BM;
-  const int64_t tiles = ntm * ntn;
-  if (tiles > (1ll << 30)) {
+  PersistentGrid p;
+  if (!persistent_grid(M, N, &p)) {
     set_error("nr_gemm: too many tiles");
     return NR_ERR_UNSUPPORTED;
   }
-  int nt, nh;
-  const dim3 grid((unsigned)persistent_schedule(tiles, &nt, &nh));
-  const __bf16* a = (const __bf16*)A;
-  const __bf16* w = (const __bf16*)W;
-  const __bf16* r = (const __bf16*)R;
-  __bf16* c = (__bf16*)C;
-#define NR_T(E) hipLaunchKernelGGL((gemm256t_kernel<E>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea, ntn, (int)ntm, nt, nh)
-#define NR_TC(E) hipLaunchKernelGGL((gemm256t_kernel<E, false, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea, ntn, (int)ntm, nt, nh)
-  if (ea.colsum) {
-    switch (epi) {
-      case NR_EPI_NONE: NR_TC(NR_EPI_NONE); break;
-      case NR_EPI_RESADD: NR_TC(NR_EPI_RESADD); break;
-      case NR_EPI_DRELU: NR_TC(NR_EPI_DRELU); break;
-      default: set_error("nr_gemm: column sums with epilogue %d unsupported", epi); return NR_ERR_INVALID;
+  return with_epilogue(epi, [&](auto e) -> int {
+    constexpr int E = decltype(e)::value;
+    if (ea.colsum) {
+      if constexpr (persistent_colsum_has(E)) {
+        persistent_launch<E, false, true>(p, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
+      } else {
+        set_error("nr_gemm: column sums with epilogue %d unsupported", E);
+        return NR_ERR_INVALID;
+      }
+    } else {
+      static_assert(persistent_has(E), "the persistent kernel has every epilogue");
+      persistent_launch<E>(p, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
     }
     NR_CHECK_LAUNCH("nr_gemm");
     return NR_OK;
-  }
-#undef NR_TC
-  switch (epi) {
-    case NR_EPI_DRELU: NR_T(NR_EPI_DRELU); break;
-    case NR_EPI_NONE: NR_T(NR_EPI_NONE); break;
-    case NR_EPI_RELU: NR_T(NR_EPI_RELU); break;
-    case NR_EPI_EXP: NR_T(NR_EPI_EXP); break;
-    case NR_EPI_GEGLU: NR_T(NR_EPI_GEGLU); break;
-    case NR_EPI_RESADD: NR_T(NR_EPI_RESADD); break;
-    case NR_EPI_GELU: NR_T(NR_EPI_GELU); break;
-    case NR_EPI_RELU_DROPOUT: NR_T(NR_EPI_RELU_DROPOUT); break;
-    case NR_EPI_SOFTMAX64: NR_T(NR_EPI_SOFTMAX64); break;
-    case NR_EPI_SOFTMAX64_BWD: NR_T(NR_EPI_SOFTMAX64_BWD); break;
-    default: set_error("nr_gemm: bad epilogue %d", epi); return NR_ERR_INVALID;
-  }
-#undef NR_T
-  NR_CHECK_LAUNCH("nr_gemm");
-  return NR_OK;
+  });
 }
 
 template <typename TI, typename TO>
 static int launch_gemm256_p(int epi, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
-                          const void* W, int64_t ldw, const float* bias, const void* R, int64_t ldr,
-                          void* C, int64_t ldc, const EpiArgs& ea, hipStream_t s) {
-  dim3 grid((unsigned)(N / G2BN), (unsigned)((M + G2BM - 1) / G2BM));
-  const TI* a = (const TI*)A;
-  const TI* w = (const TI*)W;
-  const TO* r = (const TO*)R;
-  TO* c = (TO*)C;
-  switch (epi) {
-    case NR_EPI_NONE: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_NONE, TO>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_RELU: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_RELU, TO>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_EXP: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_EXP, TO>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_GEGLU: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_GEGLU, TO>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_RESADD: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_RESADD, TO>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_GELU: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_GELU, TO>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_RELU_DROPOUT: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_RELU_DROPOUT, TO>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_DRELU: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_DRELU, TO>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_SOFTMAX64: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_SOFTMAX64, TO>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    default: set_error("nr_gemm: bad epilogue %d", epi); return NR_ERR_INVALID;
-  }
-  NR_CHECK_LAUNCH("nr_gemm");
-  return NR_OK;
+                            const void* W, int64_t ldw, const float* bias, const void* R, int64_t ldr,
+                            void* C, int64_t ldc, const EpiArgs& ea, hipStream_t s) {
+  const dim3 grid((unsigned)(N / G2BN), (unsigned)((M + G2BM - 1) / G2BM));
+  return with_epilogue(epi, [&](auto e) -> int {
+    constexpr int E = decltype(e)::value;
+    if constexpr (tile256_has(E))
+      hipLaunchKernelGGL((gemm256p_kernel<TI, E, TO>), grid, dim3(512), 0, s, M, N, K, (const TI*)A, lda, (const TI*)W,
+                         ldw, bias, (const TO*)R, ldr, (TO*)C, ldc, ea);
+    else
+      return bad_epilogue(E);
+    NR_CHECK_LAUNCH("nr_gemm");
+    return NR_OK;
+  });
 }
 
 template <typename TI, typename TO>
-static int launch_gemm256_p16(int epi, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
-                          const void* W, int64_t ldw, const float* bias, const void* R, int64_t ldr,
-                          void* C, int64_t ldc, const EpiArgs& ea, hipStream_t s) {
-  dim3 grid((unsigned)(N / G2BN), (unsigned)((M + G2BM - 1) / G2BM));
-  const TI* a = (const TI*)A;
-  const TI* w = (const TI*)W;
-  const TO* r = (const TO*)R;
-  TO* c = (TO*)C;
-  switch (epi) {
-    case NR_EPI_NONE: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_NONE, TO, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_RELU: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_RELU, TO, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_EXP: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_EXP, TO, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_GEGLU: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_GEGLU, TO, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_RESADD: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_RESADD, TO, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_GELU: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_GELU, TO, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_RELU_DROPOUT: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_RELU_DROPOUT, TO, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_DRELU: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_DRELU, TO, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_SOFTMAX64: hipLaunchKernelGGL((gemm256p_kernel<TI, NR_EPI_SOFTMAX64, TO, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    default: set_error("nr_gemm: bad epilogue %d", epi); return NR_ERR_INVALID;
-  }
-  NR_CHECK_LAUNCH("nr_gemm");
-  return NR_OK;
+static int launch_gemm_t(int epi, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
+                         const void* W, int64_t ldw, const float* bias, const void* R, int64_t ldr,
+                         void* C, int64_t ldc, const EpiArgs& ea, hipStream_t s) {
+  const dim3 grid((unsigned)(N / GBN), (unsigned)((M + GBM - 1) / GBM));
+  return with_epilogue(epi, [&](auto e) -> int {
+    constexpr int E = decltype(e)::value;
+    if constexpr (tile128_has(E))
+      hipLaunchKernelGGL((gemm_kernel<TI, E, TO>), grid, dim3(256), 0, s, M, N, K, (const TI*)A, lda, (const TI*)W, ldw,
+                         bias, (const TO*)R, ldr, (TO*)C, ldc, ea);
+    else
+      return bad_epilogue(E);
+    NR_CHECK_LAUNCH("nr_gemm");
+    return NR_OK;
+  });
 }
 
 // bf16: 16x16x32 MFMA tiles (5-8 % faster than 32x32x16 on the pooler shapes,
@@ -1664,16 +1694,13 @@ static int launch_gemm256(int epi, int64_t M, int64_t N, int64_t K, const void* 
                           void* C, int64_t ldc, const EpiArgs& ea, hipStream_t s) {
   EpiArgs eg = ea;
   eg.group_m = kGemmGroupM;
-  if (ea.colsum && !(sizeof(TI) == 2 && sizeof(TO) == 2 && persistent_ok(M, N, K, lda, ldw) &&
-                     (epi != NR_EPI_DRELU || (((uintptr_t)R & 15) == 0 && ldr % 8 == 0)))) {
+  const bool persistent = persistent_takes(sizeof(TI) == 2 && sizeof(TO) == 2, epi, M, N, K, lda, ldw, R, ldr);
+  if (ea.colsum && !persistent) {
     set_error("nr_gemm: column sums need the persistent bf16 kernel (bf16 in/out, K %% 128, 16-byte rows)");
     return NR_ERR_UNSUPPORTED;
   }
-  // persistent kernel for bf16 -> bf16 (DRELU reads its forward output in the
-  // epilogue's residual window, like RESADD)
   if constexpr (sizeof(TI) == 2 && sizeof(TO) == 2) {
-    if (persistent_ok(M, N, K, lda, ldw) && (epi != NR_EPI_DRELU || (((uintptr_t)R & 15) == 0 && ldr % 8 == 0)))
-      return launch_gemm256_t(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, eg, s);
+    if (persistent) return launch_gemm256_t(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, eg, s);
     // A past the 32-bit buffer range (e.g. the title encoder's FFN2, [M x 4096]
     // at M > 512 k tokens): persistent launches over row chunks of < 4 GiB of A.
     // A row's K chain and epilogue do not depend on its chunk, so the result is
@@ -1691,7 +1718,6 @@ static int launch_gemm256(int epi, int64_t M, int64_t N, int64_t K, const void* 
       return NR_OK;
     }
   }
-  if constexpr (sizeof(TI) == 2) return launch_gemm256_p16<TI, TO>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, eg, s);
   return launch_gemm256_p<TI, TO>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, eg, s);
 }
 
@@ -1711,49 +1737,17 @@ int gemm_lnfold_dispatch(int epi, int64_t M, int64_t N, int64_t K, const void* A
                    ((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0 &&
                    ((uintptr_t)stats & 7) == 0 && ((uintptr_t)uc & 3) == 0,
                "nr_gemm_lnfold: operands must be 16-byte aligned with 16-byte row strides");
-  const int ntn = (int)(N / G2BN);
-  const int64_t ntm = (M + G2BM - 1) / G2BM;
-  NR_CHECK_ARG(ntm * ntn <= (1ll << 30), "nr_gemm_lnfold: too many tiles");
-  int nt, nh;
-  const dim3 grid((unsigned)persistent_schedule(ntm * ntn, &nt, &nh));
+  PersistentGrid p;
+  NR_CHECK_ARG(persistent_grid(M, N, &p), "nr_gemm_lnfold: too many tiles");
   EpiArgs ea{0, 0, 1.f};
   ea.group_m = kGemmGroupM;
   ea.ln_stats = stats;
   ea.ln_uc = uc;
-  const __bf16* a = (const __bf16*)A;
-  const __bf16* w = (const __bf16*)W;
-  __bf16* c = (__bf16*)C;
   if (epi == NR_EPI_GEGLU)
-    hipLaunchKernelGGL((gemm256t_kernel<NR_EPI_GEGLU, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw, nullptr,
-                       nullptr, 0, c, ldc, ea, ntn, (int)ntm, nt, nh);
+    persistent_launch<NR_EPI_GEGLU, true>(p, M, N, K, A, lda, W, ldw, nullptr, nullptr, 0, C, ldc, ea, s);
   else
-    hipLaunchKernelGGL((gemm256t_kernel<NR_EPI_SOFTMAX64, true>), grid, dim3(512), 0, s, M, N, K, a, lda, w, ldw,
-                       nullptr, nullptr, 0, c, ldc, ea, ntn, (int)ntm, nt, nh);
+    persistent_launch<NR_EPI_SOFTMAX64, true>(p, M, N, K, A, lda, W, ldw, nullptr, nullptr, 0, C, ldc, ea, s);
   NR_CHECK_LAUNCH("nr_gemm_lnfold");
-  return NR_OK;
-}
-
-template <typename TI, typename TO>
-static int launch_gemm_t(int epi, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
-                         const void* W, int64_t ldw, const float* bias, const void* R, int64_t ldr,
-                         void* C, int64_t ldc, const EpiArgs& ea, hipStream_t s) {
-  dim3 grid((unsigned)(N / GBN), (unsigned)((M + GBM - 1) / GBM));
-  const TI* a = (const TI*)A;
-  const TI* w = (const TI*)W;
-  const TO* r = (const TO*)R;
-  TO* c = (TO*)C;
-  switch (epi) {
-    case NR_EPI_NONE: hipLaunchKernelGGL((gemm_kernel<TI, NR_EPI_NONE, TO>), grid, dim3(256), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_RELU: hipLaunchKernelGGL((gemm_kernel<TI, NR_EPI_RELU, TO>), grid, dim3(256), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_EXP: hipLaunchKernelGGL((gemm_kernel<TI, NR_EPI_EXP, TO>), grid, dim3(256), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_GEGLU: hipLaunchKernelGGL((gemm_kernel<TI, NR_EPI_GEGLU, TO>), grid, dim3(256), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_RESADD: hipLaunchKernelGGL((gemm_kernel<TI, NR_EPI_RESADD, TO>), grid, dim3(256), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_GELU: hipLaunchKernelGGL((gemm_kernel<TI, NR_EPI_GELU, TO>), grid, dim3(256), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_RELU_DROPOUT: hipLaunchKernelGGL((gemm_kernel<TI, NR_EPI_RELU_DROPOUT, TO>), grid, dim3(256), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    case NR_EPI_DRELU: hipLaunchKernelGGL((gemm_kernel<TI, NR_EPI_DRELU, TO>), grid, dim3(256), 0, s, M, N, K, a, lda, w, ldw, bias, r, ldr, c, ldc, ea); break;
-    default: set_error("nr_gemm: bad epilogue %d", epi); return NR_ERR_INVALID;
-  }
-  NR_CHECK_LAUNCH("nr_gemm");
   return NR_OK;
 }
 
@@ -1769,11 +1763,13 @@ int gemm_dispatch_ex(int dtype_in, int dtype_out, int epi, int64_t M, int64_t N,
                      const void* R, int64_t ldr, void* C, int64_t ldc, const EpiArgs& ea, hipStream_t s) {
   NR_CHECK_ARG(dtype_in == NR_F32 || dtype_in == NR_BF16, "nr_gemm: bad dtype_in %d", dtype_in);
   NR_CHECK_ARG(dtype_out == NR_F32 || dtype_out == NR_BF16, "nr_gemm: bad dtype_out %d", dtype_out);
-  NR_CHECK_ARG(M >= 0 && N > 0 && K > 0, "nr_gemm: bad shape M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
+  NR_CHECK_ARG(M >= 0 && N > 0 && K > 0, "nr_gemm: bad shape M=%lld N=%lld K=%lld", (long long)M, (long long)N,
+               (long long)K);
   if (M == 0) return NR_OK;
   const int64_t bk = dtype_in == NR_F32 ? 32 : 64;
   if (N % GBN != 0 || K % bk != 0) {
-    set_error("nr_gemm: unsupported shape N=%lld (need %%128) K=%lld (need %%%lld)", (long long)N, (long long)K, (long long)bk);
+    set_error("nr_gemm: unsupported shape N=%lld (need %%128) K=%lld (need %%%lld)", (long long)N, (long long)K,
+              (long long)bk);
     return NR_ERR_UNSUPPORTED;
   }
   NR_CHECK_ARG(A && W && C, "nr_gemm: null operand");
@@ -1781,7 +1777,8 @@ int gemm_dispatch_ex(int dtype_in, int dtype_out, int epi, int64_t M, int64_t N,
                "nr_gemm: RESADD/DRELU/SOFTMAX64_BWD need R");
   NR_CHECK_ARG(epi >= NR_EPI_NONE && epi <= NR_EPI_SOFTMAX64_BWD, "nr_gemm: bad epilogue %d", epi);
   if (epi == NR_EPI_SOFTMAX64_BWD &&
-      !(dtype_in == NR_BF16 && dtype_out == NR_BF16 && N % G2BN == 0 && persistent_ok(M, N, K, lda, ldw) &&
+      !(N % G2BN == 0 &&
+        persistent_takes(dtype_in == NR_BF16 && dtype_out == NR_BF16, epi, M, N, K, lda, ldw, R, ldr) &&
         ((uintptr_t)C & 15) == 0 && ldc % 8 == 0 && ((uintptr_t)R & 15) == 0 && ldr % 8 == 0)) {
     set_error("nr_gemm: SOFTMAX64_BWD runs on the persistent bf16 kernel only (bf16 in/out, N %% 256, K >= 128, "
               "16-byte aligned rows)");
@@ -1797,27 +1794,20 @@ int gemm_dispatch_ex(int dtype_in, int dtype_out, int epi, int64_t M, int64_t N,
   // 256x256 glds kernel when the shape allows (every pooler GEMM); the
   // 128x128 register-staged kernel covers N % 256 != 0 and unaligned outputs.
   const int64_t vo = dtype_out == NR_F32 ? 4 : 8;  // the LDS-staged epilogue stores 16 B per lane
-  const bool aligned_out = ((uintptr_t)C & 15) == 0 && ldc % vo == 0 &&
-                           ((epi != NR_EPI_RESADD && epi != NR_EPI_DRELU) || (((uintptr_t)R & 15) == 0 && ldr % vo == 0));
+  const bool res_epi = epi == NR_EPI_RESADD || epi == NR_EPI_DRELU;
+  const bool aligned_out =
+      ((uintptr_t)C & 15) == 0 && ldc % vo == 0 && (!res_epi || (((uintptr_t)R & 15) == 0 && ldr % vo == 0));
   const bool big = (N % G2BN == 0) && aligned_out;
   if (epi == NR_EPI_SOFTMAX64 && !big) {
     set_error("nr_gemm: SOFTMAX64 needs N %% 256 == 0 and 16-byte aligned output rows");
     return NR_ERR_UNSUPPORTED;
   }
-  if (dtype_in == NR_F32) {
-    if (big) {
-      if (dtype_out == NR_F32) return launch_gemm256<float, float>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
-      return launch_gemm256<float, __bf16>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
-    }
-    if (dtype_out == NR_F32) return launch_gemm_t<float, float>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
-    return launch_gemm_t<float, __bf16>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
-  }
-  if (big) {
-    if (dtype_out == NR_F32) return launch_gemm256<__bf16, float>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
-    return launch_gemm256<__bf16, __bf16>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
-  }
-  if (dtype_out == NR_F32) return launch_gemm_t<__bf16, float>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
-  return launch_gemm_t<__bf16, __bf16>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
+  return with_dtypes(dtype_in, dtype_out, [&](auto ti, auto to) -> int {
+    using TI = typename decltype(ti)::type;
+    using TO = typename decltype(to)::type;
+    if (big) return launch_gemm256<TI, TO>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
+    return launch_gemm_t<TI, TO>(epi, M, N, K, A, lda, W, ldw, bias, R, ldr, C, ldc, ea, s);
+  });
 }
 
 }  // namespace nr

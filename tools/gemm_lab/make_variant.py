@@ -473,9 +473,9 @@ __device__ __forceinline__ void gelu_erf2x2(f32x2v& g0, f32x2v& g1) {
           pk[ni] = uint2{pack_bf16x2(o0.x, o0.y), pack_bf16x2(o1.x, o1.y)};"""),
     ],
     "noprio": [
-        ("  __builtin_amdgcn_s_setprio(1);                       \\\n  mma(QM, NI, FB);                                     \\\n"
+        ("  __builtin_amdgcn_s_setprio(1);                       \\\n  if constexpr (!IDLE) mma(QM, NI, FB);               \\\n"
          "  __builtin_amdgcn_s_setprio(0);                       \\\n",
-         "  mma(QM, NI, FB);                                     \\\n"),
+         "  if constexpr (!IDLE) mma(QM, NI, FB);               \\\n"),
     ],
 }
 
