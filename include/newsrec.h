@@ -78,7 +78,7 @@ int nr_version(void);
 
 /* Hash of the sources the library was built from (16 hex digits: sha256 of
  * csrc/{capi,gemm,pool_score,rowops,rank,encoder,train,metrics,comm,latent_train,final_train}.hip,
- * csrc/nr_common.h, csrc/nr_rows.h and this header, concatenated in that order); the Python
+ * csrc/nr_common.h, csrc/nr_rows.h, csrc/nr_train.h and this header, concatenated in that order); the Python
  * loader refuses a library whose hash differs from the tree it sits in. */
 const char* nr_build_hash(void);
 

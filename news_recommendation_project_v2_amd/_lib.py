@@ -20,7 +20,7 @@ INCLUDE = Path(__file__).resolve().parent.parent / "include"
 HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip", "encoder.hip", "train.hip",
                "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip")
 # the headers they include (every object is rebuilt when one changes), hashed after the sources
-HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", INCLUDE / "newsrec.h")
+HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", INCLUDE / "newsrec.h")
 
 
 def hip_source_files() -> list:

@@ -37,8 +37,7 @@
 // the cosine kernel per pos / neg row.  f32 (the parity mode): the same sequence
 // on the exact-f32 MFMA tile kernels, with explicit transposes for the weight
 // grads.
-#include "nr_common.h"
-#include "nr_rows.h"
+#include "nr_train.h"
 
 namespace nr {
 namespace ft {
@@ -117,8 +116,7 @@ __device__ __forceinline__ void w1_fold_body(int bx, int by, int nbx, const TA* 
   red[0][grp][cl] = sg;
   red[1][grp][cl] = sb;
   if (sqp) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    sq = wave_sum(sq);
     if (cl == 0) rsq[grp] = sq;
   }
   __syncthreads();
@@ -160,8 +158,7 @@ __global__ __launch_bounds__(256) void ln_reduce_kernel(int nchunk, const float*
     db[c] = vb;
     if (sqp) {
       float q = fmaf(vg, vg, vb * vb);
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) q += __shfl_xor(q, o, 64);
+      q = wave_sum(q);
       if (cl == 0) sqp[blockIdx.x] = q;
     }
   }
@@ -173,11 +170,8 @@ __global__ __launch_bounds__(256) void sq_total_kernel(int64_t n, const float* _
   __shared__ float red[4];
   float s = 0.f;
   for (int64_t i = threadIdx.x; i < n; i += 256) s += part[i];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
+  const float t = block_sum4(s, red);
+  if (threadIdx.x == 0) *out = t;
 }
 
 // F.cosine_similarity(u, E[pos / neg]) with the per-vector 1e-8 clamp and
@@ -193,12 +187,11 @@ __global__ __launch_bounds__(256) void cos_pairs_kernel(int64_t B, const float* 
                                                         const int32_t* __restrict__ neg, float margin,
                                                         float* __restrict__ lrow, float* __restrict__ du,
                                                         float* __restrict__ gpair) {
-  constexpr float EPS = 1e-8f;
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   float u[4][4], ep[4][4], en[4][4];
-  float uu = 0.f, pp = 0.f, nn = 0.f, up = 0.f, un = 0.f;
+  CosDots dots;
   // E[n] = xhat[n] gamma + beta (the token LN's output), as slots_kernel forms S;
   // the pairs' xhat rows kept for pair_ln_kernel (xpair [2B][D]: pos rows, then neg)
   tok_xhat<TT>(tok + (int64_t)pos[b] * D, lane, ep);
@@ -218,38 +211,20 @@ __global__ __launch_bounds__(256) void cos_pairs_kernel(int64_t B, const float* 
       en[j][t] = fmaf(en[j][t], gg[t], bb[t]);
     }
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uu = fmaf(u[j][t], u[j][t], uu);
-      pp = fmaf(ep[j][t], ep[j][t], pp);
-      nn = fmaf(en[j][t], en[j][t], nn);
-      up = fmaf(u[j][t], ep[j][t], up);
-      un = fmaf(u[j][t], en[j][t], un);
-    }
+    for (int t = 0; t < 4; ++t) dots.add(u[j][t], ep[j][t], en[j][t]);
   }
-  auto wsum = [](float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  };
-  uu = wsum(uu); pp = wsum(pp); nn = wsum(nn); up = wsum(up); un = wsum(un);
-  const float nu = sqrtf(uu), np_ = sqrtf(pp), nq = sqrtf(nn);
-  const float iu = 1.0f / fmaxf(nu, EPS), ip = 1.0f / fmaxf(np_, EPS), iq = 1.0f / fmaxf(nq, EPS);
-  const float sp = up * iu * ip, sn = un * iu * iq;
-  const float v = margin - (sp - sn);
-  const float act = v >= 0.f ? 1.0f : 0.0f;  // clamp_min backward passes where input >= min
-  const float gsp = -act / (float)B, gsn = act / (float)B;
-  if (lane == 0) lrow[b] = fmaxf(v, 0.f) / (float)B;
-  const float cu = nu > EPS ? 1.f : 0.f, cp = np_ > EPS ? 1.f : 0.f, cq = nq > EPS ? 1.f : 0.f;
+  dots.reduce(wave_sum);
+  const CosMargin cm(dots, margin, B);
+  if (lane == 0) lrow[b] = cm.loss_term();
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int e = j * 256 + lane * 4;
     float g[4], gp[4], gn[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const float uh = u[j][t] * iu, ph = ep[j][t] * ip, qh = en[j][t] * iq;
-      g[t] = gsp * (ph - cu * sp * uh) * iu + gsn * (qh - cu * sn * uh) * iu;
-      gp[t] = gsp * (uh - cp * sp * ph) * ip;
-      gn[t] = gsn * (uh - cq * sn * qh) * iq;
+      g[t] = cm.du(u[j][t], ep[j][t], en[j][t]);
+      gp[t] = cm.dpos(u[j][t], ep[j][t]);
+      gn[t] = cm.dneg(u[j][t], en[j][t]);
     }
     st4<float>(du + b * D + e, g);
     st4<float>(gpair + b * D + e, gp);
@@ -287,8 +262,7 @@ __global__ __launch_bounds__(256) void pair_ln_kernel(int64_t B, const float* __
     if (blockIdx.x == 0 && blockIdx.y == 0) {
       float l = 0.f;
       for (int64_t r = threadIdx.x; r < B; r += 64) l += lrow[r];
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) l += __shfl_xor(l, o, 64);
+      l = wave_sum(l);
       if (threadIdx.x == 0) *loss = l;
     }
   }
@@ -375,8 +349,7 @@ __device__ __forceinline__ void rowsum_body(const RSum& r, int bid, float* __res
     r.out[i][c0 + threadIdx.x] = s;
     if (sqp) {
       float q = s * s;
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) q += __shfl_xor(q, o, 64);
+      q = wave_sum(q);
       if (threadIdx.x == 0) sqp[bid] = q;
     }
   }
@@ -462,50 +435,47 @@ static Layout layout(int dtype, int64_t B, int64_t U, int64_t Hs, int ncu) {
   L.csr3 = (L.Hp + 127) / 128;
   L.csr = L.mm < L.Hp ? L.mm / 128 + (L.Hp - L.mm + 31) / 32 : L.csr3;
   const int64_t Hp = L.Hp, es = L.es, Bp = pad64(B);
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) { const int64_t r = o; o += align256(bytes); return r; };
-  L.xpair = take(2 * B * D * 4);
-  L.S = take(Hp * D * es); L.XH = take(Hp * D * es); L.X1 = take(Hp * H * es); L.X2 = take(Hp * H * es); L.XP = take(Hp * 2 * D * es);
-  L.Y = take(Hp * H * es);
-  L.users = take(Bp * D * 4); L.z = take(Bp * D * 4); L.du = take(Bp * D * 4); L.gpair = take(2 * B * D * 4);
-  L.lrow = take(Bp * 4);
-  L.sqp = take(kSqParts * 4);
-  L.dXp = take(Hp * D * es); L.dL = take(Hp * D * es); L.dY = take(Hp * H * es); L.dX = take(Hp * D * es);
-  L.dZ2 = take(Hp * H * es); L.dZ1 = take(Hp * H * es); L.w1p = take((H / 64 + kPairChunks) * 2 * D * 4);
-  L.W2t = take(H * H * es); L.W3t = take(H * D * es); L.W4t = take(D * H * es);
-  L.W5t = take(H * D * es);
+  WsCursor w;
+  L.xpair = w.take(2 * B * D * 4);
+  L.S = w.take(Hp * D * es); L.XH = w.take(Hp * D * es); L.X1 = w.take(Hp * H * es); L.X2 = w.take(Hp * H * es); L.XP = w.take(Hp * 2 * D * es);
+  L.Y = w.take(Hp * H * es);
+  L.users = w.take(Bp * D * 4); L.z = w.take(Bp * D * 4); L.du = w.take(Bp * D * 4); L.gpair = w.take(2 * B * D * 4);
+  L.lrow = w.take(Bp * 4);
+  L.sqp = w.take(kSqParts * 4);
+  L.dXp = w.take(Hp * D * es); L.dL = w.take(Hp * D * es); L.dY = w.take(Hp * H * es); L.dX = w.take(Hp * D * es);
+  L.dZ2 = w.take(Hp * H * es); L.dZ1 = w.take(Hp * H * es); L.w1p = w.take((H / 64 + kPairChunks) * 2 * D * 4);
+  L.W2t = w.take(H * H * es); L.W3t = w.take(H * D * es); L.W4t = w.take(D * H * es);
+  L.W5t = w.take(H * D * es);
   if (dtype == NR_BF16) {
-    L.skP = take((int64_t)kSplit * (Hp - L.mm) * H * 4);
-    L.cs4 = take(L.csr * H * 4); L.cs3 = take(L.csr3 * D * 4); L.cs2 = take(L.csr * H * 4); L.cs1 = take(L.csr * H * 4);
+    L.skP = w.take((int64_t)kSplit * (Hp - L.mm) * H * 4);
+    L.cs4 = w.take(L.csr * H * 4); L.cs3 = w.take(L.csr3 * D * 4); L.cs2 = w.take(L.csr * H * 4); L.cs1 = w.take(L.csr * H * 4);
   } else {
     // dL^T, Y^T, dY^T, X^T, dX^T, X2^T, dZ2^T, X1^T, dZ1^T, XH^T
-    const int64_t w[10] = {D, H, H, D, D, H, H, H, H, D};
-    for (int i = 0; i < 10; ++i) L.T[i] = take(w[i] * Hp * es);
+    const int64_t cols[10] = {D, H, H, D, D, H, H, H, H, D};
+    for (int i = 0; i < 10; ++i) L.T[i] = w.take(cols[i] * Hp * es);
   }
-  L.total = o;
+  L.total = w.o;
   return L;
 }
 
-static int ncu_of(hipStream_t st) {
-  int dev = 0, n = 256;
-  if (hipStreamGetDevice(st, &dev) != hipSuccess ||
-      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    n = 256;
+// CU count of device dev (256 when it cannot be read; have_dev = dev was resolved), down to a multiple of 8
+static int ncu_of_device(bool have_dev, int dev) {
+  int n = 256;
+  if (!have_dev || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
   return n >= 8 ? n / 8 * 8 : 8;
 }
+static int ncu_of(hipStream_t st) {
+  int dev = 0;
+  const bool ok = hipStreamGetDevice(st, &dev) == hipSuccess;
+  return ncu_of_device(ok, dev);
+}
+static int ncu_current() {
+  int dev = 0;
+  const bool ok = hipGetDevice(&dev) == hipSuccess;
+  return ncu_of_device(ok, dev);
+}
 
-#define NR_FT(x)                  \
-  do {                            \
-    const int rc_ = (x);          \
-    if (rc_ != NR_OK) return rc_; \
-  } while (0)
-#define NR_FT_EV(x, what)                                         \
-  do {                                                            \
-    if ((x) != hipSuccess) {                                      \
-      set_error("nr_final_train_step: %s failed", what);          \
-      return NR_ERR_HIP;                                          \
-    }                                                             \
-  } while (0)
+constexpr const char* kFn = "nr_final_train_step";
 
 template <typename TA>
 int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
@@ -531,7 +501,7 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
   const float scale = 1.0f / (1.0f - a.p);
   const uint32_t thr = dropout_threshold(a.p);
   TrainSide side;
-  NR_FT(train_side_streams(st, "nr_final_train_step", side));
+  NR_TRY(train_side_streams(st, "nr_final_train_step", side));
 
   // ---- the weight transposes the data-grad GEMMs need, on the side stream beside
   // an N = 1024 forward GEMM (X: 132 tiles, half of the CUs idle) rather than
@@ -541,9 +511,9 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
     const TA* w[4] = {W5, W4, W3, W2};
     TA* t[4] = {W5t, W4t, W3t, W2t};
     const int64_t r[4] = {D, H, D, H}, c[4] = {H, D, H, H};  // W5 [D][H], W4 [H][D], W3 [D][H], W2 [H][H]
-    NR_FT_EV(hipEventRecord(fork, st), "fork record");
-    NR_FT_EV(hipStreamWaitEvent(side.s, fork, 0), "fork wait");
-    for (int i = i0; i < i1; ++i) NR_FT(nr_transpose(dt, dt, r[i], c[i], w[i], c[i], t[i], r[i], side.s));
+    NR_TRY_HIP(hipEventRecord(fork, st), kFn, "fork record");
+    NR_TRY_HIP(hipStreamWaitEvent(side.s, fork, 0), kFn, "fork wait");
+    for (int i = i0; i < i1; ++i) NR_TRY(nr_transpose(dt, dt, r[i], c[i], w[i], c[i], t[i], r[i], side.s));
     return NR_OK;
   };
 
@@ -555,20 +525,15 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
     const int64_t zn[4] = {H, H, D, H};
     zl.n = 4;
     for (int i = 0; i < zl.n; ++i) { zl.p[i] = zp[i]; zl.len[i] = zn[i]; }
-    NR_FT(zero_ranges(zl, 64, st));
+    NR_TRY(zero_ranges(zl, 64, st));
   }
   // ---- forward
   // the slots' S and XH: the token LN of each slot's news (one kernel, no [U][D] table)
   {
     const int64_t g = (Hp + 3) / 4;
     const dim3 grid((unsigned)(g < 4096 ? g : 4096));
-#define NR_FT_TOK(TT) \
-    hipLaunchKernelGGL((slots_kernel<TA, TT>), grid, dim3(256), 0, st, Hp, Hs, (const TT*)a.tok_last, a.hist_idx, \
-                       a.tok_g, a.tok_b, S, XH)
-    if (a.tok_dtype == NR_F32) NR_FT_TOK(float);
-    else if (a.tok_dtype == NR_BF16) NR_FT_TOK(__bf16);
-    else NR_FT_TOK(_Float16);
-#undef NR_FT_TOK
+    NR_TOK_DT(a.tok_dtype, hipLaunchKernelGGL((slots_kernel<TA, TT>), grid, dim3(256), 0, st, Hp, Hs,
+                                              (const TT*)a.tok_last, a.hist_idx, a.tok_g, a.tok_b, S, XH));
     NR_CHECK_LAUNCH("nr_final_train_step (slots)");
   }
   // relu(dropout) GEMM over Hp rows: main rows on the persistent kernel, the tail as K-slices + fixup
@@ -576,63 +541,59 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
                        int64_t ldc) -> int {
     EpiArgs ea{seed, thr, scale};
     const int64_t mm = split_tail(K) ? L.mm : Hp;
-    NR_FT(gemm_dispatch_ex(dt, dt, NR_EPI_RELU_DROPOUT, mm, H, K, A, lda, W, K, bias, nullptr, 0, C, ldc, ea, st));
+    NR_TRY(gemm_dispatch_ex(dt, dt, NR_EPI_RELU_DROPOUT, mm, H, K, A, lda, W, K, bias, nullptr, 0, C, ldc, ea, st));
     if (mm == Hp) return NR_OK;
     float* Pk = (float*)P_(L.skP);
     const int ns = kSplit;
     const int64_t kk = K / ns, rows = Hp - mm;
     GemmProblem p = {rows, H, kk, A + mm * lda, lda, kk, W, K, kk, Pk, H, rows * H, ns, 1.0f};
-    NR_FT(gemm_group_dispatch(dt, NR_F32, &p, 1, st));
+    NR_TRY(gemm_group_dispatch(dt, NR_F32, &p, 1, st));
     return nr_splitk_fixup(dt, NR_EPI_RELU_DROPOUT, rows, H, ns, Pk, bias, nullptr, 0, C + mm * ldc, ldc, mm,
                            seed, a.p, scale, st);
   };
-  NR_FT(relu_gemm(S, D, W1, D, a.b1, a.seed[0], X1, H));
-  NR_FT(relu_gemm(X1, H, W2, H, a.b2, a.seed[1], X2, H));
+  NR_TRY(relu_gemm(S, D, W1, D, a.b1, a.seed[0], X1, H));
+  NR_TRY(relu_gemm(X1, H, W2, H, a.b2, a.seed[1], X2, H));
   // all four beside X under one fork; a second fork for the last ones beside P measured
   // the same (interleaved A/B, profiles/round5/train/ab_r7u)
-  NR_FT(transposes(0, 4, side.fork));
-  NR_FT_EV(hipEventRecord(side.wt, side.s), "transpose record");
-  NR_FT(gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, D, H, X2, H, W3, H, a.b3, nullptr, 0, X, 2 * D, st));
-  NR_FT(relu_gemm(X, 2 * D, W4, D, a.b4, a.seed[2], Y, H));
-  NR_FT(gemm_dispatch(dt, dt, NR_EPI_EXP, Hp, D, H, Y, H, W5, H, nullptr, nullptr, 0, Pexp, 2 * D, st));
-  NR_FT(nr_final_pool_fwd(dt, B, a.hist_off, XP, 2 * D, users, z, st));
+  NR_TRY(transposes(0, 4, side.fork));
+  NR_TRY_HIP(hipEventRecord(side.wt, side.s), kFn, "transpose record");
+  NR_TRY(gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, D, H, X2, H, W3, H, a.b3, nullptr, 0, X, 2 * D, st));
+  NR_TRY(relu_gemm(X, 2 * D, W4, D, a.b4, a.seed[2], Y, H));
+  NR_TRY(gemm_dispatch(dt, dt, NR_EPI_EXP, Hp, D, H, Y, H, W5, H, nullptr, nullptr, 0, Pexp, 2 * D, st));
+  NR_TRY(nr_final_pool_fwd(dt, B, a.hist_off, XP, 2 * D, users, z, st));
   // ---- loss and its gradient into the pooled users and E[pos] / E[neg]
   {
     const dim3 grid((unsigned)((B + 3) / 4));
-#define NR_FT_TOK(TT) \
-    hipLaunchKernelGGL((cos_pairs_kernel<TT>), grid, dim3(256), 0, st, B, users, (const TT*)a.tok_last, xpair, \
-                       a.tok_g, a.tok_b, a.pos, a.neg, a.margin, lrow, du, gpair)
-    if (a.tok_dtype == NR_F32) NR_FT_TOK(float);
-    else if (a.tok_dtype == NR_BF16) NR_FT_TOK(__bf16);
-    else NR_FT_TOK(_Float16);
-#undef NR_FT_TOK
+    NR_TOK_DT(a.tok_dtype, hipLaunchKernelGGL((cos_pairs_kernel<TT>), grid, dim3(256), 0, st, B, users,
+                                              (const TT*)a.tok_last, xpair, a.tok_g, a.tok_b, a.pos, a.neg, a.margin,
+                                              lrow, du, gpair));
   }
   NR_CHECK_LAUNCH("nr_final_train_step (cosine)");
   // the pairs' token LN grad partials (after the W1 fold's chunks) and the loss
   hipLaunchKernelGGL(pair_ln_kernel, dim3((unsigned)(D / 64), kPairChunks), dim3(256), 0, st, B, gpair, xpair, lrow,
                      (float*)P_(L.w1p) + (H / 64) * 2 * D, a.loss);
   NR_CHECK_LAUNCH("nr_final_train_step (pair LN grads)");
-  NR_FT(nr_final_pool_bwd(dt, B, a.hist_off, Hp, XP, 2 * D, users, z, du, dXp, D, dL, D, st));
+  NR_TRY(nr_final_pool_bwd(dt, B, a.hist_off, Hp, XP, 2 * D, users, z, du, dXp, D, dL, D, st));
   // ---- data-grad chain (weights transposed on the side stream)
-  NR_FT_EV(hipStreamWaitEvent(st, side.wt, 0), "transpose wait");
+  NR_TRY_HIP(hipStreamWaitEvent(st, side.wt, 0), kFn, "transpose wait");
   float *cs4 = (float*)P_(L.cs4), *cs3 = (float*)P_(L.cs3), *cs2 = (float*)P_(L.cs2), *cs1 = (float*)P_(L.cs1);
   // drop'(A W^T) against the forward output Yf; bf16: column sums into cs
   auto drelu_gemm = [&](const TA* A, int64_t K, const TA* Wt, const TA* Yf, TA* C, float* cs, float* gbias) -> int {
     if constexpr (!BF) {
-      NR_FT(gemm_dispatch_ex(dt, dt, NR_EPI_DRELU, Hp, H, K, A, K, Wt, K, nullptr, Yf, H, C, H,
+      NR_TRY(gemm_dispatch_ex(dt, dt, NR_EPI_DRELU, Hp, H, K, A, K, Wt, K, nullptr, Yf, H, C, H,
                              EpiArgs{0, 0, scale}, st));
       return nr_col_sum(dt, Hp, H, C, H, gbias, st);
     } else {
       EpiArgs ea{0, 0, scale};
       ea.colsum = cs;
       const int64_t mm = split_tail(K) ? L.mm : Hp;
-      NR_FT(gemm_dispatch_ex(dt, dt, NR_EPI_DRELU, mm, H, K, A, K, Wt, K, nullptr, Yf, H, C, H, ea, st));
+      NR_TRY(gemm_dispatch_ex(dt, dt, NR_EPI_DRELU, mm, H, K, A, K, Wt, K, nullptr, Yf, H, C, H, ea, st));
       if (mm == Hp) return NR_OK;
       float* Pk = (float*)P_(L.skP);
       const int ns = kSplit;
       const int64_t kk = K / ns, rows = Hp - mm;
       GemmProblem p = {rows, H, kk, A + mm * K, K, kk, Wt, K, kk, Pk, H, rows * H, ns, 1.0f};
-      NR_FT(gemm_group_dispatch(dt, NR_F32, &p, 1, st));
+      NR_TRY(gemm_group_dispatch(dt, NR_F32, &p, 1, st));
       // the fixup and the tail rows' column sums (of the stored bf16 values) in one launch
       hipLaunchKernelGGL((fixup_drelu_cs_kernel<TA>), dim3((unsigned)(H / 64), (unsigned)((rows + 31) / 32)),
                          dim3(256), 0, st, mm / 128, rows, H, ns, Pk, Yf + mm * H, H, C + mm * H, H, scale, cs);
@@ -640,15 +601,15 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
       return NR_OK;
     }
   };
-  NR_FT(drelu_gemm(dL, D, W5t, Y, dY, cs4, a.g_b4));  // dY = drop'(dL W5): the grad of linear4's output
+  NR_TRY(drelu_gemm(dL, D, W5t, Y, dY, cs4, a.g_b4));  // dY = drop'(dL W5): the grad of linear4's output
   {
     EpiArgs ea{0, 0, 1.f};
     if constexpr (BF) ea.colsum = cs3;
-    NR_FT(gemm_dispatch_ex(dt, dt, NR_EPI_RESADD, Hp, D, H, dY, H, W4t, H, nullptr, dXp, D, dX, D, ea, st));
-    if constexpr (!BF) NR_FT(nr_col_sum(dt, Hp, D, dX, D, a.g_b3, st));
+    NR_TRY(gemm_dispatch_ex(dt, dt, NR_EPI_RESADD, Hp, D, H, dY, H, W4t, H, nullptr, dXp, D, dX, D, ea, st));
+    if constexpr (!BF) NR_TRY(nr_col_sum(dt, Hp, D, dX, D, a.g_b3, st));
   }
-  NR_FT(drelu_gemm(dX, D, W3t, X2, dZ2, cs2, a.g_b2));
-  NR_FT(drelu_gemm(dZ2, H, W2t, X1, dZ1, cs1, a.g_b1));
+  NR_TRY(drelu_gemm(dX, D, W3t, X2, dZ2, cs2, a.g_b2));
+  NR_TRY(drelu_gemm(dZ2, H, W2t, X1, dZ1, cs1, a.g_b1));
   // (no dS = dZ1 W1: its only consumer, the token LN parameters, folds into dW1 below)
   // ---- weight grads: dW = dOut^T X
   RSum r{};  // bf16: the bias grads from the column-sum partials
@@ -664,7 +625,7 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
     const bool sqf[5] = {true, true, true, true, false};  // dW1 is M here: counted by the fold
     // one sum-of-squares slot per tile: the five shapes are fixed, so is the tile count
     static_assert(4 * (D / 256) * (H / 256) + (H / 256) * (H / 256) == kSqTn, "weight-grad tiles != kSqTn");
-    NR_FT(gemm_group_tn_dispatch(NR_F32, p, 5, st, sqp, sqf, nullptr, kSqTn));
+    NR_TRY(gemm_group_tn_dispatch(NR_F32, p, 5, st, sqp, sqf, nullptr, kSqTn));
     float* parts[4] = {cs1, cs2, cs3, cs4};
     float* outs[4] = {a.g_b1, a.g_b2, a.g_b3, a.g_b4};
     const int64_t cols[4] = {H, H, D, H};
@@ -679,7 +640,7 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
     for (int i = 0; i < 10; ++i) T[i] = (TA*)P_(L.T[i]);
     const TA* src[10] = {dL, Y, dY, X, dX, X2, dZ2, X1, dZ1, XH};
     const int64_t cols[10] = {D, H, H, D, D, H, H, H, H, D}, ld[10] = {D, H, H, 2 * D, D, H, H, H, H, D};
-    for (int i = 0; i < 10; ++i) NR_FT(nr_transpose(dt, dt, Hp, cols[i], src[i], ld[i], T[i], Hp, st));
+    for (int i = 0; i < 10; ++i) NR_TRY(nr_transpose(dt, dt, Hp, cols[i], src[i], ld[i], T[i], Hp, st));
     GemmProblem p[5] = {
         {D, H, Hp, T[0], Hp, 0, T[1], Hp, 0, a.g_W5, H, 0, 1, 1.0f},
         {H, D, Hp, T[2], Hp, 0, T[3], Hp, 0, a.g_W4, D, 0, 1, 1.0f},
@@ -687,7 +648,7 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
         {H, H, Hp, T[6], Hp, 0, T[7], Hp, 0, a.g_W2, H, 0, 1, 1.0f},
         {H, D, Hp, T[8], Hp, 0, T[9], Hp, 0, a.g_W1, D, 0, 1, 1.0f},
     };
-    NR_FT(gemm_group_dispatch(dt, NR_F32, p, 5, st));
+    NR_TRY(gemm_group_dispatch(dt, NR_F32, p, 5, st));
   }
   // ---- token LayerNorm parameter grads: the history gather's part folded with dW1
   // (w1_fold_kernel; dW1 = gamma o M + g_b1 (x) beta), summed with the pairs' part
@@ -713,16 +674,14 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
       hipLaunchKernelGGL(sq_total_kernel, dim3(1), dim3(256), 0, st, (int64_t)kSqParts, sqp, a.sumsq);
       NR_CHECK_LAUNCH("nr_final_train_step (grad norm)");
     } else if (a.sumsq) {  // f32 mode: over the gradient arrays
-      NR_FT(zero_ranges(ZList{1, {a.sumsq}, {1}}, 1, st));
+      NR_TRY(zero_ranges(ZList{1, {a.sumsq}, {1}}, 1, st));
       float* gs[11] = {a.g_tok_g, a.g_tok_b, a.g_W1, a.g_b1, a.g_W2, a.g_b2, a.g_W3, a.g_b3, a.g_W4, a.g_b4, a.g_W5};
       const int64_t gn[11] = {D, D, H * D, H, H * H, H, D * H, D, H * D, H, D * H};
-      for (int i = 0; i < 11; ++i) NR_FT(nr_sumsq(gn[i], gs[i], a.sumsq, st));
+      for (int i = 0; i < 11; ++i) NR_TRY(nr_sumsq(gn[i], gs[i], a.sumsq, st));
     }
   }
   return NR_OK;
 }
-#undef NR_FT
-#undef NR_FT_EV
 
 }  // namespace ft
 }  // namespace nr
@@ -731,23 +690,14 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
 // sized for the CURRENT device here, checked against the stream's device by the step)
 extern "C" int64_t nr_final_train_workspace_bytes(int dtype, int64_t B, int64_t U, int64_t Hs) {
   if ((dtype != NR_F32 && dtype != NR_BF16) || B < 0 || U < 0 || Hs < 0) return -1;
-  int dev = 0, n = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    n = 256;
-  return nr::ft::layout(dtype, B, U, Hs, n >= 8 ? n / 8 * 8 : 8).total;
+  return nr::ft::layout(dtype, B, U, Hs, nr::ft::ncu_current()).total;
 }
 
 extern "C" int nr_final_train_step(const nr_final_train_args* args, void* ws, int64_t ws_bytes, void* stream) {
   nr::clear_error();
   NR_CHECK_ARG(args, "nr_final_train_step: null args");
   const nr_final_train_args& a = *args;
-  NR_CHECK_ARG(a.dtype == NR_F32 || a.dtype == NR_BF16, "nr_final_train_step: dtype must be NR_F32 or NR_BF16");
-  NR_CHECK_ARG(a.tok_dtype == NR_F32 || a.tok_dtype == NR_BF16 || a.tok_dtype == NR_F16,
-               "nr_final_train_step: bad tok_dtype");
-  NR_CHECK_ARG(a.B >= 1 && a.U >= 1 && a.Hs >= 1, "nr_final_train_step: empty batch (B=%lld U=%lld Hs=%lld)",
-               (long long)a.B, (long long)a.U, (long long)a.Hs);
-  NR_CHECK_ARG(a.Hs <= (1ll << 31) - 1024 && a.U <= (1ll << 31) && a.B <= (1ll << 24),
-               "nr_final_train_step: batch too large");
+  NR_TRY(nr::check_step_args("nr_final_train_step", a.dtype, a.tok_dtype, a.B, a.U, a.Hs));
   NR_CHECK_ARG(a.p >= 0.f && a.p < 1.f, "nr_final_train_step: dropout p outside [0, 1)");
   // bf16: the persistent GEMM (the column-sum epilogues have no other kernel) addresses
   // its [Hp][4096] operands through 32-bit buffer offsets; refuse before any launch

@@ -30,47 +30,13 @@
 //   as two grouped launches of the 8 heads, and the LN parameter grads.
 // GEMMs: nr's MFMA kernels (gemm.hip: persistent bf16, grouped strided batches);
 // everything else here is HBM-bound row work (one wave per row, 16-B lanes).
-#include "nr_common.h"
-#include "nr_rows.h"
+#include "nr_train.h"
 
 namespace nr {
 namespace lt {
 
 constexpr int D = 1024, F = 4096, S = 512, NL = 64, HEADS = 8, DH = 512;
-
-// bf16 step only (the f32 step keeps erff / expf): for two values, h = erfc(|g| /
-// sqrt 2) / 2 and e = exp(-g^2 / 2) with one packed polynomial and v_exp_f32, no
-// branches -- the erfc form of gelu_erf2x2 (nr_common.h: s = g sqrt(log2(e) / 2),
-// erfc = 2^(P(min(|s|, 4 sqrt(log2 e))) - s^2), P a degree-8 minimax fit of
-// log2(erfcx), its -1 folded in so 2^(P - s^2) = erfc / 2; relative error <= 2.2e-6
-// on erfc).  The divergent two-range erff plus expf made GEGLU's backward
-// VALU-heavy (~65 instructions per element).
-__device__ __forceinline__ void erfc_half2(f32x2v g, f32x2v& h, f32x2v& e) {
-  constexpr float kS = 0.8493218002880191f, kSmax = 4.804489635145799f;
-  const f32x2v s = g * kS;
-  const f32x2v c = {fminf(fabsf(s.x), kSmax), fminf(fabsf(s.y), kSmax)};
-  f32x2v q = (f32x2v)-3.57632359e-07f;
-  q = fma2(q, c, (f32x2v)8.19052786e-07f);
-  q = fma2(q, c, (f32x2v)0.000115395807f);
-  q = fma2(q, c, (f32x2v)-0.00191940868f);
-  q = fma2(q, c, (f32x2v)0.0159611721f);
-  q = fma2(q, c, (f32x2v)-0.0876397938f);
-  q = fma2(q, c, (f32x2v)0.364198327f);
-  q = fma2(q, c, (f32x2v)-1.35544741f);
-  q = fma2(q, c, (f32x2v)(3.20236495e-06f - 1.0f));
-  const f32x2v ns2 = -s * s, w = q + ns2;
-  e = (f32x2v){__builtin_amdgcn_exp2f(ns2.x), __builtin_amdgcn_exp2f(ns2.y)};
-  h = (f32x2v){__builtin_amdgcn_exp2f(w.x), __builtin_amdgcn_exp2f(w.y)};
-}
-
-// sum of v over the 256 threads of the block (4 waves), returned to every thread
-__device__ __forceinline__ float block_sum(float v, float* scratch /* [4] */) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
-}
+constexpr const char* kFn = "nr_latent_train_step";
 
 // ------------------------------------------------------------------ small helpers
 // *out += sum over up to 8 f32 ranges of their squares (gradients a stream of the step
@@ -102,10 +68,8 @@ __global__ __launch_bounds__(256) void sq_list_kernel(SqList q, float* __restric
     }
     s = sumsq_range(x, n, t, gs, s);
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, (part[0] + part[1]) + (part[2] + part[3]));
+  s = block_sum4(s, part);
+  if (threadIdx.x == 0) atomicAdd(out, s);
 }
 
 static int sq_list(const SqList& q, float* out, hipStream_t st) {
@@ -359,7 +323,7 @@ __global__ __launch_bounds__(256) void head_kernel(int64_t B, int64_t Bp, int np
                                                    float* __restrict__ dmc32, const float* __restrict__ Xpn,
                                                    float* __restrict__ gtg, float* __restrict__ gtb,
                                                    float* __restrict__ gb2) {
-  constexpr float EPS = 1e-8f, NEPS = 1e-12f;
+  constexpr float NEPS = 1e-12f;
   __shared__ float red[4];
   const int64_t b = blockIdx.x;
   const int tid = threadIdx.x;
@@ -386,29 +350,18 @@ __global__ __launch_bounds__(256) void head_kernel(int64_t B, int64_t Bp, int np
     en[j] = nr_[c];
     mm = fmaf(v, v, mm);
   }
-  const float nm = sqrtf(block_sum(mm, red));
+  const float nm = sqrtf(block_sum4(mm, red));
   const float den = fmaxf(nm, NEPS);
   float u[4];
-  float uu = 0.f, pp = 0.f, nn = 0.f, up = 0.f, un = 0.f;
+  CosDots dots;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     u[j] = m[j] / den;
-    uu = fmaf(u[j], u[j], uu);
-    pp = fmaf(ep[j], ep[j], pp);
-    nn = fmaf(en[j], en[j], nn);
-    up = fmaf(u[j], ep[j], up);
-    un = fmaf(u[j], en[j], un);
+    dots.add(u[j], ep[j], en[j]);
   }
-  uu = block_sum(uu, red); pp = block_sum(pp, red); nn = block_sum(nn, red);
-  up = block_sum(up, red); un = block_sum(un, red);
-  const float nu = sqrtf(uu), np_ = sqrtf(pp), nq = sqrtf(nn);
-  const float iu = 1.0f / fmaxf(nu, EPS), ip = 1.0f / fmaxf(np_, EPS), iq = 1.0f / fmaxf(nq, EPS);
-  const float sp = up * iu * ip, sn = un * iu * iq;
-  const float v = margin - (sp - sn);
-  const float act = v >= 0.f ? 1.0f : 0.0f;
-  const float gsp = -act / (float)B, gsn = act / (float)B;
-  if (tid == 0) atomicAdd(loss, fmaxf(v, 0.f) / (float)B);
-  const float cu = nu > EPS ? 1.f : 0.f, cp = np_ > EPS ? 1.f : 0.f, cq = nq > EPS ? 1.f : 0.f;
+  dots.reduce([&](float x) { return block_sum4(x, red); });
+  const CosMargin cm(dots, margin, B);
+  if (tid == 0) atomicAdd(loss, cm.loss_term());
   const float* xp = Xpn + b * D;         // xhat of E[pos[b]]'s token LN
   const float* xn = Xpn + (B + b) * D;   // and of E[neg[b]]'s
   float g[4];
@@ -416,14 +369,13 @@ __global__ __launch_bounds__(256) void head_kernel(int64_t B, int64_t Bp, int np
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int c = j * 256 + tid;
-    const float uh = u[j] * iu, ph = ep[j] * ip, qh = en[j] * iq;
-    g[j] = gsp * (ph - cu * sp * uh) * iu + gsn * (qh - cu * sn * uh) * iu;
+    g[j] = cm.du(u[j], ep[j], en[j]);
     ug = fmaf(u[j], g[j], ug);
-    const float gp = gsp * (uh - cp * sp * ph) * ip, gn = gsn * (uh - cq * sn * qh) * iq;
+    const float gp = cm.dpos(u[j], ep[j]), gn = cm.dneg(u[j], en[j]);
     atomicAdd(gtg + c, fmaf(gp, xp[c], gn * xn[c]));
     atomicAdd(gtb + c, gp + gn);
   }
-  ug = block_sum(ug, red);
+  ug = block_sum4(ug, red);
   const float icnt = 1.0f / (float)(off[b + 1] - off[b]);
   const bool live = nm > NEPS;
 #pragma unroll
@@ -488,10 +440,7 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(int64_t n_rows, const TA
         float cdf[2], pdf[2];
         if constexpr (sizeof(TA) == 4) {
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            cdf[j] = 0.5f * (1.0f + erff(g[i][k + j] * 0.70710678118654752440f));
-            pdf[j] = 0.39894228040143267794f * expf(-0.5f * g[i][k + j] * g[i][k + j]);  // exact f32, as the forward
-          }
+          for (int j = 0; j < 2; ++j) gelu_cdf_pdf(g[i][k + j], cdf[j], pdf[j]);  // exact f32, as the forward
         } else {
           f32x2v h, e;
           erfc_half2((f32x2v){g[i][k], g[i][k + 1]}, h, e);
@@ -581,7 +530,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int64_t n, int64_t nvalid, 
     }
     // x, dy and the residual row issued together (one memory round trip per row;
     // dy and res behind the statistics' reductions made the kernel latency-bound)
-    float v[4][4], g[4][4], dyv[4][4], rv[4][4], xt[NT][4];
+    float v[4][4], dyv[4][4], rv[4][4], xt[NT][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int c = j * 256 + lane * 4;
@@ -602,29 +551,15 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int64_t n, int64_t nvalid, 
     }
     float mean, rstd;
     row_stats4<4>(v, (float)D, eps, mean, rstd);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float* d4 = dyv[j];
+    ln_bwd_row<4>(v, mean, rstd, dyv, gm, (float)D, [&](int j, float (&o)[4]) {  // (v[j]: xhat here)
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        v[j][t] = (v[j][t] - mean) * rstd;  // xhat
-        ag[j][t] = fmaf(d4[t], v[j][t], ag[j][t]);
-        ab[j][t] += d4[t];
-        g[j][t] = d4[t] * gm[j][t];  // dxhat
-        s1 += g[j][t];
-        s2 = fmaf(g[j][t], v[j][t], s2);
+        ag[j][t] = fmaf(dyv[j][t], v[j][t], ag[j][t]);
+        ab[j][t] += dyv[j][t];
+        o[t] += rv[j][t];
       }
-    }
-    const float m1 = wave_sum(s1) / (float)D, m2 = wave_sum(s2) / (float)D;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = j * 256 + lane * 4;
-      float o[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) o[t] = rstd * (g[j][t] - m1 - v[j][t] * m2) + rv[j][t];
       if constexpr (MODE == 0) {
-        st4<TA>(out + row * D + c, o);
+        st4<TA>(out + row * D + j * 256 + lane * 4, o);
       } else {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -632,49 +567,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int64_t n, int64_t nvalid, 
           tba[j][t] += o[t];
         }
       }
-    }
+    });
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      sg[wave][j * 256 + lane * 4 + t] = ag[j][t];
-      sb[wave][j * 256 + lane * 4 + t] = ab[j][t];
-    }
-  __syncthreads();
-  for (int c = threadIdx.x; c < D; c += 256) {
-    atomicAdd(dgamma + c, (sg[0][c] + sg[1][c]) + (sg[2][c] + sg[3][c]));
-    atomicAdd(dbeta + c, (sb[0][c] + sb[1][c]) + (sb[2][c] + sb[3][c]));
-  }
+  fold_cols_atomic<4>(sg, sb, ag, ab, dgamma, dbeta);
   if constexpr (MODE == 1) {  // the token LN's grads, the same way
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        sg[wave][j * 256 + lane * 4 + t] = tga[j][t];
-        sb[wave][j * 256 + lane * 4 + t] = tba[j][t];
-      }
-    __syncthreads();
-    for (int c = threadIdx.x; c < D; c += 256) {
-      atomicAdd(tdg + c, (sg[0][c] + sg[1][c]) + (sg[2][c] + sg[3][c]));
-      atomicAdd(tdb + c, (sb[0][c] + sb[1][c]) + (sb[2][c] + sb[3][c]));
-    }
-  }
-}
-
-// dS = P (dP - sum_group P dP) over the 8 groups of 64 columns (one head's
-// latents, SDPA's softmax backward).  One wave per (row, group).
-template <typename TA>
-__global__ __launch_bounds__(256) void softmax64_bwd_kernel(int64_t rows, const TA* __restrict__ P,
-                                                            const TA* __restrict__ dP, TA* __restrict__ dS) {
-  const int lane = threadIdx.x & 63;
-  const int64_t ng = rows * HEADS;
-  for (int64_t gi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); gi < ng; gi += (int64_t)gridDim.x * 4) {
-    const int64_t i = gi * 64 + lane;  // rows x 512 = groups x 64
-    const float p = (float)P[i], d = (float)dP[i];
-    const float dot = wave_sum(p * d);
-    dS[i] = (TA)(p * (d - dot));
+    fold_cols_atomic<4>(sg, sb, tga, tba, tdg, tdb);
   }
 }
 
@@ -688,7 +586,7 @@ __global__ __launch_bounds__(256) void lnc_bwd_kernel(const float* __restrict__ 
   __shared__ float sg[4][D], sb[4][D];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = (int)blockIdx.x * 4 + wave;  // 16 blocks x 4 waves = the 64 latents
-  float v[4][4], g[4][4], dy[4][4];
+  float v[4][4], gm[4][4], dy[4][4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int c = j * 256 + lane * 4;
@@ -704,34 +602,15 @@ __global__ __launch_bounds__(256) void lnc_bwd_kernel(const float* __restrict__ 
   }
   float mean, rstd;
   row_stats4<4>(v, (float)D, eps, mean, rstd);
-  float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float gm[4];
-    ld4<float>(gamma + j * 256 + lane * 4, gm);
+  for (int j = 0; j < 4; ++j) ld4<float>(gamma + j * 256 + lane * 4, gm[j]);
+  ln_bwd_row<4>(v, mean, rstd, dy, gm, (float)D,
+                [&](int j, float (&o)[4]) { st4<float>(dx + row * D + j * 256 + lane * 4, o); });
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      v[j][t] = (v[j][t] - mean) * rstd;
-      sg[wave][j * 256 + lane * 4 + t] = dy[j][t] * v[j][t];
-      sb[wave][j * 256 + lane * 4 + t] = dy[j][t];
-      g[j][t] = dy[j][t] * gm[t];
-      s1 += g[j][t];
-      s2 = fmaf(g[j][t], v[j][t], s2);
-    }
-  }
-  const float m1 = wave_sum(s1) / (float)D, m2 = wave_sum(s2) / (float)D;
+  for (int j = 0; j < 4; ++j)
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float o[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) o[t] = rstd * (g[j][t] - m1 - v[j][t] * m2);
-    st4<float>(dx + row * D + j * 256 + lane * 4, o);
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < D; c += 256) {
-    atomicAdd(dgamma + c, (sg[0][c] + sg[1][c]) + (sg[2][c] + sg[3][c]));
-    atomicAdd(dbeta + c, (sb[0][c] + sb[1][c]) + (sb[2][c] + sb[3][c]));
-  }
+    for (int t = 0; t < 4; ++t) v[j][t] *= dy[j][t];  // xhat -> the row's dgamma terms
+  fold_cols_atomic<4>(sg, sb, v, dy, dgamma, dbeta);
 }
 
 // ------------------------------------------------------------------ batched transposes
@@ -941,34 +820,33 @@ static Layout layout(int dtype, int64_t B, int64_t U, int64_t Hs) {
   L.Bp = pad64(B);
   L.es = dtype == NR_F32 ? 4 : 2;
   const int64_t Hp = L.Hp, Hpp = L.Hpp, Bp = L.Bp, es = L.es;
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) { const int64_t r = o; o += align256(bytes); return r; };
-  L.E = take(2 * Bp * D * 4);  // Epn: E[pos] rows then E[neg] rows (no [U][D] E table)
-  L.Xpn = take(2 * Bp * D * 4);  // the same rows' token-LN xhat
+  WsCursor w;
+  L.E = w.take(2 * Bp * D * 4);  // Epn: E[pos] rows then E[neg] rows (no [U][D] E table)
+  L.Xpn = w.take(2 * Bp * D * 4);  // the same rows' token-LN xhat
   // X, P, dH1, dS hold Hpp rows: the dA / dBt K-slices read them directly (bf16: TN
   // weight-grad GEMMs), rows [Hp, Hpp) zeroed by the step
-  L.Sx = take(Hp * D * es); L.X = take(Hpp * D * es); L.P = take(Hpp * S * es); L.H1 = take(Hp * D * es);
-  L.Y = take(Hp * D * es); L.G = take(Hp * 2 * F * es);
-  L.zbar = take(Bp * F * es); L.h1bar = take(Bp * D * 4); L.row_seg = take(Hp * 4);
-  L.hparts = take((int64_t)kHParts * Bp * D * 4); L.hsum = take(Bp * D * 4);
-  L.dmA = take(Bp * D * es); L.dmc = take(Bp * D * es); L.dmc32 = take(Bp * D * 4); L.dZ = take((int64_t)kZParts * Bp * F * 4);
-  L.dZs = take(Bp * F * 4);
-  L.gpart = take((Hp + kGRows - 1) / kGRows * 2 * F * 4);
-  L.dG = take(Hp * 2 * F * es); L.dY = take(Hp * D * es); L.dH1 = take(Hpp * D * es);
-  L.dP = take(Hp * S * es); L.dS = take(Hpp * S * es); L.dX = take(Hp * D * es);
-  L.dGT = take(2 * F * Hp * es); L.YT = take(D * Hp * es); L.dH1T = take(D * Hpp * es); L.PT = take(S * Hpp * es);
-  L.dST = take(S * Hpp * es); L.XT = take(D * Hpp * es); L.dmT = take(D * Bp * es); L.zbarT = take(F * Bp * es);
-  L.WqT = take(D * F * es); L.W1T = take(D * 2 * F * es); L.W2T = take(F * D * es); L.WoT = take(F * D * es);
-  L.WkvT = take(D * 2 * F * es);
-  L.latn = take(NL * D * es); L.latnT = take(D * NL * es); L.KVp = take((int64_t)kKVParts * NL * 2 * F * 4);
-  L.KV = take(NL * 2 * F * es); L.KVT = take(2 * F * NL * es);
-  L.A = take(S * D * es); L.AT = take(D * S * es); L.BtT = take(S * D * es); L.Bt = take(D * S * es);
-  L.gA = take((int64_t)kWParts * S * D * 4); L.gBt = take((int64_t)kWParts * D * S * 4);
-  L.gA16 = take(S * D * es); L.gAT16 = take(D * S * es); L.gBt16 = take(D * S * es); L.gBtT16 = take(S * D * es);
-  L.dKV = take(NL * 2 * F * 4); L.dKV16 = take(NL * 2 * F * es); L.dKVT16 = take(2 * F * NL * es);
-  L.dlat = take((int64_t)kLatParts * NL * D * 4);
-  L.sqp = take(kSqSlots * 4);
-  L.total = o;
+  L.Sx = w.take(Hp * D * es); L.X = w.take(Hpp * D * es); L.P = w.take(Hpp * S * es); L.H1 = w.take(Hp * D * es);
+  L.Y = w.take(Hp * D * es); L.G = w.take(Hp * 2 * F * es);
+  L.zbar = w.take(Bp * F * es); L.h1bar = w.take(Bp * D * 4); L.row_seg = w.take(Hp * 4);
+  L.hparts = w.take((int64_t)kHParts * Bp * D * 4); L.hsum = w.take(Bp * D * 4);
+  L.dmA = w.take(Bp * D * es); L.dmc = w.take(Bp * D * es); L.dmc32 = w.take(Bp * D * 4); L.dZ = w.take((int64_t)kZParts * Bp * F * 4);
+  L.dZs = w.take(Bp * F * 4);
+  L.gpart = w.take((Hp + kGRows - 1) / kGRows * 2 * F * 4);
+  L.dG = w.take(Hp * 2 * F * es); L.dY = w.take(Hp * D * es); L.dH1 = w.take(Hpp * D * es);
+  L.dP = w.take(Hp * S * es); L.dS = w.take(Hpp * S * es); L.dX = w.take(Hp * D * es);
+  L.dGT = w.take(2 * F * Hp * es); L.YT = w.take(D * Hp * es); L.dH1T = w.take(D * Hpp * es); L.PT = w.take(S * Hpp * es);
+  L.dST = w.take(S * Hpp * es); L.XT = w.take(D * Hpp * es); L.dmT = w.take(D * Bp * es); L.zbarT = w.take(F * Bp * es);
+  L.WqT = w.take(D * F * es); L.W1T = w.take(D * 2 * F * es); L.W2T = w.take(F * D * es); L.WoT = w.take(F * D * es);
+  L.WkvT = w.take(D * 2 * F * es);
+  L.latn = w.take(NL * D * es); L.latnT = w.take(D * NL * es); L.KVp = w.take((int64_t)kKVParts * NL * 2 * F * 4);
+  L.KV = w.take(NL * 2 * F * es); L.KVT = w.take(2 * F * NL * es);
+  L.A = w.take(S * D * es); L.AT = w.take(D * S * es); L.BtT = w.take(S * D * es); L.Bt = w.take(D * S * es);
+  L.gA = w.take((int64_t)kWParts * S * D * 4); L.gBt = w.take((int64_t)kWParts * D * S * 4);
+  L.gA16 = w.take(S * D * es); L.gAT16 = w.take(D * S * es); L.gBt16 = w.take(D * S * es); L.gBtT16 = w.take(S * D * es);
+  L.dKV = w.take(NL * 2 * F * 4); L.dKV16 = w.take(NL * 2 * F * es); L.dKVT16 = w.take(2 * F * NL * es);
+  L.dlat = w.take((int64_t)kLatParts * NL * D * 4);
+  L.sqp = w.take(kSqSlots * 4);
+  L.total = w.o;
   return L;
 }
 
@@ -1016,8 +894,7 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
            *W2 = (const TA*)a.W2;
   const float scale = 1.0f / sqrtf((float)DH);  // SDPA default scale (latent_attention.py:72)
   TrainSide side;
-  int rc;
-  if ((rc = train_side_streams(st, "nr_latent_train_step", side))) return rc;
+  NR_TRY(train_side_streams(st, kFn, side));
 #define NR_LT_CHECK(name) NR_CHECK_LAUNCH("nr_latent_train_step (" name ")")
 
   // ---- fork 0: the fold (weights only) runs on the side stream beside Wq^T, the
@@ -1025,20 +902,14 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
   // (interleaved A/B: Wq^T here 1.045-1.055 vs on the fold stream 1.053-1.061 ms/step,
   // profiles/round5/train/ab_r8c); the P GEMM joins them.  The side stream first waits for everything before the step on
   // this one (the previous step's AdamW rewrote the weights).
-  if (hipEventRecord(side.fork, st) != hipSuccess || hipStreamWaitEvent(side.s, side.fork, 0) != hipSuccess) {
-    set_error("nr_latent_train_step: fork 0 failed");
-    return NR_ERR_HIP;
-  }
+  NR_TRY(stream_fork(st, side.s, side.fork, kFn, "fork 0"));
   // Wq^T (the A fold's operand) first on this stream, event wt: the fold stream runs
   // LN_c and the KV GEMM meanwhile and waits for it just before the A / Bt GEMMs
   {
     TList t;
     t.add(Wq, D, WqT, F, F, D, true);  // [4096, 1024] -> [1024, 4096]
-    if ((rc = launch_tlist<TA, TA>(t, st))) return rc;
-    if (hipEventRecord(side.wt, st) != hipSuccess) {
-      set_error("nr_latent_train_step: Wq transpose record failed");
-      return NR_ERR_HIP;
-    }
+    NR_TRY(launch_tlist<TA, TA>(t, st));
+    NR_TRY_HIP(hipEventRecord(side.wt, st), kFn, "Wq transpose record");
   }
   // the data-grad GEMMs' W operands (first needed by the dZ GEMM), on this stream
   // before the gathers: beside LN_c and the KV GEMM rather than the A / Bt GEMMs, and
@@ -1050,7 +921,7 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
     t.add(W2, F, W2T, D, D, F, true);          // [1024, 4096] -> [4096, 1024]
     t.add(Wo, F, WoT, D, D, F, true);          // [1024, 4096] -> [4096, 1024]
     t.add(Wkv, D, WkvT, 2 * F, 2 * F, D, true);
-    if ((rc = launch_tlist<TA, TA>(t, st))) return rc;
+    NR_TRY(launch_tlist<TA, TA>(t, st));
   }
   // ---- accumulators: the step zeroes every gradient it accumulates (the GEMM-written
   // ones are overwritten whole) and the loss
@@ -1067,66 +938,53 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
     z.p[14] = (float*)(dS + Hp * S); z.len[14] = tail * S;
     z.n = 15;
     if (a.sumsq) { z.p[15] = a.sumsq; z.len[15] = 1; z.n = 16; }
-    if ((rc = zero_ranges(z, 1024, st))) return rc;
+    NR_TRY(zero_ranges(z, 1024, st));
   }
   // (one box, interleaved, ms/step: all of this serial on one stream 1.195-1.215, every
   // weight transpose before the fold on the side stream 1.20, this layout 1.185 --
   // profiles/round4/train/step_tuning/r4ab1)
   hipStream_t fs = side.s;
   // fold: latn = LN_c(latents); KV = latn Wkv^T (split-K); A_h = s K_h Wq_h; BtT_h = V_h Wo_h^T
-  if ((rc = layernorm_dispatch(NR_F32, dt, NL, D, a.latents, D, a.nc_g, a.nc_b, 1e-5f, latn, D, fs))) return rc;
+  NR_TRY(layernorm_dispatch(NR_F32, dt, NL, D, a.latents, D, a.nc_g, a.nc_b, 1e-5f, latn, D, fs));
   {
     const int64_t ks = D / kKVParts;
     GemmProblem p = {NL, 2 * F, ks, latn, D, ks, Wkv, D, ks, KVp, 2 * F, (int64_t)NL * 2 * F, kKVParts, 1.0f};
-    if ((rc = gemm_group_dispatch(dt, NR_F32, &p, 1, fs))) return rc;
+    NR_TRY(gemm_group_dispatch(dt, NR_F32, &p, 1, fs));
     SCList t;
-    if ((rc = t.add(KVp, 2 * F, kKVParts, (int64_t)NL * 2 * F, NL, 2 * F, KV, 2 * F, KVT, NL))) return rc;
-    if ((rc = launch_sumconv<TA>(t, fs))) return rc;
+    NR_TRY(t.add(KVp, 2 * F, kKVParts, (int64_t)NL * 2 * F, NL, 2 * F, KV, 2 * F, KVT, NL));
+    NR_TRY(launch_sumconv<TA>(t, fs));
   }
-  if (hipStreamWaitEvent(fs, side.wt, 0) != hipSuccess) {
-    set_error("nr_latent_train_step: Wq transpose wait failed");
-    return NR_ERR_HIP;
-  }
+  NR_TRY_HIP(hipStreamWaitEvent(fs, side.wt, 0), kFn, "Wq transpose wait");
   {
     GemmProblem p[2] = {
         {NL, D, DH, KV, 2 * F, DH, WqT, F, DH, Am, D, (int64_t)NL * D, HEADS, scale},
         {NL, D, DH, KV + F, 2 * F, DH, Wo, F, DH, BtT, D, (int64_t)NL * D, HEADS, 1.0f},
     };
-    if ((rc = gemm_group_dispatch(dt, dt, p, 2, fs))) return rc;
+    NR_TRY(gemm_group_dispatch(dt, dt, p, 2, fs));
   }
   {
     TList t;
     t.add(Am, D, AT, S, S, D, true);         // A [512, 1024] -> AT [1024, 512]
     t.add(BtT, D, Bt, S, S, D, true);        // BtT [512, 1024] -> Bt [1024, 512]
     t.add(latn, D, latnT, NL, NL, D, true);  // [64, 1024] -> [1024, 64]
-    if ((rc = launch_tlist<TA, TA>(t, fs))) return rc;
+    NR_TRY(launch_tlist<TA, TA>(t, fs));
   }
-  if (hipEventRecord(side.join, fs) != hipSuccess) {
-    set_error("nr_latent_train_step: join 0 record failed");
-    return NR_ERR_HIP;
-  }
-#define NR_LT_TOK(...)                                                       \
-  do {                                                                       \
-    if (a.tok_dtype == NR_F32) { typedef float TT; __VA_ARGS__; }            \
-    else if (a.tok_dtype == NR_BF16) { typedef __bf16 TT; __VA_ARGS__; }     \
-    else { typedef _Float16 TT; __VA_ARGS__; }                              \
-  } while (0)
+  NR_TRY_HIP(hipEventRecord(side.join, fs), kFn, "join 0 record");
   // ---- E[pos] / E[neg] rows for the head (the token LN of those news' last tokens) and their xhat
-  NR_LT_TOK(hipLaunchKernelGGL((pn_rows_kernel<TT>), dim3((unsigned)((2 * B + 3) / 4)), dim3(256), 0, st, B,
+  NR_TOK_DT(a.tok_dtype,
+            hipLaunchKernelGGL((pn_rows_kernel<TT>), dim3((unsigned)((2 * B + 3) / 4)), dim3(256), 0, st, B,
                                (const TT*)a.tok_last, a.pos, a.neg, a.tok_g, a.tok_b, Epn, Xpn));
   NR_LT_CHECK("pos / neg rows");
   // ---- per-slot forward
-  NR_LT_TOK(hipLaunchKernelGGL((gather_ln_kernel<TA, TT>), dim3(grid_rows(Hp)), dim3(256), 0, st, Hp, a.Hs,
+  NR_TOK_DT(a.tok_dtype,
+            hipLaunchKernelGGL((gather_ln_kernel<TA, TT>), dim3(grid_rows(Hp)), dim3(256), 0, st, Hp, a.Hs,
                                (const TT*)a.tok_last, a.tok_g, a.tok_b, a.hist_idx, a.nq_g, a.nq_b, 1e-5f, Sx, X));
   NR_LT_CHECK("gather_ln");
-  if (hipStreamWaitEvent(st, side.join, 0) != hipSuccess) {
-    set_error("nr_latent_train_step: join 0 failed");
-    return NR_ERR_HIP;
-  }
-  if ((rc = gemm_dispatch(dt, dt, NR_EPI_SOFTMAX64, Hp, S, D, X, D, Am, D, nullptr, nullptr, 0, Pm, S, st))) return rc;
-  if ((rc = gemm_dispatch(dt, dt, NR_EPI_RESADD, Hp, D, S, Pm, S, Bt, S, nullptr, Sx, D, H1, D, st))) return rc;
-  if ((rc = layernorm_dispatch(dt, dt, Hp, D, H1, D, a.nf_g, a.nf_b, 1e-5f, Y, D, st))) return rc;
-  if ((rc = gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, 2 * F, D, Y, D, W1, D, a.b1, nullptr, 0, G, 2 * F, st))) return rc;
+  NR_TRY_HIP(hipStreamWaitEvent(st, side.join, 0), kFn, "join 0");
+  NR_TRY(gemm_dispatch(dt, dt, NR_EPI_SOFTMAX64, Hp, S, D, X, D, Am, D, nullptr, nullptr, 0, Pm, S, st));
+  NR_TRY(gemm_dispatch(dt, dt, NR_EPI_RESADD, Hp, D, S, Pm, S, Bt, S, nullptr, Sx, D, H1, D, st));
+  NR_TRY(layernorm_dispatch(dt, dt, Hp, D, H1, D, a.nf_g, a.nf_b, 1e-5f, Y, D, st));
+  NR_TRY(gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, 2 * F, D, Y, D, W1, D, a.b1, nullptr, 0, G, 2 * F, st));
   // ---- per batch row: means, m = zbar W2^T (split-K) + b2 + h1bar, loss
   hipLaunchKernelGGL((segmean_kernel<TA>), dim3((F + D) / 256, (unsigned)(Bp + 1)), dim3(512), 0, st, B, Bp, a.hist_off, Hp, G,
                      H1, zbar, h1bar, row_seg);
@@ -1134,9 +992,9 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
   {
     const int64_t ks = F / kHParts;
     GemmProblem p = {Bp, D, ks, zbar, F, ks, W2, F, ks, hparts, D, Bp * D, kHParts, 1.0f};
-    if ((rc = gemm_group_dispatch(dt, NR_F32, &p, 1, st))) return rc;
+    NR_TRY(gemm_group_dispatch(dt, NR_F32, &p, 1, st));
     // the split-K partials summed in parallel (the head reads one row per batch row)
-    if ((rc = sum_parts(hparts, kHParts, Bp * D, hsum, Bp * D, st))) return rc;
+    NR_TRY(sum_parts(hparts, kHParts, Bp * D, hsum, Bp * D, st));
   }
   hipLaunchKernelGGL((head_kernel<TA>), dim3((unsigned)Bp), dim3(256), 0, st, B, Bp, 1, hsum, a.b2, h1bar,
                      a.hist_off, Epn, a.margin, a.loss, a.users, dmA, dmc, dmc32, Xpn, a.g_tok_g, a.g_tok_b, a.g_b2);
@@ -1146,20 +1004,17 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
   {
     const int64_t ks = D / kZParts;
     GemmProblem p = {Bp, F, ks, dmc, D, ks, W2T, D, ks, dZ, F, Bp * F, kZParts, 1.0f};
-    if ((rc = gemm_group_dispatch(dt, NR_F32, &p, 1, st))) return rc;
+    NR_TRY(gemm_group_dispatch(dt, NR_F32, &p, 1, st));
   }
-  if ((rc = sum_parts(dZ, kZParts, Bp * F, dZs, Bp * F, st))) return rc;
+  NR_TRY(sum_parts(dZ, kZParts, Bp * F, dZs, Bp * F, st));
   const int64_t gchunks = (Hp + kGRows - 1) / kGRows;
   hipLaunchKernelGGL((geglu_bwd_kernel<TA, kGRows>), dim3(F / 512, (unsigned)gchunks), dim3(256), 0, st, Hp, G, dZs,
                      row_seg, dG, gpart);
   NR_LT_CHECK("geglu_bwd");
-  if ((rc = nr_col_sum(NR_F32, gchunks, 2 * F, gpart, 2 * F, a.g_b1, st))) return rc;
+  NR_TRY(nr_col_sum(NR_F32, gchunks, 2 * F, gpart, 2 * F, a.g_b1, st));
   // fork: the weight grads of W1 (K = Hp, 128 tiles) and W2 on the side stream,
   // beside the data-grad GEMM dY = dG W1 (132 persistent workgroups) on this one
-  if (hipEventRecord(side.fork, st) != hipSuccess || hipStreamWaitEvent(side.s, side.fork, 0) != hipSuccess) {
-    set_error("nr_latent_train_step: fork failed");
-    return NR_ERR_HIP;
-  }
+  NR_TRY(stream_fork(st, side.s, side.fork, kFn, "fork"));
   if constexpr (sizeof(TA) == 2) {
     // bf16: the weight grads read dG, Y, dm, zbar row-major (TN grouped GEMM, no transposes)
     GemmProblem p[2] = {
@@ -1167,58 +1022,46 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
         {D, F, Bp, dmA, D, 0, zbar, F, 0, a.g_W2, F, 0, 1, 1.0f},
     };
     const bool sqf[2] = {true, true};
-    if ((rc = gemm_group_tn_dispatch(NR_F32, p, 2, side.s, sqp ? sqp + kSqW12 : nullptr, sqf, &n_sq12,
-                                     kSqFold - kSqW12)))
-      return rc;
+    NR_TRY(gemm_group_tn_dispatch(NR_F32, p, 2, side.s, sqp ? sqp + kSqW12 : nullptr, sqf, &n_sq12,
+                                  kSqFold - kSqW12));
   } else {
     TList t;
     t.add(dG, 2 * F, dGT, Hp, Hp, 2 * F, true);
     t.add(Y, D, YT, Hp, Hp, D, true);
     t.add(dmA, D, dmT, Bp, Bp, D, true);
     t.add(zbar, F, zbarT, Bp, Bp, F, true);
-    if ((rc = launch_tlist<TA, TA>(t, side.s))) return rc;
+    NR_TRY(launch_tlist<TA, TA>(t, side.s));
     GemmProblem p[2] = {
         {2 * F, D, Hp, dGT, Hp, 0, YT, Hp, 0, a.g_W1, D, 0, 1, 1.0f},
         {D, F, Bp, dmT, Bp, 0, zbarT, Bp, 0, a.g_W2, F, 0, 1, 1.0f},
     };
     const bool sqf[2] = {true, true};
-    if ((rc = gemm_group_dispatch(dt, NR_F32, p, 2, side.s, sqp ? sqp + kSqW12 : nullptr, sqf, &n_sq12,
-                                  kSqFold - kSqW12)))
-      return rc;
+    NR_TRY(gemm_group_dispatch(dt, NR_F32, p, 2, side.s, sqp ? sqp + kSqW12 : nullptr, sqf, &n_sq12,
+                               kSqFold - kSqW12));
   }
-  {
-    if (hipEventRecord(side.join, side.s) != hipSuccess) {
-      set_error("nr_latent_train_step: join record failed");
-      return NR_ERR_HIP;
-    }
-  }
-  if ((rc = gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, D, 2 * F, dG, 2 * F, W1T, 2 * F, nullptr, nullptr, 0, dY, D, st)))
-    return rc;
+  NR_TRY_HIP(hipEventRecord(side.join, side.s), kFn, "join record");
+  NR_TRY(gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, D, 2 * F, dG, 2 * F, W1T, 2 * F, nullptr, nullptr, 0, dY, D, st));
   hipLaunchKernelGGL((ln_bwd_kernel<TA, 0>), dim3(grid_rows(Hp, 512)), dim3(256), 0, st, Hp, Hp, H1, nullptr, a.nf_g, 1e-5f, dY,
                      dmc32, row_seg, dH1, nullptr, nullptr, a.g_nf_g, a.g_nf_b, nullptr, nullptr);
   NR_LT_CHECK("ln_f_bwd");
   if (dt == NR_BF16) {
     // dS = P (dP - sum_group P dP) in the dP GEMM's epilogue (NR_EPI_SOFTMAX64_BWD, R = P)
-    if ((rc = gemm_dispatch(dt, dt, NR_EPI_SOFTMAX64_BWD, Hp, S, D, dH1, D, BtT, D, nullptr, Pm, S, dS, S, st)))
-      return rc;
+    NR_TRY(gemm_dispatch(dt, dt, NR_EPI_SOFTMAX64_BWD, Hp, S, D, dH1, D, BtT, D, nullptr, Pm, S, dS, S, st));
   } else {
-    if ((rc = gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, S, D, dH1, D, BtT, D, nullptr, nullptr, 0, dP, S, st)))
-      return rc;
+    NR_TRY(gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, S, D, dH1, D, BtT, D, nullptr, nullptr, 0, dP, S, st));
     const int64_t g = (Hp * HEADS + 3) / 4;
-    hipLaunchKernelGGL((softmax64_bwd_kernel<TA>), dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, st, Hp, Pm,
-                       dP, dS);
+    hipLaunchKernelGGL((softmax64_bwd_kernel<TA, TA>), dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, st,
+                       Hp * HEADS, (int64_t)HEADS, Pm, (int64_t)S, dP, (int64_t)S, dS, (int64_t)S);
     NR_LT_CHECK("softmax64_bwd");
   }
   // fork 2: dA / dBt and the whole fold backward need only dS, dH1, P, X from here on,
   // so they run on a third stream beside dX and the LN_q / token LN grads.
   // (Starting dBt's transposes and GEMM before the dS GEMM, on a third event, measured
   // no gain: they slowed dS by as much, profiles/round4/train/r4s9.)
-  if (hipEventRecord(side.fork2, st) != hipSuccess || hipStreamWaitEvent(side.s2, side.fork2, 0) != hipSuccess) {
-    set_error("nr_latent_train_step: fork 2 failed");
-    return NR_ERR_HIP;
-  }
-  if ((rc = gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, D, S, dS, S, AT, S, nullptr, nullptr, 0, dX, D, st))) return rc;
-  NR_LT_TOK(hipLaunchKernelGGL((ln_bwd_kernel<TA, 1, TT>), dim3(grid_rows(Hp, 512)), dim3(256), 0, st, Hp, a.Hs, Sx,
+  NR_TRY(stream_fork(st, side.s2, side.fork2, kFn, "fork 2"));
+  NR_TRY(gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, D, S, dS, S, AT, S, nullptr, nullptr, 0, dX, D, st));
+  NR_TOK_DT(a.tok_dtype,
+            hipLaunchKernelGGL((ln_bwd_kernel<TA, 1, TT>), dim3(grid_rows(Hp, 512)), dim3(256), 0, st, Hp, a.Hs, Sx,
                                a.tok_last, a.nq_g, 1e-5f, dX, dH1, a.hist_idx, nullptr, a.g_tok_g, a.g_tok_b,
                                a.g_nq_g, a.g_nq_b, a.tok_g, a.tok_b));
   NR_LT_CHECK("ln_q_bwd");  // (with the head's pos / neg part: the token LN's grads are final)
@@ -1228,7 +1071,7 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
     const float* gp[] = {a.g_tok_g, a.g_tok_b, a.g_nq_g, a.g_nq_b, a.g_nf_g, a.g_nf_b, a.g_b1, a.g_b2};
     const int64_t gn[] = {D, D, D, D, D, D, 2 * F, D};
     for (int i = 0; i < 8; ++i) q.add(gp[i], gn[i]);
-    if ((rc = sq_list(q, a.sumsq, st))) return rc;
+    NR_TRY(sq_list(q, a.sumsq, st));
   }
   hipStream_t s2 = side.s2;
   // ---- dA = dS^T X and dBt = dH1^T P as kWParts K-slices (16 + 16 tiles alone would hold 32 CUs
@@ -1240,29 +1083,29 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
         {S, D, kw, dS, S, kw * S, X, D, kw * D, gA, D, (int64_t)S * D, kWParts, 1.0f},
         {D, S, kw, dH1, D, kw * D, Pm, S, kw * S, gBt, S, (int64_t)D * S, kWParts, 1.0f},
     };
-    if ((rc = gemm_group_tn_dispatch(NR_F32, p, 2, s2))) return rc;
+    NR_TRY(gemm_group_tn_dispatch(NR_F32, p, 2, s2));
   } else {
     TList t;
     t.add(dH1, D, dH1T, Hpp, Hp, D, true, Hpp);
     t.add(Pm, S, PT, Hpp, Hp, S, true, Hpp);
     t.add(dS, S, dST, Hpp, Hp, S, true, Hpp);
     t.add(X, D, XT, Hpp, Hp, D, true, Hpp);
-    if ((rc = launch_tlist<TA, TA>(t, s2))) return rc;
+    NR_TRY(launch_tlist<TA, TA>(t, s2));
     const int64_t kw = L.kw;
     GemmProblem p[2] = {
         {S, D, kw, dST, Hpp, kw, XT, Hpp, kw, gA, D, (int64_t)S * D, kWParts, 1.0f},
         {D, S, kw, dH1T, Hpp, kw, PT, Hpp, kw, gBt, S, (int64_t)D * S, kWParts, 1.0f},
     };
-    if ((rc = gemm_group_dispatch(dt, NR_F32, p, 2, s2))) return rc;
+    NR_TRY(gemm_group_dispatch(dt, NR_F32, p, 2, s2));
   }
   // ---- fold backward
   {
     // the K-slices summed on the way into both converted operands (one launch; the
     // slices summed in order)
     SCList t;
-    if ((rc = t.add(gA, D, kWParts, (int64_t)S * D, S, D, gA16, D, gAT16, S))) return rc;
-    if ((rc = t.add(gBt, S, kWParts, (int64_t)D * S, D, S, gBt16, S, gBtT16, D))) return rc;
-    if ((rc = launch_sumconv<TA>(t, s2))) return rc;
+    NR_TRY(t.add(gA, D, kWParts, (int64_t)S * D, S, D, gA16, D, gAT16, S));
+    NR_TRY(t.add(gBt, S, kWParts, (int64_t)D * S, D, S, gBt16, S, gBtT16, D));
+    NR_TRY(launch_sumconv<TA>(t, s2));
   }
   {
     GemmProblem p[4] = {
@@ -1276,13 +1119,12 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
         {D, DH, NL, gBt16, S, NL, KVT + (int64_t)F * NL, NL, (int64_t)DH * NL, a.g_Wo, F, DH, HEADS, 1.0f},
     };
     const bool sqf[4] = {true, false, false, true};  // dWq, dWo
-    if ((rc = gemm_group_dispatch(dt, NR_F32, p, 4, s2, sqp ? sqp + kSqFold : nullptr, sqf, &n_sqf, kSqKv - kSqFold)))
-      return rc;
+    NR_TRY(gemm_group_dispatch(dt, NR_F32, p, 4, s2, sqp ? sqp + kSqFold : nullptr, sqf, &n_sqf, kSqKv - kSqFold));
   }
   {
     SCList t;
-    if ((rc = t.add(dKV, 2 * F, 1, 0, NL, 2 * F, dKV16, 2 * F, dKVT16, NL))) return rc;
-    if ((rc = launch_sumconv<TA>(t, s2))) return rc;
+    NR_TRY(t.add(dKV, 2 * F, 1, 0, NL, 2 * F, dKV16, 2 * F, dKVT16, NL));
+    NR_TRY(launch_sumconv<TA>(t, s2));
   }
   {
     const int64_t ks = 2 * F / kLatParts;
@@ -1293,22 +1135,16 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
         {NL, D, ks, dKV16, 2 * F, ks, WkvT, 2 * F, ks, dlat, D, (int64_t)NL * D, kLatParts, 1.0f},
     };
     const bool sqf[2] = {true, false};  // dWkv
-    if ((rc = gemm_group_dispatch(dt, NR_F32, p, 2, s2, sqp ? sqp + kSqKv : nullptr, sqf, &n_sqkv, kSqSlots - kSqKv)))
-      return rc;
+    NR_TRY(gemm_group_dispatch(dt, NR_F32, p, 2, s2, sqp ? sqp + kSqKv : nullptr, sqf, &n_sqkv, kSqSlots - kSqKv));
   }
-  if ((rc = sum_parts(dlat, kLatParts, (int64_t)NL * D, dlat, (int64_t)NL * D, s2))) return rc;
+  NR_TRY(sum_parts(dlat, kLatParts, (int64_t)NL * D, dlat, (int64_t)NL * D, s2));
   hipLaunchKernelGGL(lnc_bwd_kernel, dim3(NL / 4), dim3(256), 0, s2, a.latents, a.nc_g, 1e-5f, 1, dlat,
                      a.g_latents, a.g_nc_g, a.g_nc_b);
   NR_LT_CHECK("ln_c_bwd");
-  if (hipEventRecord(side.join2, s2) != hipSuccess) {
-    set_error("nr_latent_train_step: join 2 record failed");
-    return NR_ERR_HIP;
-  }
+  NR_TRY_HIP(hipEventRecord(side.join2, s2), kFn, "join 2 record");
   // join: the side stream's weight grads are done before anything later on `stream`
-  if (hipStreamWaitEvent(st, side.join, 0) != hipSuccess || hipStreamWaitEvent(st, side.join2, 0) != hipSuccess) {
-    set_error("nr_latent_train_step: join failed");
-    return NR_ERR_HIP;
-  }
+  NR_TRY_HIP(hipStreamWaitEvent(st, side.join, 0), kFn, "join");
+  NR_TRY_HIP(hipStreamWaitEvent(st, side.join2, 0), kFn, "join");
   if (sqp) {
     // the side streams' weight grads: their GEMM-epilogue partials and the squares of
     // the small fold grads (here, not on s2: the optimizer that follows on this stream
@@ -1320,49 +1156,13 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
     q.add(a.g_latents, NL * D);
     q.add(a.g_nc_g, D);
     q.add(a.g_nc_b, D);
-    if ((rc = sq_list(q, a.sumsq, st))) return rc;
+    NR_TRY(sq_list(q, a.sumsq, st));
   }
-#undef NR_LT_TOK
 #undef NR_LT_CHECK
   return NR_OK;
 }
 
 }  // namespace lt
-
-// (nr_common.h) one set per host thread and device; the streams are created on
-// the device of `st`, so a step launched on another GPU's stream than the
-// current device forks and joins on that GPU.
-int train_side_streams(hipStream_t st, const char* fn, TrainSide& out) {
-  thread_local TrainSide t_side[64];
-  int dev = 0;
-  if (hipStreamGetDevice(st, &dev) != hipSuccess || dev < 0 || dev >= 64) {
-    set_error("%s: cannot resolve the stream's device", fn);
-    return NR_ERR_HIP;
-  }
-  TrainSide& sd = t_side[dev];
-  if (!sd.s) {
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess || (cur != dev && hipSetDevice(dev) != hipSuccess)) {
-      set_error("%s: cannot select device %d", fn, dev);
-      return NR_ERR_HIP;
-    }
-    const bool ok = hipStreamCreateWithFlags(&sd.s, hipStreamNonBlocking) == hipSuccess &&
-                    hipStreamCreateWithFlags(&sd.s2, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&sd.join, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&sd.fork2, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&sd.join2, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&sd.wt, hipEventDisableTiming) == hipSuccess;
-    if (cur != dev) (void)hipSetDevice(cur);
-    if (!ok) {
-      set_error("%s: cannot create the side streams / events", fn);
-      sd = TrainSide{};
-      return NR_ERR_HIP;
-    }
-  }
-  out = sd;
-  return NR_OK;
-}
 }  // namespace nr
 
 extern "C" int64_t nr_latent_train_workspace_bytes(int dtype, int64_t B, int64_t U, int64_t Hs) {
@@ -1374,13 +1174,7 @@ extern "C" int nr_latent_train_step(const nr_latent_train_args* args, void* ws, 
   nr::clear_error();
   NR_CHECK_ARG(args, "nr_latent_train_step: null args");
   const nr_latent_train_args& a = *args;
-  NR_CHECK_ARG(a.dtype == NR_F32 || a.dtype == NR_BF16, "nr_latent_train_step: dtype must be NR_F32 or NR_BF16");
-  NR_CHECK_ARG(a.tok_dtype == NR_F32 || a.tok_dtype == NR_BF16 || a.tok_dtype == NR_F16,
-               "nr_latent_train_step: bad tok_dtype");
-  NR_CHECK_ARG(a.B >= 1 && a.U >= 1 && a.Hs >= 1, "nr_latent_train_step: empty batch (B=%lld U=%lld Hs=%lld)",
-               (long long)a.B, (long long)a.U, (long long)a.Hs);
-  NR_CHECK_ARG(a.Hs <= (1ll << 31) - 1024 && a.U <= (1ll << 31) && a.B <= (1ll << 24),
-               "nr_latent_train_step: batch too large");
+  NR_TRY(nr::check_step_args("nr_latent_train_step", a.dtype, a.tok_dtype, a.B, a.U, a.Hs));
   NR_CHECK_DEVICE("nr_latent_train_step", a.tok_last, a.hist_idx, a.hist_off, a.pos, a.neg, a.tok_g, a.tok_b,
                   a.latents, a.nq_g, a.nq_b, a.nc_g, a.nc_b, a.Wq, a.Wkv, a.Wo, a.nf_g, a.nf_b, a.W1, a.b1, a.W2, a.b2);
   NR_CHECK_DEVICE("nr_latent_train_step", a.g_tok_g, a.g_tok_b, a.g_latents, a.g_nq_g, a.g_nq_b, a.g_nc_g, a.g_nc_b,

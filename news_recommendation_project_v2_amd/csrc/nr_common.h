@@ -63,7 +63,7 @@ int row_stats_dispatch(int dtype, int64_t rows, int64_t dim, const void* x, int6
 // NR_EPI_GEGLU): C = epi(rstd_m * (A W^T - mean_m u_n) + c_n); stats [M] (mean, rstd), uc [2][N]
 int gemm_lnfold_dispatch(int epi, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* W,
                          int64_t ldw, const float* stats, const float* uc, void* C, int64_t ldc, hipStream_t s);
-// The training steps' side streams (latent_train.hip): two non-blocking streams
+// The training steps' side streams (train.hip): two non-blocking streams
 // and their fork / join events per host thread and device, created on first use
 // on the DEVICE OF `st` (not the caller's current device) and kept.
 struct TrainSide {
@@ -177,18 +177,27 @@ __device__ __forceinline__ float wave_max(float v) {
 // kernels keep gelu_erf.
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2v fma2(f32x2v a, f32x2v b, f32x2v c) { return __builtin_elementwise_fma(a, b, c); }
+constexpr float kErfcS = 0.8493218002880191f, kErfcSmax = 4.804489635145799f;  // sqrt(log2(e) / 2), 4 sqrt(log2 e)
+// p[n] = P(c[n]) - 1 for N pairs of values c = min(|s|, kErfcSmax), the N Horner chains
+// stepped together: the one copy of the fit's coefficients
+template <int N>
+__device__ __forceinline__ void erfc_poly2(const f32x2v (&c)[N], f32x2v (&p)[N]) {
+  constexpr float k[9] = {-3.57632359e-07f, 8.19052786e-07f, 0.000115395807f, -0.00191940868f,       0.0159611721f,
+                          -0.0876397938f,   0.364198327f,    -1.35544741f,    3.20236495e-06f - 1.0f};
+#pragma unroll
+  for (int n = 0; n < N; ++n) p[n] = (f32x2v)k[0];
+#pragma unroll
+  for (int i = 1; i < 9; ++i)
+#pragma unroll
+    for (int n = 0; n < N; ++n) p[n] = fma2(p[n], c[n], (f32x2v)k[i]);
+}
 __device__ __forceinline__ void gelu_erf2x2(f32x2v& g0, f32x2v& g1) {
-  constexpr float kS = 0.8493218002880191f, kSmax = 4.804489635145799f;
-  const f32x2v s0 = g0 * kS, s1 = g1 * kS;
-  const f32x2v c0 = {fminf(fabsf(s0.x), kSmax), fminf(fabsf(s0.y), kSmax)};
-  const f32x2v c1 = {fminf(fabsf(s1.x), kSmax), fminf(fabsf(s1.y), kSmax)};
-  f32x2v p0 = (f32x2v)-3.57632359e-07f, p1 = (f32x2v)-3.57632359e-07f;
-#define NR_G4(c)                      \
-  p0 = fma2(p0, c0, (f32x2v)(c)); \
-  p1 = fma2(p1, c1, (f32x2v)(c));
-  NR_G4(8.19052786e-07f) NR_G4(0.000115395807f) NR_G4(-0.00191940868f) NR_G4(0.0159611721f)
-  NR_G4(-0.0876397938f) NR_G4(0.364198327f) NR_G4(-1.35544741f) NR_G4(3.20236495e-06f - 1.0f)
-#undef NR_G4
+  const f32x2v s0 = g0 * kErfcS, s1 = g1 * kErfcS;
+  const f32x2v c[2] = {{fminf(fabsf(s0.x), kErfcSmax), fminf(fabsf(s0.y), kErfcSmax)},
+                       {fminf(fabsf(s1.x), kErfcSmax), fminf(fabsf(s1.y), kErfcSmax)}};
+  f32x2v p[2];
+  erfc_poly2<2>(c, p);
+  const f32x2v p0 = p[0], p1 = p[1];
   // w = P - 1 - s^2: 2^w = erfc / 2; gelu = max(g, 0) - |g| erfc / 2 (g (1 - erfc / 2)
   // for g >= 0, g erfc / 2 below) -- one fma with |.| / neg modifiers, no select
   const f32x2v w0 = fma2(-s0, s0, p0), w1 = fma2(-s1, s1, p1);

@@ -8,19 +8,9 @@
 // The GEMMs (forward, data-grad and weight-grad) all run on the C = A·Wᵀ MFMA
 // kernel; the weight-grad and data-grad operands are produced by the LDS
 // transpose below.  Everything here is HBM-bound row / reduction work.
-#include "nr_common.h"
-#include "nr_rows.h"
+#include "nr_train.h"
 
 namespace nr {
-
-template <typename T>
-__device__ __forceinline__ float ldf(const T* p) {
-  if constexpr (sizeof(T) == 4) return *p; else return (float)*p;
-}
-template <typename T>
-__device__ __forceinline__ void stf(T* p, float v) {
-  if constexpr (sizeof(T) == 4) *p = v; else *p = (T)v;
-}
 
 // ----------------------------------------------------------------- gather rows
 // dst[i] = src[idx[i]] (idx < 0 -> zero row), with dtype conversion.
@@ -203,10 +193,8 @@ __global__ __launch_bounds__(256) void final_pool_bwd_kernel(int64_t n_seg, cons
 }
 
 // ----------------------------------------------------------------- cosine + margin loss
-// F.cosine_similarity(u, e) = (u / max(|u|, 1e-8)) . (e / max(|e|, 1e-8))
-// (data_model_helper.py / trainer.py:1058-1061), MarginRankingLoss(margin)(s_pos,
-// s_neg, y=1) = mean(clamp_min(margin - (s_pos - s_neg), 0)) (trainer.py:1063-1066).
-// One wave per batch row; du written, dE rows (pos / neg) accumulated with atomics.
+// The loss and its gradient are CosMargin (nr_train.h).  One wave per batch row;
+// du written, dE rows (pos / neg) accumulated with atomics.
 __global__ __launch_bounds__(256) void cosine_margin_kernel(int64_t B, const float* __restrict__ users,
                                                             const float* __restrict__ E, int64_t lde,
                                                             const int32_t* __restrict__ pos,
@@ -214,12 +202,11 @@ __global__ __launch_bounds__(256) void cosine_margin_kernel(int64_t B, const flo
                                                             float* __restrict__ s_out, float* __restrict__ loss,
                                                             float* __restrict__ du, float* __restrict__ dE) {
   constexpr int D = 1024, NJ = D / 256;
-  constexpr float EPS = 1e-8f;
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   float u[NJ][4], ep[NJ][4], en[NJ][4];
-  float uu = 0.f, pp = 0.f, nn = 0.f, up = 0.f, un = 0.f;
+  CosDots dots;
   const float* ur = users + b * D;
   const float* pr = E + (int64_t)pos[b] * lde;
   const float* nr_ = E + (int64_t)neg[b] * lde;
@@ -233,27 +220,14 @@ __global__ __launch_bounds__(256) void cosine_margin_kernel(int64_t B, const flo
     ep[j][0] = p.x; ep[j][1] = p.y; ep[j][2] = p.z; ep[j][3] = p.w;
     en[j][0] = q.x; en[j][1] = q.y; en[j][2] = q.z; en[j][3] = q.w;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uu = fmaf(u[j][t], u[j][t], uu);
-      pp = fmaf(ep[j][t], ep[j][t], pp);
-      nn = fmaf(en[j][t], en[j][t], nn);
-      up = fmaf(u[j][t], ep[j][t], up);
-      un = fmaf(u[j][t], en[j][t], un);
-    }
+    for (int t = 0; t < 4; ++t) dots.add(u[j][t], ep[j][t], en[j][t]);
   }
-  uu = wave_sum(uu); pp = wave_sum(pp); nn = wave_sum(nn); up = wave_sum(up); un = wave_sum(un);
-  const float nu = sqrtf(uu), np_ = sqrtf(pp), nq = sqrtf(nn);
-  const float iu = 1.0f / fmaxf(nu, EPS), ip = 1.0f / fmaxf(np_, EPS), iq = 1.0f / fmaxf(nq, EPS);
-  const float sp = up * iu * ip, sn = un * iu * iq;
-  const float v = margin - (sp - sn);
-  const float act = v >= 0.f ? 1.0f : 0.0f;  // clamp_min backward passes where input >= min
-  const float gsp = -act / (float)B, gsn = act / (float)B;
+  dots.reduce(wave_sum);
+  const CosMargin cm(dots, margin, B);
   if (lane == 0) {
-    if (s_out) { s_out[b] = sp; s_out[B + b] = sn; }
-    atomicAdd(loss, fmaxf(v, 0.f) / (float)B);
+    if (s_out) { s_out[b] = cm.sp; s_out[B + b] = cm.sn; }
+    atomicAdd(loss, cm.loss_term());
   }
-  // d cos(u, e) / du = (ê - [|u| > eps] cos û) / max(|u|, eps)   (û = u / max(|u|, eps))
-  const float cu = nu > EPS ? 1.f : 0.f, cp = np_ > EPS ? 1.f : 0.f, cq = nq > EPS ? 1.f : 0.f;
   float* dp = dE + (int64_t)pos[b] * lde;
   float* dn = dE + (int64_t)neg[b] * lde;
 #pragma unroll
@@ -262,10 +236,9 @@ __global__ __launch_bounds__(256) void cosine_margin_kernel(int64_t B, const flo
     float g[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const float uh = u[j][t] * iu, ph = ep[j][t] * ip, qh = en[j][t] * iq;
-      g[t] = gsp * (ph - cu * sp * uh) * iu + gsn * (qh - cu * sn * uh) * iu;
-      atomicAdd(dp + e + t, gsp * (uh - cp * sp * ph) * ip);
-      atomicAdd(dn + e + t, gsn * (uh - cq * sn * qh) * iq);
+      g[t] = cm.du(u[j][t], ep[j][t], en[j][t]);
+      atomicAdd(dp + e + t, cm.dpos(u[j][t], ep[j][t]));
+      atomicAdd(dn + e + t, cm.dneg(u[j][t], en[j][t]));
     }
     *reinterpret_cast<float4*>(du + b * D + e) = make_float4(g[0], g[1], g[2], g[3]);
   }
@@ -348,22 +321,12 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(int64_t n, const TI*
     for (int t = 0; t < 4; ++t) { ag[j][t] = 0.f; ab[j][t] = 0.f; }
   for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n; i += (int64_t)gridDim.x * 4) {
     const int64_t row = row_idx ? row_idx[i] : i;
-    float v[NJ][4];
-    float s = 0.f;
+    float v[NJ][4], mean, rstd;
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        v[j][t] = ldf<TI>(x + row * ldx + j * 256 + lane * 4 + t);
-        s += v[j][t];
-      }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { const float dd = v[j][t] - mean; q = fmaf(dd, dd, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+      for (int t = 0; t < 4; ++t) v[j][t] = ldf<TI>(x + row * ldx + j * 256 + lane * 4 + t);
+    row_stats4<NJ>(v, (float)D, eps, mean, rstd);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const float4 g = *reinterpret_cast<const float4*>(dy + i * lddy + j * 256 + lane * 4);
@@ -375,19 +338,7 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(int64_t n, const TI*
       }
     }
   }
-  // fold the 4 waves' register partials in LDS (fixed order), one atomic per column per block
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      sg[wave][j * 256 + lane * 4 + t] = ag[j][t];
-      sb[wave][j * 256 + lane * 4 + t] = ab[j][t];
-    }
-  __syncthreads();
-  for (int c = threadIdx.x; c < D; c += 256) {
-    atomicAdd(dg + c, (sg[0][c] + sg[1][c]) + (sg[2][c] + sg[3][c]));
-    atomicAdd(db + c, (sb[0][c] + sb[1][c]) + (sb[2][c] + sb[3][c]));
-  }
+  fold_cols_atomic<NJ>(sg, sb, ag, ab, dg, db);
 }
 
 // ----------------------------------------------------------------- latent attention training (f32)
@@ -406,6 +357,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(int64_t n, const flo
   constexpr int D = 1024, NJ = D / 256;
   const int lane = threadIdx.x & 63;
   for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (int64_t)gridDim.x * 4) {
+    // (A private copy of ln_bwd_row, nr_train.h: the residual add sits under a branch,
+    // and which of this body's multiplies the compiler fuses into the adds that follow
+    // depends on the blocks that branch cuts it into.  Through the shared helper the
+    // fused set, and with it the last bit of some dx, came out different.)
     float v[NJ][4], g[NJ][4];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) ld4<float>(x + row * ldx + j * 256 + lane * 4, v[j]);
@@ -441,21 +396,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(int64_t n, const flo
   }
 }
 
-// dS = P * (dP - sum_group(P * dP)) over groups of 64 columns (one head's
-// latents; SDPA softmax, latent_attention.py:72).  One wave per (row, group).
-template <typename TO>
-__global__ __launch_bounds__(256) void softmax64_bwd_kernel(int64_t n_groups, int64_t groups_per_row,
-                                                            const float* __restrict__ p, int64_t ldp,
-                                                            const float* __restrict__ dp, int64_t lddp,
-                                                            TO* __restrict__ ds, int64_t ldds) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t gi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); gi < n_groups; gi += (int64_t)gridDim.x * 4) {
-    const int64_t row = gi / groups_per_row, col = (gi % groups_per_row) * 64 + lane;
-    const float pv = p[row * ldp + col], dv = dp[row * lddp + col];
-    const float dot = wave_sum(pv * dv);
-    stf<TO>(ds + row * ldds + col, pv * (dv - dot));
-  }
-}
+// (the per-head softmax backward is softmax64_bwd_kernel, nr_train.h)
 
 // z[:, j] = a_j * gelu(g_j),  a = G[:, :F], g = G[:, F:]  (GEGLU, latent_attention.py:24-27)
 template <typename TO>
@@ -487,8 +428,8 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(int64_t rows, int64_t f,
     float da[4], dg[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const float cdf = 0.5f * (1.0f + erff(g[t] * 0.70710678118654752440f));
-      const float pdf = 0.39894228040143267794f * expf(-0.5f * g[t] * g[t]);
+      float cdf, pdf;
+      gelu_cdf_pdf(g[t], cdf, pdf);
       da[t] = d[t] * g[t] * cdf;
       dg[t] = d[t] * a[t] * (cdf + g[t] * pdf);
     }
@@ -503,11 +444,9 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(int64_t rows, int64_t f,
 // serialise at the memory side: MI355X_MICROARCH.md "Global float atomics").
 __global__ __launch_bounds__(256) void sumsq_kernel(int64_t n, const float* __restrict__ x, float* __restrict__ out) {
   __shared__ float part[4];
-  float s = sumsq_range(x, n, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, (part[0] + part[1]) + (part[2] + part[3]));
+  const float s = sumsq_range(x, n, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256);
+  const float t = block_sum4(s, part);
+  if (threadIdx.x == 0) atomicAdd(out, t);
 }
 
 // torch.nn.utils.clip_grad_norm_(max_norm): coef = min(max_norm / (norm + 1e-6), 1)
@@ -573,6 +512,41 @@ __global__ __launch_bounds__(256) void zero_kernel(ZList z) {
 int zero_ranges(const ZList& z, int blocks, hipStream_t s) {
   hipLaunchKernelGGL(zero_kernel, dim3((unsigned)blocks), dim3(256), 0, s, z);
   NR_CHECK_LAUNCH("zero_ranges");
+  return NR_OK;
+}
+
+// (nr_common.h) one set per host thread and device; the streams are created on
+// the device of `st`, so a step launched on another GPU's stream than the
+// current device forks and joins on that GPU.
+int train_side_streams(hipStream_t st, const char* fn, TrainSide& out) {
+  thread_local TrainSide t_side[64];
+  int dev = 0;
+  if (hipStreamGetDevice(st, &dev) != hipSuccess || dev < 0 || dev >= 64) {
+    set_error("%s: cannot resolve the stream's device", fn);
+    return NR_ERR_HIP;
+  }
+  TrainSide& sd = t_side[dev];
+  if (!sd.s) {
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess || (cur != dev && hipSetDevice(dev) != hipSuccess)) {
+      set_error("%s: cannot select device %d", fn, dev);
+      return NR_ERR_HIP;
+    }
+    const bool ok = hipStreamCreateWithFlags(&sd.s, hipStreamNonBlocking) == hipSuccess &&
+                    hipStreamCreateWithFlags(&sd.s2, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&sd.join, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&sd.fork2, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&sd.join2, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&sd.wt, hipEventDisableTiming) == hipSuccess;
+    if (cur != dev) (void)hipSetDevice(cur);
+    if (!ok) {
+      set_error("%s: cannot create the side streams / events", fn);
+      sd = TrainSide{};
+      return NR_ERR_HIP;
+    }
+  }
+  out = sd;
   return NR_OK;
 }
 
@@ -877,10 +851,10 @@ extern "C" int nr_softmax64_bwd(int dtype_out, int64_t rows, int64_t cols, const
   NR_CHECK_DEVICE("nr_softmax64_bwd", p, dp, ds);
   const int64_t gpr = cols / 64, ng = rows * gpr;
   if (dtype_out == NR_F32)
-    hipLaunchKernelGGL((softmax64_bwd_kernel<float>), dim3(rowwave_grid(ng)), dim3(256), 0, (hipStream_t)stream, ng,
+    hipLaunchKernelGGL((softmax64_bwd_kernel<float, float>), dim3(rowwave_grid(ng)), dim3(256), 0, (hipStream_t)stream, ng,
                        gpr, p, ldp, dp, lddp, (float*)ds, ldds);
   else
-    hipLaunchKernelGGL((softmax64_bwd_kernel<__bf16>), dim3(rowwave_grid(ng)), dim3(256), 0, (hipStream_t)stream, ng,
+    hipLaunchKernelGGL((softmax64_bwd_kernel<float, __bf16>), dim3(rowwave_grid(ng)), dim3(256), 0, (hipStream_t)stream, ng,
                        gpr, p, ldp, dp, lddp, (__bf16*)ds, ldds);
   NR_CHECK_LAUNCH("nr_softmax64_bwd");
   return NR_OK;

@@ -139,3 +139,21 @@ def test_final_train_step_refuses_host_pointers(lib, H):
     rc = lib.nr_final_train_step(ctypes.byref(a), P, 1 << 26, None)
     assert rc == -1 and "not device memory" in lib.nr_last_error().decode()
     assert lib.nr_final_train_workspace_bytes(7, 1, 1, 1) == -1
+
+
+def test_train_workspace_layouts_keep_their_sizes(lib):
+    """The two steps' workspace totals (every buffer at a 256-byte aligned offset, in
+    layout order) for a handful of (dtype, B, U, Hs), as recorded before the
+    layouts shared one cursor.  The FinalAttention sizes here do not depend on
+    the device's CU count (f32, or bf16 with a whole number of 256-row tiles)."""
+    F32, BF16 = _lib.NR_F32, _lib.NR_BF16
+    latent = {(F32, 1, 1, 1): 230428160, (BF16, 1, 1, 1): 147131904, (F32, 5, 40, 63): 230428160,
+              (BF16, 5, 40, 65): 151260928, (F32, 16, 500, 517): 308024832, (BF16, 16, 500, 517): 186455552,
+              (BF16, 256, 8000, 8310): 818581248, (F32, 256, 8000, 8310): 1522568960,
+              (BF16, 300, 9000, 12345): 1141755392}
+    final = {(F32, 1, 1, 1): 134307072, (F32, 5, 40, 63): 134372608, (F32, 16, 500, 517): 258284800,
+             (F32, 256, 8000, 8310): 2136023040, (BF16, 256, 8000, 8192): 590159872, (F32, 64, 100, 4096): 1109728512}
+    for args, want in latent.items():
+        assert lib.nr_latent_train_workspace_bytes(*args) == want, args
+    for args, want in final.items():
+        assert lib.nr_final_train_workspace_bytes(*args) == want, args
