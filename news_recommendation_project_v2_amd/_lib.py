@@ -143,30 +143,29 @@ class EncoderLayer(ctypes.Structure):
 
 LATENT_TRAIN_PARAMS = ("tok_g", "tok_b", "latents", "nq_g", "nq_b", "nc_g", "nc_b", "Wq", "Wkv", "Wo", "nf_g", "nf_b",
                        "W1", "b1", "W2", "b2")
-LATENT_TRAIN_GRADS = ("g_tok_g", "g_tok_b", "g_latents", "g_nq_g", "g_nq_b", "g_nc_g", "g_nc_b", "g_Wq", "g_Wkv",
-                      "g_Wo", "g_nf_g", "g_nf_b", "g_W1", "g_b1", "g_W2", "g_b2")
-
-
-class LatentTrainArgs(ctypes.Structure):
-    """struct nr_latent_train_args (include/newsrec.h)."""
-    _fields_ = ([("dtype", ctypes.c_int), ("tok_dtype", ctypes.c_int), ("B", ctypes.c_int64), ("U", ctypes.c_int64),
-                 ("Hs", ctypes.c_int64)]
-                + [(n, ctypes.c_void_p) for n in ("tok_last", "hist_idx", "hist_off", "pos", "neg")]
-                + [("margin", ctypes.c_float)]
-                + [(n, ctypes.c_void_p) for n in LATENT_TRAIN_PARAMS + LATENT_TRAIN_GRADS + ("loss", "users", "sumsq")])
-
-
+LATENT_TRAIN_GRADS = tuple("g_" + n for n in LATENT_TRAIN_PARAMS)
 FINAL_TRAIN_PARAMS = ("tok_g", "tok_b", "W1", "b1", "W2", "b2", "W3", "b3", "W4", "b4", "W5")
 FINAL_TRAIN_GRADS = tuple("g_" + n for n in FINAL_TRAIN_PARAMS)
 
 
+def _train_fields(params, grads, extra_fields=()) -> list:
+    """Fields of a train step's args struct: the batch head both steps share, the
+    step's own scalars (``extra_fields``, after ``margin``), then its parameter,
+    gradient and output pointers."""
+    ptrs = lambda names: [(n, _p) for n in names]
+    return ([("dtype", _i), ("tok_dtype", _i), ("B", _l), ("U", _l), ("Hs", _l)]
+            + ptrs(("tok_last", "hist_idx", "hist_off", "pos", "neg")) + [("margin", _f)] + list(extra_fields)
+            + ptrs(tuple(params) + tuple(grads) + ("loss", "users", "sumsq")))
+
+
+class LatentTrainArgs(ctypes.Structure):
+    """struct nr_latent_train_args (include/newsrec.h)."""
+    _fields_ = _train_fields(LATENT_TRAIN_PARAMS, LATENT_TRAIN_GRADS)
+
+
 class FinalTrainArgs(ctypes.Structure):
     """struct nr_final_train_args (include/newsrec.h)."""
-    _fields_ = ([("dtype", ctypes.c_int), ("tok_dtype", ctypes.c_int), ("B", ctypes.c_int64), ("U", ctypes.c_int64),
-                 ("Hs", ctypes.c_int64)]
-                + [(n, ctypes.c_void_p) for n in ("tok_last", "hist_idx", "hist_off", "pos", "neg")]
-                + [("margin", ctypes.c_float), ("p", ctypes.c_float), ("seed", ctypes.c_uint64 * 3)]
-                + [(n, ctypes.c_void_p) for n in FINAL_TRAIN_PARAMS + FINAL_TRAIN_GRADS + ("loss", "users", "sumsq")])
+    _fields_ = _train_fields(FINAL_TRAIN_PARAMS, FINAL_TRAIN_GRADS, [("p", _f), ("seed", ctypes.c_uint64 * 3)])
 
 
 class NewsRecHIPError(RuntimeError):

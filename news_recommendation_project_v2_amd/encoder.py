@@ -125,8 +125,7 @@ class XLMREncoder:
         T = int(np.asarray(lens, dtype=np.int64).sum())
         need = _lib.load().nr_encoder_workspace_bytes(_lib.NR_F32 if self.dtype == torch.float32 else _lib.NR_BF16,
                                                       T, len(lens))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._ws = ops.grow_workspace(self._ws, need, dev)
         return ops.encoder_forward(self._layers, self._emb, ids_d, lens_d, T, pool=pool, want_hidden=want_hidden,
                                    eps=LN_EPS, workspace=self._ws, status=status)
 

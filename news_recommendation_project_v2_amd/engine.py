@@ -156,9 +156,7 @@ class PoolScoreEngine:
         dt = _lib.NR_F32 if self.dtype == torch.float32 else _lib.NR_BF16
         fn = (_lib.load().nr_final_attn_workspace_bytes if self.pooler == "final"
               else _lib.load().nr_latent_workspace_bytes)
-        need = fn(dt, n)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws = ops.grow_workspace(self._ws, fn(dt, n), self.device)
         return self._ws
 
     def transform(self, rows: Optional[slice] = None, out: Optional[torch.Tensor] = None,

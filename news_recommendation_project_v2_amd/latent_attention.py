@@ -92,8 +92,12 @@ def lnfold_weights(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bia
     return {f"W{tag}_ln": wf.contiguous(), f"uc{tag}": torch.stack([u, c]).to(torch.float32).contiguous()}
 
 
-def _pad64(n: int) -> int:
-    return max(64, (n + 63) // 64 * 64)
+def _param_key(module: torch.nn.Module, dtype) -> tuple:
+    """Cache key of a pooler's prepared device weights: dtype, device, and every
+    parameter's storage and version (an in-place edit or a re-pointed ``.data``
+    moves it; writes through raw pointers do not -- the train steps reset the cache)."""
+    ps = list(module.parameters())
+    return (dtype, ps[0].device, tuple((p.data_ptr(), p._version) for p in ps))
 
 
 class _LatentItemFn(torch.autograd.Function):
@@ -121,12 +125,8 @@ class _LatentItemFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rows, A, Bt, gq, bq, gf, bf, W1, b1, W2, b2, mm_dtype=torch.float32):
-        Hs, D = rows.shape
-        Hp = _pad64(Hs)
-        dev = rows.device
-        E = torch.empty((Hp, D), dtype=torch.float32, device=dev)
-        E[:Hs] = rows
-        E[Hs:].zero_()
+        Hs = rows.shape[0]
+        E = ops.padded_rows(rows)
         A, Bt, W1, W2 = A.contiguous(), Bt.contiguous(), W1.contiguous(), W2.contiguous()
         f32 = torch.float32
         # GEMM operands in mm_dtype (bf16: MFMA bf16 operands, f32 accumulate and f32
@@ -148,12 +148,9 @@ class _LatentItemFn(torch.autograd.Function):
     def backward(ctx, dH):
         E, X, P, H1, Y, G, Z, A, Bt, gq, gf, W1, W2 = ctx.saved_tensors
         Hs, lo = ctx.Hs, ctx.mm_dtype
-        Hp, D = E.shape
-        dev = E.device
+        D, dev = E.shape[1], E.device
         f32 = torch.float32
-        dHp = torch.empty((Hp, D), dtype=f32, device=dev)
-        dHp[:Hs] = dH
-        dHp[Hs:].zero_()
+        dHp = ops.padded_rows(dH)
         c = (lambda t: t) if lo == f32 else (lambda t: ops.gather_rows(t, None, out_dtype=lo))
         T = lambda t: ops.transpose(t, out_dtype=lo)
         dZ = ops.gemm(c(dHp), T(W2), out_dtype=f32)
@@ -234,10 +231,6 @@ class LatentAttentionModel(torch.nn.Module):
         self.latents = torch.nn.Parameter(torch.randn(num_latents, latent_dim))
         self._hip_cache: Dict[tuple, dict] = {}
 
-    def _param_key(self, dtype):
-        ps = list(self.parameters())
-        return (dtype, ps[0].device, tuple((p.data_ptr(), p._version) for p in ps))
-
     @torch.no_grad()
     def folded_weights(self) -> Dict[str, torch.Tensor]:
         """float64 host fold of the constant latent K/V into A and Bt (see module doc)."""
@@ -273,7 +266,7 @@ class LatentAttentionModel(torch.nn.Module):
         }
 
     def hip_weights(self, dtype: torch.dtype = torch.float32) -> dict:
-        key = self._param_key(dtype)
+        key = _param_key(self, dtype)
         w = self._hip_cache.get(key)
         if w is None:
             dev = self.latents.device

@@ -20,7 +20,7 @@ from . import ops
 from ._lib import NewsRecHIPError
 from .attention import MyEncoder
 from .config import DEVICE, EMBEDDING_DIM, FINAL_ATTENTION_HIDDEN_DIM, NUM_HIDDEN_LAYERS, REDUCED_DIM
-from .latent_attention import LatentAttentionModel
+from .latent_attention import LatentAttentionModel, _param_key
 
 
 def last_token_pool(last_hidden_states: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
@@ -76,10 +76,6 @@ def pool_rows(pooler: str, table: torch.Tensor, hist_off: torch.Tensor) -> torch
     return ops.pool_rows(pooler, table, hist_off)
 
 
-def _pad64(n: int) -> int:
-    return max(64, (n + 63) // 64 * 64)
-
-
 class _FinalAttentionFn(torch.autograd.Function):
     """FinalAttention forward + backward on the HIP kernels, over the packed valid
     history rows (CSR ``off``), so the reference module trains through autograd
@@ -100,10 +96,9 @@ class _FinalAttentionFn(torch.autograd.Function):
     def forward(ctx, rows, off, ps, seeds, W1, b1, W2, b2, W3, b3, W4, b4, W5):
         Hs, D = rows.shape
         H = W1.shape[0]
-        Hp = _pad64(Hs)
         dev = rows.device
-        S = torch.zeros((Hp, D), dtype=torch.float32, device=dev)
-        S[:Hs] = rows
+        S = ops.padded_rows(rows)
+        Hp = S.shape[0]
         X1 = ops.gemm_relu_dropout(S, W1.contiguous(), b1.contiguous(), seeds[0], ps[0])
         X2 = ops.gemm_relu_dropout(X1, W2.contiguous(), b2.contiguous(), seeds[1], ps[1])
         XP = torch.empty((Hp, 2 * D), dtype=torch.float32, device=dev)
@@ -171,13 +166,9 @@ class FinalAttention(torch.nn.Module):
 
     pooler_kind = "final"
 
-    def _param_key(self, dtype):
-        ps = list(self.parameters())
-        return (dtype, ps[0].device, tuple((p.data_ptr(), p._version) for p in ps))
-
     def hip_weights(self, dtype: torch.dtype = torch.float32) -> dict:
         """Device weights for nr_final_attn_transform (cached until params change)."""
-        key = self._param_key(dtype)
+        key = _param_key(self, dtype)
         w = self._hip_cache.get(key)
         if w is None:
             with torch.no_grad():

@@ -14,6 +14,8 @@ import torch
 from . import _lib
 
 _DT = {torch.float32: _lib.NR_F32, torch.bfloat16: _lib.NR_BF16}
+# dtypes of the token-state rows (the blobs are fp16): gather_layernorm, ln_param_grad, the train steps
+TOKEN_DT = {**_DT, torch.float16: _lib.NR_F16}
 _EPI = {
     "none": _lib.NR_EPI_NONE,
     "relu": _lib.NR_EPI_RELU,
@@ -60,6 +62,28 @@ def _dtype(t: torch.Tensor, name: str) -> int:
     if t.dtype not in _DT:
         raise _lib.NewsRecHIPError(f"{name}: unsupported dtype {t.dtype}")
     return _DT[t.dtype]
+
+
+def _pad64(n: int) -> int:
+    """Rows padded to a multiple of 64 (the weight-grad GEMMs' K), at least 64."""
+    return max(64, (n + 63) // 64 * 64)
+
+
+def padded_rows(rows: torch.Tensor) -> torch.Tensor:
+    """``rows`` [n, D] as a fresh f32 [_pad64(n), D] tensor, the padding rows zero."""
+    n = rows.shape[0]
+    out = torch.empty((_pad64(n), rows.shape[1]), dtype=torch.float32, device=rows.device)
+    out[:n] = rows
+    out[n:].zero_()
+    return out
+
+
+def grow_workspace(ws: Optional[torch.Tensor], need: int, dev) -> torch.Tensor:
+    """``ws`` when it holds ``need`` bytes, else a new uint8 buffer of that size
+    (callers keep the result, so a workspace only ever grows)."""
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
 
 
 def set_persistent_workgroups(n: int = 0) -> None:
@@ -126,7 +150,7 @@ def gather_layernorm(x: torch.Tensor, row_idx: Optional[torch.Tensor], gammas: O
     dev = _dev(x, row_idx, gammas, betas, out)
     if x.dim() != 2 or x.stride(1) != 1:
         raise _lib.NewsRecHIPError("gather_layernorm: x must be row-major 2-D")
-    dt = {torch.float32: _lib.NR_F32, torch.bfloat16: _lib.NR_BF16, torch.float16: _lib.NR_F16}.get(x.dtype)
+    dt = TOKEN_DT.get(x.dtype)
     if dt is None:
         raise _lib.NewsRecHIPError(f"gather_layernorm: unsupported dtype {x.dtype}")
     dim = x.shape[1]
@@ -325,8 +349,7 @@ def final_attn_transform(emb: torch.Tensor, w: dict, out: Optional[torch.Tensor]
     if out is None:
         out = torch.empty((n, 2 * dim), dtype=emb.dtype, device=dev)
     need = _lib.load().nr_final_attn_workspace_bytes(dt, n)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    workspace = grow_workspace(workspace, need, dev)
     for k in ("W1", "W2", "W3", "W4", "W5"):
         if w[k].dtype != emb.dtype or not w[k].is_contiguous():
             raise _lib.NewsRecHIPError(f"final_attn_transform: {k} must be contiguous {emb.dtype}")
@@ -347,8 +370,7 @@ def latent_transform(emb: torch.Tensor, w: dict, out: Optional[torch.Tensor] = N
     if out is None:
         out = torch.empty((n, dim), dtype=emb.dtype, device=dev)
     need = _lib.load().nr_latent_workspace_bytes(dt, n)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    workspace = grow_workspace(workspace, need, dev)
     for k in ("A", "Bt", "W1i", "W2"):
         if w[k].dtype != emb.dtype or not w[k].is_contiguous():
             raise _lib.NewsRecHIPError(f"latent_transform: {k} must be contiguous {emb.dtype}")
@@ -431,8 +453,7 @@ def encoder_forward(layers, emb: dict, ids: torch.Tensor, seq_lens: torch.Tensor
     pooled = torch.empty((n_seq, 1024), dtype=torch.float32, device=dev) if pool else None
     hidden = torch.empty((n_tokens, 1024), dtype=emb["word"].dtype, device=dev) if want_hidden else None
     need = _lib.load().nr_encoder_workspace_bytes(dt, n_tokens, n_seq)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    workspace = grow_workspace(workspace, need, dev)
     _lib.call("nr_encoder_forward", dt, len(layers), ctypes.cast(layers, ctypes.c_void_p) if len(layers) else None,
               _ptr(emb["word"]), emb["word"].shape[0], _ptr(emb["pos"]), emb["pos"].shape[0], _ptr(emb["type"]),
               _ptr(emb["ln_g"]), _ptr(emb["ln_b"]), ctypes.c_float(eps), n_seq, n_tokens, _ptr(seq_lens), _ptr(ids),
@@ -441,8 +462,16 @@ def encoder_forward(layers, emb: dict, ids: torch.Tensor, seq_lens: torch.Tensor
 
 
 # ------------------------------------------------------------------ training step (config 5)
-def _dt(t: torch.Tensor, name: str) -> int:
-    return _dtype(t, name)
+def _grouped_arrays(problems, mnk):
+    """The (M, N, K, A, lda, W, ldw, C, ldc) ctypes arrays of grouped (a, w, out)
+    problems whose sizes are ``mnk`` = [(M, N, K), ...]."""
+    n = len(problems)
+    L, P = ctypes.c_int64 * n, ctypes.c_void_p * n
+    M, N, K = (L(*d) for d in zip(*mnk))
+    a, w, out = zip(*problems)
+    ptrs = lambda ts: P(*[t.data_ptr() for t in ts])
+    lds = lambda ts, name: L(*[_rowmajor(t, name) for t in ts])
+    return M, N, K, ptrs(a), lds(a, "a"), ptrs(w), lds(w, "w"), ptrs(out), lds(out, "out")
 
 
 def gemm_grouped(problems) -> None:
@@ -453,21 +482,14 @@ def gemm_grouped(problems) -> None:
     if not 1 <= len(problems) <= 8:
         raise _lib.NewsRecHIPError("gemm_grouped: 1..8 problems")
     dev = _dev(*[t for pr in problems for t in pr])
-    n = len(problems)
-    L = ctypes.c_int64 * n
-    P = ctypes.c_void_p * n
-    M, N, K, lda, ldw, ldc = L(), L(), L(), L(), L(), L()
-    A, W, C = P(), P(), P()
     for i, (a, w, out) in enumerate(problems):
         if a.dtype != w.dtype or a.shape[1] != w.shape[1] or tuple(out.shape) != (a.shape[0], w.shape[0]):
             raise _lib.NewsRecHIPError(f"gemm_grouped: problem {i} shape/dtype mismatch")
         if out.dtype != problems[0][2].dtype:
             raise _lib.NewsRecHIPError("gemm_grouped: all outputs must share a dtype")
-        M[i], K[i], N[i] = a.shape[0], a.shape[1], w.shape[0]
-        lda[i], ldw[i], ldc[i] = _rowmajor(a, "a"), _rowmajor(w, "w"), _rowmajor(out, "out")
-        A[i], W[i], C[i] = a.data_ptr(), w.data_ptr(), out.data_ptr()
-    _lib.call("nr_gemm_grouped", _dtype(problems[0][0], "a"), _dtype(problems[0][2], "out"), n, M, N, K, A, lda, W,
-              ldw, C, ldc, _stream(dev))
+    arrays = _grouped_arrays(problems, [(a.shape[0], w.shape[0], a.shape[1]) for a, w, _ in problems])
+    _lib.call("nr_gemm_grouped", _dtype(problems[0][0], "a"), _dtype(problems[0][2], "out"), len(problems), *arrays,
+              _stream(dev))
 
 
 def gemm_grouped_tn(problems, alpha=None) -> None:
@@ -479,10 +501,6 @@ def gemm_grouped_tn(problems, alpha=None) -> None:
         raise _lib.NewsRecHIPError("gemm_grouped_tn: 1..8 problems")
     dev = _dev(*[t for pr in problems for t in pr])
     n = len(problems)
-    L = ctypes.c_int64 * n
-    P = ctypes.c_void_p * n
-    M, N, K, lda, ldw, ldc = L(), L(), L(), L(), L(), L()
-    A, W, C = P(), P(), P()
     al = (ctypes.c_float * n)(*([1.0] * n if alpha is None else alpha))
     for i, (a, w, out) in enumerate(problems):
         if a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or a.shape[0] != w.shape[0] \
@@ -490,11 +508,8 @@ def gemm_grouped_tn(problems, alpha=None) -> None:
             raise _lib.NewsRecHIPError(f"gemm_grouped_tn: problem {i} shape/dtype mismatch")
         if out.dtype != problems[0][2].dtype:
             raise _lib.NewsRecHIPError("gemm_grouped_tn: all outputs must share a dtype")
-        K[i], M[i], N[i] = a.shape[0], a.shape[1], w.shape[1]
-        lda[i], ldw[i], ldc[i] = _rowmajor(a, "a"), _rowmajor(w, "w"), _rowmajor(out, "out")
-        A[i], W[i], C[i] = a.data_ptr(), w.data_ptr(), out.data_ptr()
-    _lib.call("nr_gemm_grouped_tn", _dtype(problems[0][2], "out"), n, M, N, K, A, lda, W, ldw, C, ldc, al,
-              _stream(dev))
+    arrays = _grouped_arrays(problems, [(a.shape[1], w.shape[1], a.shape[0]) for a, w, _ in problems])
+    _lib.call("nr_gemm_grouped_tn", _dtype(problems[0][2], "out"), n, *arrays, al, _stream(dev))
 
 
 def gemm_relu_dropout(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], seed: int, p: float,
@@ -505,7 +520,7 @@ def gemm_relu_dropout(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Ten
     N = w.shape[0]
     if out is None:
         out = torch.empty((M, N), dtype=a.dtype, device=dev)
-    _lib.call("nr_gemm_relu_dropout", _dt(a, "a"), _dt(out, "out"), M, N, K, _ptr(a), _rowmajor(a, "a"), _ptr(w),
+    _lib.call("nr_gemm_relu_dropout", _dtype(a, "a"), _dtype(out, "out"), M, N, K, _ptr(a), _rowmajor(a, "a"), _ptr(w),
               _rowmajor(w, "w"), _ptr(bias), _ptr(out), _rowmajor(out, "out"), ctypes.c_uint64(seed & (2**64 - 1)),
               ctypes.c_float(p), _stream(dev))
     return out
@@ -519,7 +534,7 @@ def gemm_drelu(a: torch.Tensor, w: torch.Tensor, y: torch.Tensor, scale: float,
     N = w.shape[0]
     if out is None:
         out = torch.empty((M, N), dtype=y.dtype, device=dev)
-    _lib.call("nr_gemm_drelu", _dt(a, "a"), _dt(out, "out"), M, N, K, _ptr(a), _rowmajor(a, "a"), _ptr(w),
+    _lib.call("nr_gemm_drelu", _dtype(a, "a"), _dtype(out, "out"), M, N, K, _ptr(a), _rowmajor(a, "a"), _ptr(w),
               _rowmajor(w, "w"), _ptr(y), _rowmajor(y, "y"), _ptr(out), _rowmajor(out, "out"), ctypes.c_float(scale),
               _stream(dev))
     return out
@@ -539,7 +554,7 @@ def splitk_fixup(partials: torch.Tensor, out: torch.Tensor, epilogue: str = "non
     parts, rows, N = partials.shape
     if tuple(out.shape) != (rows, N):
         raise _lib.NewsRecHIPError("splitk_fixup: out must be [rows, N]")
-    _lib.call("nr_splitk_fixup", _dt(out, "out"), epi, rows, N, parts, _ptr(partials), _ptr(bias), _ptr(residual),
+    _lib.call("nr_splitk_fixup", _dtype(out, "out"), epi, rows, N, parts, _ptr(partials), _ptr(bias), _ptr(residual),
               _rowmajor(residual, "residual") if residual is not None else 0, _ptr(out), _rowmajor(out, "out"), row0,
               ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_float(p), ctypes.c_float(scale), _stream(dev))
     return out
@@ -554,8 +569,8 @@ def gather_rows(src: torch.Tensor, idx: Optional[torch.Tensor], n: Optional[int]
     dim = src.shape[1]
     if out is None:
         out = torch.empty((n, dim), dtype=out_dtype or src.dtype, device=dev)
-    _lib.call("nr_gather_rows", _dt(src, "src"), _dt(out, "out"), n, dim, _ptr(src), _rowmajor(src, "src"), _ptr(idx),
-              _ptr(out), _rowmajor(out, "out"), _stream(dev))
+    _lib.call("nr_gather_rows", _dtype(src, "src"), _dtype(out, "out"), n, dim, _ptr(src), _rowmajor(src, "src"),
+              _ptr(idx), _ptr(out), _rowmajor(out, "out"), _stream(dev))
     return out
 
 
@@ -565,7 +580,7 @@ def transpose(src: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
     rows, cols = src.shape
     if out is None:
         out = torch.empty((cols, rows), dtype=out_dtype or src.dtype, device=dev)
-    _lib.call("nr_transpose", _dt(src, "src"), _dt(out, "out"), rows, cols, _ptr(src), _rowmajor(src, "src"),
+    _lib.call("nr_transpose", _dtype(src, "src"), _dtype(out, "out"), rows, cols, _ptr(src), _rowmajor(src, "src"),
               _ptr(out), _rowmajor(out, "out"), _stream(dev))
     return out
 
@@ -575,7 +590,7 @@ def final_pool_fwd(xp: torch.Tensor, off: torch.Tensor):
     n_seg = off.numel() - 1
     users = torch.empty((n_seg, 1024), dtype=torch.float32, device=dev)
     z = torch.empty_like(users)
-    _lib.call("nr_final_pool_fwd", _dt(xp, "xp"), n_seg, _ptr(off), _ptr(xp), _rowmajor(xp, "xp"), _ptr(users),
+    _lib.call("nr_final_pool_fwd", _dtype(xp, "xp"), n_seg, _ptr(off), _ptr(xp), _rowmajor(xp, "xp"), _ptr(users),
               _ptr(z), _stream(dev))
     return users, z
 
@@ -583,7 +598,7 @@ def final_pool_fwd(xp: torch.Tensor, off: torch.Tensor):
 def final_pool_bwd(xp: torch.Tensor, off: torch.Tensor, users: torch.Tensor, z: torch.Tensor, du: torch.Tensor,
                    dx: torch.Tensor, dw: torch.Tensor) -> None:
     dev = _dev(xp, off, users, z, du, dx, dw)
-    _lib.call("nr_final_pool_bwd", _dt(xp, "xp"), off.numel() - 1, _ptr(off), dx.shape[0], _ptr(xp),
+    _lib.call("nr_final_pool_bwd", _dtype(xp, "xp"), off.numel() - 1, _ptr(off), dx.shape[0], _ptr(xp),
               _rowmajor(xp, "xp"), _ptr(users), _ptr(z), _ptr(du), _ptr(dx), _rowmajor(dx, "dx"), _ptr(dw),
               _rowmajor(dw, "dw"), _stream(dev))
 
@@ -598,20 +613,20 @@ def cosine_margin(users: torch.Tensor, E: torch.Tensor, pos: torch.Tensor, neg: 
 
 def scatter_add_rows(src: torch.Tensor, idx: torch.Tensor, dst: torch.Tensor) -> None:
     dev = _dev(src, idx, dst)
-    _lib.call("nr_scatter_add_rows", _dt(src, "src"), idx.numel(), src.shape[1], _ptr(src), _rowmajor(src, "src"),
+    _lib.call("nr_scatter_add_rows", _dtype(src, "src"), idx.numel(), src.shape[1], _ptr(src), _rowmajor(src, "src"),
               _ptr(idx), _ptr(dst), _rowmajor(dst, "dst"), _stream(dev))
 
 
 def col_sum(src: torch.Tensor, out: torch.Tensor) -> None:
     dev = _dev(src, out)
-    _lib.call("nr_col_sum", _dt(src, "src"), src.shape[0], src.shape[1], _ptr(src), _rowmajor(src, "src"), _ptr(out),
+    _lib.call("nr_col_sum", _dtype(src, "src"), src.shape[0], src.shape[1], _ptr(src), _rowmajor(src, "src"), _ptr(out),
               _stream(dev))
 
 
 def ln_param_grad(x: torch.Tensor, row_idx: Optional[torch.Tensor], eps: float, dy: torch.Tensor,
                   dgamma: torch.Tensor, dbeta: torch.Tensor) -> None:
     dev = _dev(x, row_idx, dy, dgamma, dbeta)
-    dt = {torch.float32: _lib.NR_F32, torch.bfloat16: _lib.NR_BF16, torch.float16: _lib.NR_F16}[x.dtype]
+    dt = TOKEN_DT[x.dtype]
     n = row_idx.numel() if row_idx is not None else x.shape[0]
     _lib.call("nr_ln_param_grad", dt, n, x.shape[1], _ptr(x), _rowmajor(x, "x"), _ptr(row_idx), ctypes.c_float(eps),
               _ptr(dy), _rowmajor(dy, "dy"), _ptr(dgamma), _ptr(dbeta), _stream(dev))

@@ -37,23 +37,22 @@ gradient because MyLayer discards them, attention.py:193).
 from __future__ import annotations
 
 import ctypes
+import itertools
 from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from ._lib import NewsRecHIPError
+from .ops import _pad64
 
 D = 1024
 H = 4096
 DROP_P = 0.1
 MARGIN = 2.0  # MarginRankingLoss(2), trainer.py:985
-
-
-def _pad64(n: int) -> int:
-    return max(64, (n + 63) // 64 * 64)
+_BLK = "latent.cross_attend_blocks."  # LatentAttentionModel's parameter names in the flat buffer
 
 
 @dataclass
@@ -85,100 +84,162 @@ def _check_loss_out(t: torch.Tensor, dev) -> torch.Tensor:
     return t
 
 
-def _weights_version(step) -> tuple:
-    """Version counters of everything that can write the master weights outside
-    AdamW: the flat buffer and its views (``views``), and the modules' Parameters,
-    whose ``.data`` was pointed at those views -- a Parameter keeps its own version
-    counter through ``.data =``, so load_state_dict on a wrapped module moves only
-    the Parameter's, not the flat buffer's.  AdamW (a library call through raw
-    pointers) moves neither."""
-    return (step.flat._version,) + tuple(p._version for p in step._mod_params)
+class _FlatTrainStep:
+    """What the two config-5 steps share: the token LayerNorm's and the pooler's
+    parameters adopted into one flat f32 buffer (with gradient, AdamW state and,
+    for the bf16 compute dtype, a bf16 mirror), the native step as ONE library
+    call per batch, and clip + AdamW as one more.  A subclass describes its native
+    step in the attributes below and sets the struct fields only it has (``_fill_args``)."""
 
+    _what = "train step"  # names the step in the dtype error
+    _prefix = ""          # of the pooler's parameter names in ``names``
+    _args: type           # the native step's args struct (_lib.*TrainArgs)
+    _step_fn: str         # library entry points: the step and its workspace size
+    _workspace_fn: str
+    _pmap: dict           # struct field -> parameter name (``g_`` + field is its gradient)
+    _mirrored: tuple      # the fields read in the compute dtype (``cviews``), the GEMM weights
 
-def _refresh_mirror(step) -> None:
-    """Rewrite a step's bf16 weight mirror when its master weights changed outside
-    AdamW (load_state_dict on the wrapped modules, an edit through ``views``;
-    ADVICE r4)."""
-    v = _weights_version(step)
-    if step.flat16 is not None and v != step._mirror_version:
+    def __init__(self, token_model, pooler, dtype, lr, betas, eps, weight_decay, max_norm, seed, device):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise NewsRecHIPError(f"{self._what} dtype must be float32 or bfloat16")
+        layers = list(token_model.encoder.layer)
+        if len(layers) != 1:
+            raise NewsRecHIPError("training supports NUM_HIDDEN_LAYERS == 1 (config.py:35)")
+        self.device = dev = device or torch.device("cuda")
+        self.dtype = dtype
+        self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
+        self.seed, self.step_count = seed, 0
+        self.ln = layers[0].g_mlp_layernorm
+        self.ln_eps = float(self.ln.eps)
+        self.pooler = pooler
+        named = {"ln.weight": self.ln.weight, "ln.bias": self.ln.bias,
+                 **{self._prefix + n: p for n, p in pooler.named_parameters()}}
+        self.names, self._mod_params = list(named), list(named.values())  # the modules' own Parameters
+        # every slice starts at a multiple of 64 floats, so every view is a valid GEMM operand
+        offs = list(itertools.accumulate(((p.numel() + 63) // 64 * 64 for p in self._mod_params), initial=0))
+        self.n_flat = offs[-1]
+        self.flat = torch.zeros(self.n_flat, dtype=torch.float32, device=dev)
+        self.grad, self.m, self.v = (torch.zeros_like(self.flat) for _ in range(3))
+        self.flat16 = torch.zeros_like(self.flat, dtype=torch.bfloat16) if dtype == torch.bfloat16 else None
+        views = lambda buf: {n: buf[o:o + p.numel()].view(p.shape) for (n, p), o in zip(named.items(), offs)}
+        self.views, self.gviews = views(self.flat), views(self.grad)
+        self.cviews = views(self.flat16) if self.flat16 is not None else dict(self.views)
         with torch.no_grad():
-            step.flat16.copy_(step.flat)
-    step._mirror_version = v
+            for prm, v in zip(self._mod_params, self.views.values()):
+                v.copy_(prm.detach().to(dev, torch.float32))
+                prm.data = v  # the module now reads the master weights
+            if self.flat16 is not None:
+                self.flat16.copy_(self.flat)
+        self._mirror_version = self._weights_version()
+        self.sumsq, self.loss = (torch.zeros(1, dtype=torch.float32, device=dev) for _ in range(2))
+        self._ws = None  # the native step's workspace
+        self._users = None
+
+    def _fill_args(self, a) -> None:
+        """Set the struct fields only this step has."""
+
+    def _weights_version(self) -> tuple:
+        """Version counters of everything that can write the master weights outside
+        AdamW: the flat buffer and its ``views``, and the modules' Parameters -- one
+        keeps its own counter through ``.data =``, so load_state_dict on a wrapped module
+        moves only the Parameter's.  AdamW (a call through raw pointers) moves neither."""
+        return (self.flat._version,) + tuple(p._version for p in self._mod_params)
+
+    def _refresh_mirror(self) -> None:
+        """Rewrite the bf16 weight mirror when the master weights changed outside
+        AdamW (load_state_dict on the wrapped modules, an edit through ``views``)."""
+        v = self._weights_version()
+        if self.flat16 is not None and v != self._mirror_version:
+            with torch.no_grad():
+                self.flat16.copy_(self.flat)
+        self._mirror_version = v
+
+    def forward_backward(self, batch: TrainBatch, loss_out: torch.Tensor | None = None):
+        """Loss (device scalar, written to ``loss_out`` when given) and gradients
+        into ``self.grad`` as ONE library call: the forward, the margin loss and the
+        whole backward of the batch.  The step rewrites every gradient slice, so there
+        is no ``grad.zero_()`` (the alignment gaps stay zero from construction).
+        Returns (loss, users, None): users = the pooled users [B, D] f32.  Both are
+        views of buffers the next call overwrites in place (on the stream); clone
+        them to keep a step's values."""
+        U, B, Hs = batch.tok_last.shape[0], batch.B, batch.hist_idx.numel()
+        lib = _lib.load()
+        self._refresh_mirror()
+        dt = ops.TOKEN_DT[self.dtype]
+        with torch.cuda.device(self.device):  # the native layout depends on the current device's CU count
+            need = int(getattr(lib, self._workspace_fn)(dt, B, U, Hs))
+        self._ws = ops.grow_workspace(self._ws, need, self.device)
+        if self._users is None or self._users.shape[0] < B:
+            self._users = torch.empty((B, D), dtype=torch.float32, device=self.device)
+        tok = batch.tok_last.contiguous()
+        hi, ho = batch.hist_idx.to(torch.int32).contiguous(), batch.hist_off.to(torch.int64).contiguous()
+        pos, neg = batch.pos.to(torch.int32).contiguous(), batch.neg.to(torch.int32).contiguous()
+        a = self._args()
+        a.dtype, a.tok_dtype, a.B, a.U, a.Hs, a.margin = dt, ops.TOKEN_DT[tok.dtype], B, U, Hs, MARGIN
+        self._fill_args(a)
+        a.tok_last, a.hist_idx, a.hist_off, a.pos, a.neg = (t.data_ptr() for t in (tok, hi, ho, pos, neg))
+        for f, name in self._pmap.items():
+            src = self.cviews if f in self._mirrored else self.views
+            setattr(a, f, src[name].data_ptr())
+            setattr(a, "g_" + f, self.gviews[name].data_ptr())
+        loss = self.loss if loss_out is None else _check_loss_out(loss_out, self.device)
+        a.loss, a.users, a.sumsq = loss.data_ptr(), self._users.data_ptr(), self.sumsq.data_ptr()
+        _lib.check(getattr(lib, self._step_fn)(ctypes.byref(a), self._ws.data_ptr(), self._ws.numel(),
+                                               torch.cuda.current_stream(self.device).cuda_stream), self._step_fn)
+        self._keep = (tok, hi, ho, pos, neg)  # alive until the stream has run the step
+        return loss, self._users[:B], None
+
+    def optimizer_step(self) -> None:
+        """clip_grad_norm_(max_norm) + AdamW in one launch (trainer.py:1067-1069): the
+        squared grad norm was summed by the step itself (``sumsq``), and the same
+        launch rewrites the bf16 weight mirror."""
+        self.step_count += 1
+        ops.adamw(self.flat, self.grad, self.m, self.v, self.step_count, self.lr, self.betas, self.eps, self.wd,
+                  self.max_norm, self.sumsq if self.max_norm > 0 else None, self.flat16)
+        if hasattr(self.pooler, "_hip_cache"):
+            self.pooler._hip_cache = {}  # keyed on data_ptr() and _version, which AdamW moved neither of
+
+    def step(self, batch: TrainBatch) -> torch.Tensor:
+        """One full step; returns this step's loss as its own device scalar (a
+        fresh allocation the step writes, so no copy launch)."""
+        out = torch.empty(1, dtype=torch.float32, device=self.device)
+        self.forward_backward(batch, loss_out=out)
+        self.optimizer_step()
+        return out
+
+    def grad_dict(self) -> dict:
+        return dict(self.gviews)
 
 
-class FinalAttentionTrainStep:
-    """Owns the flat parameters, AdamW state and scratch of the config-5 step."""
+class FinalAttentionTrainStep(_FlatTrainStep):
+    """The module docstring's step: ``FinalAttention`` pools (``nr_final_train_step``, csrc/final_train.hip)."""
+
+    _args, _step_fn, _workspace_fn = _lib.FinalTrainArgs, "nr_final_train_step", "nr_final_train_workspace_bytes"
+    _pmap = {"tok_g": "ln.weight", "tok_b": "ln.bias", "W5": "linear5.weight",
+             **{f"W{i}": f"linear{i}.weight" for i in range(1, 5)},
+             **{f"b{i}": f"linear{i}.bias" for i in range(1, 5)}}
+    _mirrored = ("W1", "W2", "W3", "W4", "W5")
 
     def __init__(self, token_model, final_attention, dtype: torch.dtype = torch.bfloat16, lr: float = 1e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01, max_norm: float = 0.5,
                  dropout: float = DROP_P, seed: int = 1234, device=None):
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise NewsRecHIPError("train step dtype must be float32 or bfloat16")
-        layers = list(token_model.encoder.layer)
-        if len(layers) != 1:
-            raise NewsRecHIPError("training supports NUM_HIDDEN_LAYERS == 1 (config.py:35)")
-        self.device = device or torch.device("cuda")
-        self.dtype = dtype
+        super().__init__(token_model, final_attention, dtype, lr, betas, eps, weight_decay, max_norm, seed, device)
         # CUs the persistent GEMMs spread one 256x256 tile round over (multiple of the 8 XCDs)
         self._ncu = torch.cuda.get_device_properties(self.device).multi_processor_count // 8 * 8
-        self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
         self.p = dropout
-        self.seed = seed
-        self.step_count = 0
-        self.ln = layers[0].g_mlp_layernorm
-        self.ln_eps = float(self.ln.eps)
-        fa = final_attention
-        self.names = ["ln.weight", "ln.bias"]
-        params = [self.ln.weight, self.ln.bias]
-        for i in range(1, 6):
-            lin = getattr(fa, f"linear{i}")
-            self.names.append(f"linear{i}.weight")
-            params.append(lin.weight)
-            if lin.bias is not None:
-                self.names.append(f"linear{i}.bias")
-                params.append(lin.bias)
-        sizes = [p.numel() for p in params]
-        # 16-B aligned slices (64 floats) so every view is a valid GEMM operand
-        offs, o = [], 0
-        for n in sizes:
-            offs.append(o)
-            o += (n + 63) // 64 * 64
-        self.n_flat = o
-        dev = self.device
-        self.flat = torch.zeros(o, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros_like(self.flat)
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self.flat16 = torch.zeros(o, dtype=torch.bfloat16, device=dev) if dtype == torch.bfloat16 else None
-        self.views, self.gviews, self.cviews = {}, {}, {}
-        with torch.no_grad():
-            for name, prm, off, n in zip(self.names, params, offs, sizes):
-                v = self.flat[off:off + n].view(prm.shape)
-                v.copy_(prm.detach().to(dev, torch.float32))
-                prm.data = v  # the module now reads the master weights
-                self.views[name] = v
-                self.gviews[name] = self.grad[off:off + n].view(prm.shape)
-                self.cviews[name] = (self.flat16[off:off + n].view(prm.shape) if self.flat16 is not None else v)
-            if self.flat16 is not None:
-                self.flat16.copy_(self.flat)
-        self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._ws = {}
-        self._ws_native = None
-        self._users = None
-        self._mod_params = list(params)  # the modules' Parameters (now views of flat)
-        self._mirror_version = _weights_version(self)
-        self._pmap = {"tok_g": "ln.weight", "tok_b": "ln.bias", "W5": "linear5.weight",
-                      **{f"W{i}": f"linear{i}.weight" for i in range(1, 5)},
-                      **{f"b{i}": f"linear{i}.bias" for i in range(1, 5)}}
+        self._scratch = {}  # _buf's named buffers
+
+    def _fill_args(self, a) -> None:
+        a.p = self.p
+        a.seed[:] = [self.layer_seed(layer) for layer in (1, 2, 3)]
 
     # ------------------------------------------------------------------ helpers
     def _buf(self, name: str, shape, dtype) -> torch.Tensor:
-        t = self._ws.get(name)
+        t = self._scratch.get(name)
         n = int(np.prod(shape))
         if t is None or t.numel() < n or t.dtype != dtype:
             t = torch.empty(max(n, 1), dtype=dtype, device=self.device)
-            self._ws[name] = t
+            self._scratch[name] = t
         return t[:n].view(shape)
 
     # _tail_rows / _relu_gemm: the Python driver of the split-K tail the native
@@ -234,67 +295,6 @@ class FinalAttentionTrainStep:
         """Dropout stream of one forward layer in the current step."""
         return (self.seed * 1_000_003 + self.step_count * 7919 + layer * 104_729) & (2**64 - 1)
 
-    # ------------------------------------------------------------------ step
-    def forward_backward(self, batch: TrainBatch, loss_out: torch.Tensor | None = None):
-        """Loss (device scalar, written to ``loss_out`` when given) and gradients
-        into ``self.grad`` (every slice rewritten) as ONE library call (``nr_final_train_step``, csrc/final_train.hip):
-        the forward, the margin loss and the whole backward of the batch.
-        Returns (loss, users, None): users = the pooled users [B, D] f32.  Both
-        returned tensors are views of buffers the next call overwrites in place
-        (on the stream); clone them to keep a step's values."""
-        from . import _lib
-        U, B, Hs = batch.tok_last.shape[0], batch.B, batch.hist_idx.numel()
-        lib = _lib.load()
-        self._refresh_mirror()
-        dt = _lib.NR_BF16 if self.dtype == torch.bfloat16 else _lib.NR_F32
-        with torch.cuda.device(self.device):
-            need = int(lib.nr_final_train_workspace_bytes(dt, B, U, Hs))
-        if self._ws_native is None or self._ws_native.numel() < need:
-            self._ws_native = torch.empty(need, dtype=torch.uint8, device=self.device)
-        if self._users is None or self._users.shape[0] < B:
-            self._users = torch.empty((B, D), dtype=torch.float32, device=self.device)
-        tok = batch.tok_last.contiguous()
-        tdt = {torch.float32: _lib.NR_F32, torch.bfloat16: _lib.NR_BF16, torch.float16: _lib.NR_F16}[tok.dtype]
-        hi, ho = batch.hist_idx.to(torch.int32).contiguous(), batch.hist_off.to(torch.int64).contiguous()
-        pos, neg = batch.pos.to(torch.int32).contiguous(), batch.neg.to(torch.int32).contiguous()
-        a = _lib.FinalTrainArgs()
-        a.dtype, a.tok_dtype, a.B, a.U, a.Hs, a.margin, a.p = dt, tdt, B, U, Hs, MARGIN, self.p
-        for i in range(3):
-            a.seed[i] = self.layer_seed(i + 1)
-        a.tok_last, a.hist_idx, a.hist_off, a.pos, a.neg = (tok.data_ptr(), hi.data_ptr(), ho.data_ptr(), pos.data_ptr(),
-                                                            neg.data_ptr())
-        for f, name in self._pmap.items():
-            src = self.cviews[name] if f.startswith("W") else self.views[name]
-            setattr(a, f, src.data_ptr())
-            setattr(a, "g_" + f, self.gviews[name].data_ptr())
-        loss = self.loss if loss_out is None else _check_loss_out(loss_out, self.device)
-        a.loss, a.users, a.sumsq = loss.data_ptr(), self._users.data_ptr(), self.sumsq.data_ptr()
-        _lib.check(lib.nr_final_train_step(ctypes.byref(a), self._ws_native.data_ptr(), self._ws_native.numel(),
-                                           torch.cuda.current_stream(self.device).cuda_stream), "nr_final_train_step")
-        self._keep = (tok, hi, ho, pos, neg)  # alive until the stream has run the step
-        return loss, self._users[:B], None
-
-    def _refresh_mirror(self) -> None:
-        _refresh_mirror(self)
-
-    def optimizer_step(self) -> None:
-        """clip_grad_norm_(max_norm) + AdamW (trainer.py:1067-1069): one launch; the
-        squared grad norm was summed by the step itself (``sumsq``)."""
-        self.step_count += 1
-        ops.adamw(self.flat, self.grad, self.m, self.v, self.step_count, self.lr, self.betas, self.eps, self.wd,
-                  self.max_norm, self.sumsq if self.max_norm > 0 else None, self.flat16)
-
-    def step(self, batch: TrainBatch) -> torch.Tensor:
-        """One full step; returns this step's loss as its own device scalar (a
-        fresh allocation the step writes, so no copy launch)."""
-        out = torch.empty(1, dtype=torch.float32, device=self.device)
-        self.forward_backward(batch, loss_out=out)
-        self.optimizer_step()
-        return out
-
-    def grad_dict(self) -> dict:
-        return {k: v for k, v in self.gviews.items()}
-
     def flops_per_step(self, Hs: int) -> float:
         """MFMA FLOPs of one step (forward + data-grad + weight-grad GEMMs)."""
         Hp = _pad64(Hs)
@@ -316,7 +316,7 @@ class FinalAttentionTrainStep:
         return {"adamw": 30.0 * self.n_flat, "row_kernels": float(rows)}
 
 
-class LatentAttentionTrainStep:
+class LatentAttentionTrainStep(_FlatTrainStep):
     """Config-5 step with ``LatentAttentionModel`` in the pooler slot (BASELINE
     configs[4]: "backward for encoder + latent attention"; the reference
     trainer's loop, trainer.py:1044-1069, with the latent pooler) as ONE library
@@ -333,128 +333,29 @@ class LatentAttentionTrainStep:
 
     dtype float32: exact-f32 MFMA GEMMs and f32 activations (the parity mode);
     bfloat16: bf16 operands and activations with f32 accumulation, statistics
-    and gradients, weights read from a bf16 mirror AdamW rewrites.  The
-    parameters are views of one flat f32 buffer (as in FinalAttentionTrainStep),
-    so ``state_dict()`` stays current and AdamW is one launch."""
+    and gradients, weights read from a bf16 mirror AdamW rewrites."""
+
+    _what, _prefix = "latent-attention train step", "latent."
+    _args, _step_fn, _workspace_fn = _lib.LatentTrainArgs, "nr_latent_train_step", "nr_latent_train_workspace_bytes"
+    _pmap = {"tok_g": "ln.weight", "tok_b": "ln.bias", "latents": "latent.latents",
+             "nq_g": _BLK + "0.norm.weight", "nq_b": _BLK + "0.norm.bias",
+             "nc_g": _BLK + "0.norm_context.weight", "nc_b": _BLK + "0.norm_context.bias",
+             "Wq": _BLK + "0.fn.to_q.weight", "Wkv": _BLK + "0.fn.to_kv.weight", "Wo": _BLK + "0.fn.to_out.weight",
+             "nf_g": _BLK + "1.norm.weight", "nf_b": _BLK + "1.norm.bias",
+             "W1": _BLK + "1.fn.net.0.weight", "b1": _BLK + "1.fn.net.0.bias",
+             "W2": _BLK + "1.fn.net.2.weight", "b2": _BLK + "1.fn.net.2.bias"}
+    _mirrored = ("Wq", "Wkv", "Wo", "W1", "W2")
 
     def __init__(self, token_model, latent_model, dtype: torch.dtype = torch.float32, lr: float = 1e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01, max_norm: float = 0.5,
                  seed: int = 1234, device=None):
         # (no dropout argument: LatentAttentionModel has no dropout, latent_attention.py:77-171)
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise NewsRecHIPError("latent-attention train step dtype must be float32 or bfloat16")
-        layers = list(token_model.encoder.layer)
-        if len(layers) != 1:
-            raise NewsRecHIPError("training supports NUM_HIDDEN_LAYERS == 1 (config.py:35)")
-        self.device = device or torch.device("cuda")
-        self.dtype = dtype
-        self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
-        self.seed = seed
-        self.step_count = 0
-        self.ln = layers[0].g_mlp_layernorm
-        self.ln_eps = float(self.ln.eps)
+        super().__init__(token_model, latent_model, dtype, lr, betas, eps, weight_decay, max_norm, seed, device)
+        self.model = latent_model
         if abs(self.ln_eps - 1e-12) > 1e-18:
             raise NewsRecHIPError("the token LayerNorm of MyLayer has eps 1e-12 (attention.py:155)")
-        self.model = latent_model
-        lat = list(latent_model.named_parameters())
-        self.names = ["ln.weight", "ln.bias"] + [f"latent.{n}" for n, _ in lat]
-        params = [self.ln.weight, self.ln.bias] + [p for _, p in lat]
-        offs, o = [], 0
-        for prm in params:
-            offs.append(o)
-            o += (prm.numel() + 63) // 64 * 64
-        dev = self.device
-        self.n_flat = o
-        self.flat = torch.zeros(o, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros_like(self.flat)
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self.flat16 = torch.zeros(o, dtype=torch.bfloat16, device=dev) if dtype == torch.bfloat16 else None
-        self.views, self.gviews, self.cviews = {}, {}, {}
-        with torch.no_grad():
-            for name, prm, off in zip(self.names, params, offs):
-                n = prm.numel()
-                view = self.flat[off:off + n].view(prm.shape)
-                view.copy_(prm.detach().to(dev, torch.float32))
-                prm.data = view  # the modules now read the master weights
-                self.views[name] = view
-                self.gviews[name] = self.grad[off:off + n].view(prm.shape)
-                self.cviews[name] = self.flat16[off:off + n].view(prm.shape) if self.flat16 is not None else view
-            if self.flat16 is not None:
-                self.flat16.copy_(self.flat)
-        self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._ws = None
-        self._users = None
-        self._mod_params = list(params)  # the modules' Parameters (now views of flat)
-        self._mirror_version = _weights_version(self)
-        b = "latent.cross_attend_blocks."
-        self._pmap = {"tok_g": "ln.weight", "tok_b": "ln.bias", "latents": "latent.latents",
-                      "nq_g": b + "0.norm.weight", "nq_b": b + "0.norm.bias",
-                      "nc_g": b + "0.norm_context.weight", "nc_b": b + "0.norm_context.bias",
-                      "Wq": b + "0.fn.to_q.weight", "Wkv": b + "0.fn.to_kv.weight", "Wo": b + "0.fn.to_out.weight",
-                      "nf_g": b + "1.norm.weight", "nf_b": b + "1.norm.bias",
-                      "W1": b + "1.fn.net.0.weight", "b1": b + "1.fn.net.0.bias",
-                      "W2": b + "1.fn.net.2.weight", "b2": b + "1.fn.net.2.bias"}
         if set(self._pmap.values()) != set(self.names):
             raise NewsRecHIPError(f"unexpected LatentAttentionModel parameters: {sorted(self.names)}")
-
-    def forward_backward(self, batch: TrainBatch, loss_out: torch.Tensor | None = None):
-        """Loss (device scalar, written to ``loss_out`` when given) and gradients
-        into ``self.grad`` (every slice rewritten).  Returns (loss, users, None): users = the normalized pooled
-        users [B, D].  Both are views of buffers the next call overwrites in
-        place (on the stream); clone them to keep a step's values."""
-        from . import _lib
-        U, B, Hs = batch.tok_last.shape[0], batch.B, batch.hist_idx.numel()
-        lib = _lib.load()
-        _refresh_mirror(self)
-        dt = _lib.NR_BF16 if self.dtype == torch.bfloat16 else _lib.NR_F32
-        need = int(lib.nr_latent_train_workspace_bytes(dt, B, U, Hs))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        if self._users is None or self._users.shape[0] < B:
-            self._users = torch.empty((B, D), dtype=torch.float32, device=self.device)
-        tok = batch.tok_last.contiguous()
-        tdt = {torch.float32: _lib.NR_F32, torch.bfloat16: _lib.NR_BF16, torch.float16: _lib.NR_F16}[tok.dtype]
-        hi, ho = batch.hist_idx.to(torch.int32).contiguous(), batch.hist_off.to(torch.int64).contiguous()
-        pos, neg = batch.pos.to(torch.int32).contiguous(), batch.neg.to(torch.int32).contiguous()
-        a = _lib.LatentTrainArgs()
-        a.dtype, a.tok_dtype, a.B, a.U, a.Hs, a.margin = dt, tdt, B, U, Hs, MARGIN
-        a.tok_last, a.hist_idx, a.hist_off, a.pos, a.neg = (tok.data_ptr(), hi.data_ptr(), ho.data_ptr(), pos.data_ptr(),
-                                                            neg.data_ptr())
-        for f, name in self._pmap.items():
-            src = self.cviews[name] if f in ("Wq", "Wkv", "Wo", "W1", "W2") else self.views[name]
-            setattr(a, f, src.data_ptr())
-            setattr(a, "g_" + f, self.gviews[name].data_ptr())
-        loss = self.loss if loss_out is None else _check_loss_out(loss_out, self.device)
-        a.loss, a.users, a.sumsq = loss.data_ptr(), self._users.data_ptr(), self.sumsq.data_ptr()
-        # (no grad.zero_(): the step writes every gradient and zeroes its own accumulators;
-        # the flat buffer's alignment gaps were zeroed at construction and are never written)
-        _lib.check(lib.nr_latent_train_step(ctypes.byref(a), self._ws.data_ptr(), self._ws.numel(),
-                                            torch.cuda.current_stream(self.device).cuda_stream),
-                   "nr_latent_train_step")
-        self._keep = (tok, hi, ho, pos, neg)  # alive until the stream has run the step
-        return loss, self._users[:B], None
-
-    def optimizer_step(self) -> None:
-        """clip_grad_norm_(max_norm) + AdamW in one launch (trainer.py:1067-1069): the
-        squared grad norm was summed by the step itself (``sumsq``, each stream over
-        the gradients it wrote); the bf16 mode's weight mirror is rewritten by the
-        same AdamW launch."""
-        self.step_count += 1
-        ops.adamw(self.flat, self.grad, self.m, self.v, self.step_count, self.lr, self.betas, self.eps, self.wd,
-                  self.max_norm, self.sumsq if self.max_norm > 0 else None, self.flat16)
-        if hasattr(self.model, "_hip_cache"):
-            self.model._hip_cache = {}  # the eval path's folded weights are stale now
-
-    def step(self, batch: TrainBatch) -> torch.Tensor:
-        out = torch.empty(1, dtype=torch.float32, device=self.device)
-        self.forward_backward(batch, loss_out=out)
-        self.optimizer_step()
-        return out
-
-    def grad_dict(self) -> dict:
-        return dict(self.gviews)
 
     def flops_per_step(self, Hs: int, B: int = 256) -> float:
         """MFMA FLOPs the step executes (forward, data-grad and weight-grad GEMMs,
@@ -466,14 +367,12 @@ class LatentAttentionTrainStep:
         return 3.0 * (slot + row + fold)
 
     def hbm_bytes_per_step(self, Hs: int, U: int) -> dict:
-        """Algorithmic HBM bytes of the step's non-GEMM kernels (the GEMMs are
-        priced by their FLOPs): AdamW 30 B per parameter (f32 param, grad, m, v
-        read; param, m, v written; the bf16 mirror written) and the row kernels
-        per history slot (es = 2 bf16): gather + LN_q writes S and X (2 D es);
-        segmean reads G and H1 (8192 es + D es); the GEGLU backward reads G and
-        writes dG (2 x 8192 es); the LN_f backward reads H1 and dY and writes dH1
-        (3 D es); the LN_q backward reads dX and X and adds dE in f32 (2 D es +
-        4 D) -- 32,768 es + 4 D bytes per slot -- plus the token rows read."""
+        """Algorithmic HBM bytes of the step's non-GEMM kernels: AdamW as in
+        FinalAttentionTrainStep, and the row kernels per history slot (es = 2 bf16):
+        gather + LN_q writes S and X (2 D es); segmean reads G and H1 (8192 es + D es);
+        the GEGLU backward reads G and writes dG (2 x 8192 es); the LN_f backward reads
+        H1 and dY and writes dH1 (3 D es); the LN_q backward reads dX and X and adds dE in
+        f32 (2 D es + 4 D) -- 32,768 es + 4 D bytes per slot -- plus the token rows read."""
         es = 2 if self.dtype == torch.bfloat16 else 4
         Hp = _pad64(Hs)
         per_slot = (2 * D + 8192 + D + 2 * 8192 + 3 * D + 2 * D) * es + 4 * D

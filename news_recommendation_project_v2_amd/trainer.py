@@ -120,12 +120,7 @@ class AttentionAttentionTrainer:
                 break
         if not stop:
             drain()
-        self._invalidate_eval_cache()
         return running_loss / max(running_count, 1)
-
-    def _invalidate_eval_cache(self):
-        if hasattr(self.final_attention_model, "_hip_cache"):
-            self.final_attention_model._hip_cache = {}
 
     def train(self, num_epochs: int):
         for i in range(num_epochs):
