@@ -146,7 +146,7 @@ extern "C" int nr_final_attn_transform(int dtype, int64_t n, const void* emb, in
                                        const void* W4, const float* b4, const void* W5,
                                        void* table, void* ws, int64_t ws_bytes, void* stream) {
   nr::clear_error();
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "nr_final_attn_transform: bad dtype");
+  NR_CHECK_ARG(nr::ok_dtype(dtype), "nr_final_attn_transform: bad dtype");
   NR_CHECK_ARG(n >= 0, "nr_final_attn_transform: n < 0");
   if (n == 0) return NR_OK;
   NR_CHECK_ARG(emb && W1 && b1 && W2 && b2 && W3 && b3 && W4 && b4 && W5 && table && ws,
@@ -193,7 +193,7 @@ extern "C" int nr_latent_transform(int dtype, int64_t n, const void* emb, int64_
                                    const float* b2, void* table, void* ws, int64_t ws_bytes,
                                    void* stream) {
   nr::clear_error();
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "nr_latent_transform: bad dtype");
+  NR_CHECK_ARG(nr::ok_dtype(dtype), "nr_latent_transform: bad dtype");
   NR_CHECK_ARG(n >= 0, "nr_latent_transform: n < 0");
   if (n == 0) return NR_OK;
   NR_CHECK_ARG(emb && A && Bt && W1i && b1i && W2 && b2 && table && ws,

@@ -314,6 +314,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     __bf16* __restrict__ ctx) {
   attention_body<__bf16>(qkv, cu, qoff, n_seq, ctx);
 }
+static auto attention_kernel(TypeTag<float>) { return attention_kernel_f32; }
+static auto attention_kernel(TypeTag<__bf16>) { return attention_kernel_bf16; }
 
 // ------------------------------------------------------------ whole forward
 constexpr int kPadId = 1;  // XLM-R <pad>; positions start at kPadId + 1
@@ -445,7 +447,7 @@ extern "C" int nr_encoder_forward(int dtype, int n_layers, const nr_encoder_laye
                                   float* pooled, void* hidden, int32_t* status, void* ws, int64_t ws_bytes,
                                   void* stream) {
   nr::clear_error();
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "nr_encoder_forward: bad dtype %d", dtype);
+  NR_CHECK_ARG(nr::ok_dtype(dtype), "nr_encoder_forward: bad dtype %d", dtype);
   NR_CHECK_ARG(n_layers >= 0 && (n_layers == 0 || layers), "nr_encoder_forward: bad layers");
   NR_CHECK_ARG(pool == NR_POOL_MEAN || pool == NR_POOL_LATENT || pool == NR_POOL_NONE,
                "nr_encoder_forward: bad pool %d", pool);
@@ -518,26 +520,25 @@ extern "C" int nr_embed_ln(int dtype, int64_t n_tokens, const int32_t* ids, cons
                            const void* word, const void* pos_emb, const void* type_emb, const float* gamma,
                            const float* beta, float eps, void* out, void* stream) {
   nr::clear_error();
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "nr_embed_ln: bad dtype");
+  NR_CHECK_ARG(nr::ok_dtype(dtype), "nr_embed_ln: bad dtype");
   if (n_tokens <= 0) return NR_OK;
   NR_CHECK_ARG(ids && pos && word && pos_emb && type_emb && gamma && beta && out, "nr_embed_ln: null pointer");
   NR_CHECK_DEVICE("nr_embed_ln", ids, pos, word, pos_emb, type_emb, gamma, beta, out);
   const dim3 grid((unsigned)((n_tokens + 3) / 4));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == NR_F32)
-    hipLaunchKernelGGL(nr::embed_ln_kernel<float>, grid, dim3(256), 0, s, n_tokens, ids, pos, (const float*)word,
-                       (const float*)pos_emb, (const float*)type_emb, gamma, beta, eps, (float*)out);
-  else
-    hipLaunchKernelGGL(nr::embed_ln_kernel<__bf16>, grid, dim3(256), 0, s, n_tokens, ids, pos, (const __bf16*)word,
-                       (const __bf16*)pos_emb, (const __bf16*)type_emb, gamma, beta, eps, (__bf16*)out);
-  NR_CHECK_LAUNCH("nr_embed_ln");
-  return NR_OK;
+  return nr::with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(nr::embed_ln_kernel<T>, grid, dim3(256), 0, s, n_tokens, ids, pos, (const T*)word,
+                       (const T*)pos_emb, (const T*)type_emb, gamma, beta, eps, (T*)out);
+    NR_CHECK_LAUNCH("nr_embed_ln");
+    return NR_OK;
+  });
 }
 
 extern "C" int nr_attention_varlen(int dtype, int32_t n_seq, int64_t n_qblocks, const void* qkv,
                                    const int32_t* cu_seqlens, const int32_t* qblock_off, void* ctx, void* stream) {
   nr::clear_error();
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "nr_attention_varlen: bad dtype");
+  NR_CHECK_ARG(nr::ok_dtype(dtype), "nr_attention_varlen: bad dtype");
   if (n_seq <= 0 || n_qblocks <= 0) return NR_OK;
   NR_CHECK_ARG(qkv && cu_seqlens && qblock_off && ctx, "nr_attention_varlen: null pointer");
   NR_CHECK_DEVICE("nr_attention_varlen", qkv, cu_seqlens, qblock_off, ctx);
@@ -545,12 +546,11 @@ extern "C" int nr_attention_varlen(int dtype, int32_t n_seq, int64_t n_qblocks, 
   NR_CHECK_ARG(n_qblocks <= (1 << 22) - 1, "nr_attention_varlen: too many query blocks");
   const dim3 grid((unsigned)(4 * n_qblocks));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == NR_F32)
-    hipLaunchKernelGGL(nr::attention_kernel_f32, grid, dim3(256), 0, s, (const float*)qkv, cu_seqlens,
-                       qblock_off, n_seq, (float*)ctx);
-  else
-    hipLaunchKernelGGL(nr::attention_kernel_bf16, grid, dim3(256), 0, s, (const __bf16*)qkv, cu_seqlens,
-                       qblock_off, n_seq, (__bf16*)ctx);
-  NR_CHECK_LAUNCH("nr_attention_varlen");
-  return NR_OK;
+  return nr::with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(nr::attention_kernel(t), grid, dim3(256), 0, s, (const T*)qkv, cu_seqlens, qblock_off, n_seq,
+                       (T*)ctx);
+    NR_CHECK_LAUNCH("nr_attention_varlen");
+    return NR_OK;
+  });
 }

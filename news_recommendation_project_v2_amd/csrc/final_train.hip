@@ -477,7 +477,7 @@ static int ncu_current() {
 
 constexpr const char* kFn = "nr_final_train_step";
 
-template <typename TA>
+template <typename TA, typename TT>  // activation / weight type, token-state type
 int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
   constexpr bool BF = sizeof(TA) == 2;
   const int dt = a.dtype;
@@ -532,8 +532,8 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
   {
     const int64_t g = (Hp + 3) / 4;
     const dim3 grid((unsigned)(g < 4096 ? g : 4096));
-    NR_TOK_DT(a.tok_dtype, hipLaunchKernelGGL((slots_kernel<TA, TT>), grid, dim3(256), 0, st, Hp, Hs,
-                                              (const TT*)a.tok_last, a.hist_idx, a.tok_g, a.tok_b, S, XH));
+    hipLaunchKernelGGL((slots_kernel<TA, TT>), grid, dim3(256), 0, st, Hp, Hs, (const TT*)a.tok_last, a.hist_idx, a.tok_g,
+                       a.tok_b, S, XH);
     NR_CHECK_LAUNCH("nr_final_train_step (slots)");
   }
   // relu(dropout) GEMM over Hp rows: main rows on the persistent kernel, the tail as K-slices + fixup
@@ -564,9 +564,8 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
   // ---- loss and its gradient into the pooled users and E[pos] / E[neg]
   {
     const dim3 grid((unsigned)((B + 3) / 4));
-    NR_TOK_DT(a.tok_dtype, hipLaunchKernelGGL((cos_pairs_kernel<TT>), grid, dim3(256), 0, st, B, users,
-                                              (const TT*)a.tok_last, xpair, a.tok_g, a.tok_b, a.pos, a.neg, a.margin,
-                                              lrow, du, gpair));
+    hipLaunchKernelGGL((cos_pairs_kernel<TT>), grid, dim3(256), 0, st, B, users, (const TT*)a.tok_last, xpair, a.tok_g,
+                       a.tok_b, a.pos, a.neg, a.margin, lrow, du, gpair);
   }
   NR_CHECK_LAUNCH("nr_final_train_step (cosine)");
   // the pairs' token LN grad partials (after the W1 fold's chunks) and the loss
@@ -689,7 +688,7 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
 // (the split-K tail, and so the workspace, depends on the device's CU count:
 // sized for the CURRENT device here, checked against the stream's device by the step)
 extern "C" int64_t nr_final_train_workspace_bytes(int dtype, int64_t B, int64_t U, int64_t Hs) {
-  if ((dtype != NR_F32 && dtype != NR_BF16) || B < 0 || U < 0 || Hs < 0) return -1;
+  if (!nr::ok_dtype(dtype) || B < 0 || U < 0 || Hs < 0) return -1;
   return nr::ft::layout(dtype, B, U, Hs, nr::ft::ncu_current()).total;
 }
 
@@ -717,5 +716,7 @@ extern "C" int nr_final_train_step(const nr_final_train_args* args, void* ws, in
   NR_CHECK_ARG(ws_bytes >= need, "nr_final_train_step: workspace too small (%lld < %lld)", (long long)ws_bytes,
                (long long)need);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "nr_final_train_step: workspace must be 256-byte aligned");
-  return a.dtype == NR_F32 ? nr::ft::step<float>(a, (char*)ws, s) : nr::ft::step<__bf16>(a, (char*)ws, s);
+  return nr::with_dtypes_tok(a.dtype, a.tok_dtype, [&](auto ta, auto tt) {
+    return nr::ft::step<typename decltype(ta)::type, typename decltype(tt)::type>(a, (char*)ws, s);
+  });
 }

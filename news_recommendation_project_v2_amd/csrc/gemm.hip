@@ -802,17 +802,7 @@ __global__ __launch_bounds__(512, 2) void gemm256p_group_kernel(GemmGroup g) {
 }
 
 // ---------------------------------------------------------------------------
-// Host side: from runtime codes to template arguments.
-template <typename T> struct TypeTag { using type = T; };
-
-// f(TypeTag<TI>, TypeTag<TO>) for a validated (dtype_in, dtype_out) pair.
-template <typename F>
-static int with_dtypes(int dtype_in, int dtype_out, F&& f) {
-  if (dtype_in == NR_F32)
-    return dtype_out == NR_F32 ? f(TypeTag<float>{}, TypeTag<float>{}) : f(TypeTag<float>{}, TypeTag<__bf16>{});
-  return dtype_out == NR_F32 ? f(TypeTag<__bf16>{}, TypeTag<float>{}) : f(TypeTag<__bf16>{}, TypeTag<__bf16>{});
-}
-
+// Host side: from runtime codes to template arguments (with_dtypes, with_int: nr_common.h).
 static int bad_epilogue(int epi) {
   set_error("nr_gemm: bad epilogue %d", epi);
   return NR_ERR_INVALID;
@@ -827,21 +817,8 @@ constexpr bool persistent_colsum_has(int e) { return e == NR_EPI_NONE || e == NR
 
 template <typename F>
 static int with_epilogue(int epi, F&& f) {
-  switch (epi) {
-#define NR_EPI_CASE(E) case E: return f(std::integral_constant<int, E>{});
-    NR_EPI_CASE(NR_EPI_NONE)
-    NR_EPI_CASE(NR_EPI_RELU)
-    NR_EPI_CASE(NR_EPI_EXP)
-    NR_EPI_CASE(NR_EPI_GEGLU)
-    NR_EPI_CASE(NR_EPI_RESADD)
-    NR_EPI_CASE(NR_EPI_GELU)
-    NR_EPI_CASE(NR_EPI_RELU_DROPOUT)
-    NR_EPI_CASE(NR_EPI_DRELU)
-    NR_EPI_CASE(NR_EPI_SOFTMAX64)
-    NR_EPI_CASE(NR_EPI_SOFTMAX64_BWD)
-#undef NR_EPI_CASE
-    default: return bad_epilogue(epi);
-  }
+  return with_int<NR_EPI_NONE, NR_EPI_RELU, NR_EPI_EXP, NR_EPI_GEGLU, NR_EPI_RESADD, NR_EPI_GELU, NR_EPI_RELU_DROPOUT,
+                  NR_EPI_DRELU, NR_EPI_SOFTMAX64, NR_EPI_SOFTMAX64_BWD>(epi, [&] { return bad_epilogue(epi); }, f);
 }
 
 // Appends the validated problem q to the group and advances the running tile
@@ -867,8 +844,8 @@ static bool group_push(GemmGroup& g, const GemmProblem& q, bool sq, int64_t* til
 
 int gemm_group_dispatch(int dtype_in, int dtype_out, const GemmProblem* probs, int n, hipStream_t s, float* sq_part,
                         const bool* sq, int* n_tiles, int sq_cap) {
-  NR_CHECK_ARG(dtype_in == NR_BF16 || dtype_in == NR_F32, "gemm_group: bad dtype_in %d", dtype_in);
-  NR_CHECK_ARG(dtype_out == NR_F32 || dtype_out == NR_BF16, "gemm_group: bad dtype_out %d", dtype_out);
+  NR_CHECK_ARG(ok_dtype(dtype_in), "gemm_group: bad dtype_in %d", dtype_in);
+  NR_CHECK_ARG(ok_dtype(dtype_out), "gemm_group: bad dtype_out %d", dtype_out);
   NR_CHECK_ARG(n >= 0 && n <= kGroupMax, "gemm_group: n=%d outside [0, %d]", n, kGroupMax);
   GemmGroup g{};
   int64_t tiles = 0;
@@ -908,7 +885,7 @@ int gemm_group_dispatch(int dtype_in, int dtype_out, const GemmProblem* probs, i
 // b kw.. of the same activation.  M, N multiples of 256, K of 64.
 int gemm_group_tn_dispatch(int dtype_out, const GemmProblem* probs, int n, hipStream_t s, float* sq_part,
                            const bool* sq, int* n_tiles, int sq_cap) {
-  NR_CHECK_ARG(dtype_out == NR_F32 || dtype_out == NR_BF16, "gemm_group_tn: bad dtype_out %d", dtype_out);
+  NR_CHECK_ARG(ok_dtype(dtype_out), "gemm_group_tn: bad dtype_out %d", dtype_out);
   NR_CHECK_ARG(n >= 0 && n <= kGroupMax, "gemm_group_tn: n=%d outside [0, %d]", n, kGroupMax);
   GemmGroup g{};
   int64_t tiles = 0;
@@ -932,12 +909,12 @@ int gemm_group_tn_dispatch(int dtype_out, const GemmProblem* probs, int n, hipSt
   NR_CHECK_ARG(!sq_part || tiles <= sq_cap, "gemm_group_tn: %lld workgroups exceed the %d sum-of-squares slots",
                (long long)tiles, sq_cap);
   g.sq_part = sq_part;
-  if (dtype_out == NR_F32)
-    hipLaunchKernelGGL((gemm256p_group_kernel<__bf16, float, true>), dim3((unsigned)tiles), dim3(512), 0, s, g);
-  else
-    hipLaunchKernelGGL((gemm256p_group_kernel<__bf16, __bf16, true>), dim3((unsigned)tiles), dim3(512), 0, s, g);
-  NR_CHECK_LAUNCH("gemm_group_tn");
-  return NR_OK;
+  return with_dtype(dtype_out, [&](auto to) -> int {
+    using TO = typename decltype(to)::type;
+    hipLaunchKernelGGL((gemm256p_group_kernel<__bf16, TO, true>), dim3((unsigned)tiles), dim3(512), 0, s, g);
+    NR_CHECK_LAUNCH("gemm_group_tn");
+    return NR_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1761,8 +1738,8 @@ int gemm_dispatch(int dtype_in, int dtype_out, int epi, int64_t M, int64_t N, in
 int gemm_dispatch_ex(int dtype_in, int dtype_out, int epi, int64_t M, int64_t N, int64_t K,
                      const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias,
                      const void* R, int64_t ldr, void* C, int64_t ldc, const EpiArgs& ea, hipStream_t s) {
-  NR_CHECK_ARG(dtype_in == NR_F32 || dtype_in == NR_BF16, "nr_gemm: bad dtype_in %d", dtype_in);
-  NR_CHECK_ARG(dtype_out == NR_F32 || dtype_out == NR_BF16, "nr_gemm: bad dtype_out %d", dtype_out);
+  NR_CHECK_ARG(ok_dtype(dtype_in), "nr_gemm: bad dtype_in %d", dtype_in);
+  NR_CHECK_ARG(ok_dtype(dtype_out), "nr_gemm: bad dtype_out %d", dtype_out);
   NR_CHECK_ARG(M >= 0 && N > 0 && K > 0, "nr_gemm: bad shape M=%lld N=%lld K=%lld", (long long)M, (long long)N,
                (long long)K);
   if (M == 0) return NR_OK;

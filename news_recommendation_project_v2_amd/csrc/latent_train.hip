@@ -855,7 +855,7 @@ static int grid_rows(int64_t rows, int cap = 1024) {
   return (int)(g < cap ? (g > 0 ? g : 1) : cap);
 }
 
-template <typename TA>
+template <typename TA, typename TT>  // activation / weight type, token-state type
 int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
   const int dt = a.dtype;
   const Layout L = layout(dt, a.B, a.U, a.Hs);
@@ -971,14 +971,12 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
   }
   NR_TRY_HIP(hipEventRecord(side.join, fs), kFn, "join 0 record");
   // ---- E[pos] / E[neg] rows for the head (the token LN of those news' last tokens) and their xhat
-  NR_TOK_DT(a.tok_dtype,
-            hipLaunchKernelGGL((pn_rows_kernel<TT>), dim3((unsigned)((2 * B + 3) / 4)), dim3(256), 0, st, B,
-                               (const TT*)a.tok_last, a.pos, a.neg, a.tok_g, a.tok_b, Epn, Xpn));
+  hipLaunchKernelGGL((pn_rows_kernel<TT>), dim3((unsigned)((2 * B + 3) / 4)), dim3(256), 0, st, B,
+                     (const TT*)a.tok_last, a.pos, a.neg, a.tok_g, a.tok_b, Epn, Xpn);
   NR_LT_CHECK("pos / neg rows");
   // ---- per-slot forward
-  NR_TOK_DT(a.tok_dtype,
-            hipLaunchKernelGGL((gather_ln_kernel<TA, TT>), dim3(grid_rows(Hp)), dim3(256), 0, st, Hp, a.Hs,
-                               (const TT*)a.tok_last, a.tok_g, a.tok_b, a.hist_idx, a.nq_g, a.nq_b, 1e-5f, Sx, X));
+  hipLaunchKernelGGL((gather_ln_kernel<TA, TT>), dim3(grid_rows(Hp)), dim3(256), 0, st, Hp, a.Hs,
+                     (const TT*)a.tok_last, a.tok_g, a.tok_b, a.hist_idx, a.nq_g, a.nq_b, 1e-5f, Sx, X);
   NR_LT_CHECK("gather_ln");
   NR_TRY_HIP(hipStreamWaitEvent(st, side.join, 0), kFn, "join 0");
   NR_TRY(gemm_dispatch(dt, dt, NR_EPI_SOFTMAX64, Hp, S, D, X, D, Am, D, nullptr, nullptr, 0, Pm, S, st));
@@ -1060,10 +1058,9 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
   // no gain: they slowed dS by as much, profiles/round4/train/r4s9.)
   NR_TRY(stream_fork(st, side.s2, side.fork2, kFn, "fork 2"));
   NR_TRY(gemm_dispatch(dt, dt, NR_EPI_NONE, Hp, D, S, dS, S, AT, S, nullptr, nullptr, 0, dX, D, st));
-  NR_TOK_DT(a.tok_dtype,
-            hipLaunchKernelGGL((ln_bwd_kernel<TA, 1, TT>), dim3(grid_rows(Hp, 512)), dim3(256), 0, st, Hp, a.Hs, Sx,
-                               a.tok_last, a.nq_g, 1e-5f, dX, dH1, a.hist_idx, nullptr, a.g_tok_g, a.g_tok_b,
-                               a.g_nq_g, a.g_nq_b, a.tok_g, a.tok_b));
+  hipLaunchKernelGGL((ln_bwd_kernel<TA, 1, TT>), dim3(grid_rows(Hp, 512)), dim3(256), 0, st, Hp, a.Hs, Sx, a.tok_last,
+                     a.nq_g, 1e-5f, dX, dH1, a.hist_idx, nullptr, a.g_tok_g, a.g_tok_b, a.g_nq_g, a.g_nq_b, a.tok_g,
+                     a.tok_b);
   NR_LT_CHECK("ln_q_bwd");  // (with the head's pos / neg part: the token LN's grads are final)
   {
     // this stream's gradients are all final here
@@ -1166,7 +1163,7 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
 }  // namespace nr
 
 extern "C" int64_t nr_latent_train_workspace_bytes(int dtype, int64_t B, int64_t U, int64_t Hs) {
-  if ((dtype != NR_F32 && dtype != NR_BF16) || B < 0 || U < 0 || Hs < 0) return -1;
+  if (!nr::ok_dtype(dtype) || B < 0 || U < 0 || Hs < 0) return -1;
   return nr::lt::layout(dtype, B, U, Hs).total;
 }
 
@@ -1187,5 +1184,7 @@ extern "C" int nr_latent_train_step(const nr_latent_train_args* args, void* ws, 
                (long long)need);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "nr_latent_train_step: workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  return a.dtype == NR_F32 ? nr::lt::step<float>(a, (char*)ws, s) : nr::lt::step<__bf16>(a, (char*)ws, s);
+  return nr::with_dtypes_tok(a.dtype, a.tok_dtype, [&](auto ta, auto tt) {
+    return nr::lt::step<typename decltype(ta)::type, typename decltype(tt)::type>(a, (char*)ws, s);
+  });
 }

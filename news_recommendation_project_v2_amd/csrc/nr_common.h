@@ -12,6 +12,7 @@
 #include <stdarg.h>
 
 #include <initializer_list>
+#include <type_traits>
 
 #include "../../include/newsrec.h"
 
@@ -113,6 +114,48 @@ int zero_ranges(const ZList& z, int blocks, hipStream_t s);
 // workspace sizes: row counts padded to whole 64-row tiles, byte counts to 256
 static inline int64_t pad64(int64_t n) { return n < 64 ? 64 : (n + 63) / 64 * 64; }
 static inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+
+// ---------------------------------------------------------------------------
+// Host side: from the C ABI's runtime codes to template arguments.  Every
+// launch that depends on a dtype, a row width, an epilogue or a pooler takes
+// its template arguments from one of these; each returns the int of f.
+template <typename T> struct TypeTag { using type = T; };
+
+constexpr bool ok_dtype(int code) { return code == NR_F32 || code == NR_BF16; }
+
+// Every entry point validates its codes (with its own error text) before it gets
+// here, so this is unreachable from the ABI: a code outside a helper's list
+// is an error, never a launch of some other code's kernel.
+inline int unvalidated_code(const char* what, int code) {
+  set_error("internal: %s code %d reached a launch unvalidated", what, code);
+  return NR_ERR_INVALID;
+}
+
+// f(TypeTag<float>) / f(TypeTag<__bf16>) for NR_F32 / NR_BF16
+template <typename F>
+int with_dtype(int code, F&& f) {
+  if (code == NR_F32) return f(TypeTag<float>{});
+  if (code == NR_BF16) return f(TypeTag<__bf16>{});
+  return unvalidated_code("dtype", code);
+}
+// the same with _Float16 for NR_F16: the token states' types
+template <typename F>
+int with_tok_dtype(int code, F&& f) {
+  return code == NR_F16 ? f(TypeTag<_Float16>{}) : with_dtype(code, f);
+}
+// f(TypeTag<TI>, TypeTag<TO>) for a (dtype_in, dtype_out) pair
+template <typename F>
+int with_dtypes(int dtype_in, int dtype_out, F&& f) {
+  return with_dtype(dtype_in, [&](auto ti) { return with_dtype(dtype_out, [&](auto to) { return f(ti, to); }); });
+}
+// f(std::integral_constant<int, V>) for the V of Vs... that equals v (a row width, an
+// epilogue, a pooler); miss() -- the caller's own error text and code -- when none does
+template <int... Vs, typename Miss, typename F>
+int with_int(int64_t v, Miss&& miss, F&& f) {
+  int rc = NR_OK;
+  const bool hit = ((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return hit ? rc : miss();
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

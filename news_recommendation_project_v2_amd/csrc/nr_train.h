@@ -188,12 +188,18 @@ static inline int stream_fork(hipStream_t from, hipStream_t to, hipEvent_t ev, c
 
 // the argument checks nr_final_train_step and nr_latent_train_step share
 static inline int check_step_args(const char* fn, int dtype, int tok_dtype, int64_t B, int64_t U, int64_t Hs) {
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "%s: dtype must be NR_F32 or NR_BF16", fn);
+  NR_CHECK_ARG(ok_dtype(dtype), "%s: dtype must be NR_F32 or NR_BF16", fn);
   NR_CHECK_ARG(tok_dtype == NR_F32 || tok_dtype == NR_BF16 || tok_dtype == NR_F16, "%s: bad tok_dtype", fn);
   NR_CHECK_ARG(B >= 1 && U >= 1 && Hs >= 1, "%s: empty batch (B=%lld U=%lld Hs=%lld)", fn, (long long)B, (long long)U,
                (long long)Hs);
   NR_CHECK_ARG(Hs <= (1ll << 31) - 1024 && U <= (1ll << 31) && B <= (1ll << 24), "%s: batch too large", fn);
   return NR_OK;
+}
+
+// f(TypeTag<TA>, TypeTag<TT>): a step's activation / weight type and its token states' type
+template <typename F>
+int with_dtypes_tok(int dtype, int tok_dtype, F&& f) {
+  return with_dtype(dtype, [&](auto ta) { return with_tok_dtype(tok_dtype, [&](auto tt) { return f(ta, tt); }); });
 }
 
 }  // namespace nr
@@ -210,12 +216,4 @@ static inline int check_step_args(const char* fn, int dtype, int tok_dtype, int6
       nr::set_error("%s: %s failed", fn, what); \
       return NR_ERR_HIP;                        \
     }                                           \
-  } while (0)
-
-// the token states' type (f32 / bf16 / f16) as TT
-#define NR_TOK_DT(tok_dtype, ...)                                      \
-  do {                                                                 \
-    if ((tok_dtype) == NR_F32) { typedef float TT; __VA_ARGS__; }      \
-    else if ((tok_dtype) == NR_BF16) { typedef __bf16 TT; __VA_ARGS__; } \
-    else { typedef _Float16 TT; __VA_ARGS__; }                        \
   } while (0)

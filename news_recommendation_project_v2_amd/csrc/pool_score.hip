@@ -272,14 +272,14 @@ static int launch_pool_score(const void* ht, int64_t hld, const void* ct, int64_
 int pool_rows_dispatch(int pooler, int dtype, const void* table, int64_t ld, const int64_t* off, int64_t n_seg,
                        float* users, hipStream_t s) {
   if (n_seg == 0) return NR_OK;
-  if (dtype == NR_F32) {
-    if (pooler == NR_POOL_MEAN)
-      return launch_pool_score<float, NR_POOL_MEAN>(table, ld, table, ld, nullptr, nullptr, off, nullptr, nullptr, n_seg, nullptr, users, s);
-    return launch_pool_score<float, NR_POOL_LATENT>(table, ld, table, ld, nullptr, nullptr, off, nullptr, nullptr, n_seg, nullptr, users, s);
-  }
-  if (pooler == NR_POOL_MEAN)
-    return launch_pool_score<__bf16, NR_POOL_MEAN>(table, ld, table, ld, nullptr, nullptr, off, nullptr, nullptr, n_seg, nullptr, users, s);
-  return launch_pool_score<__bf16, NR_POOL_LATENT>(table, ld, table, ld, nullptr, nullptr, off, nullptr, nullptr, n_seg, nullptr, users, s);
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    const auto miss = [&] { return unvalidated_code("pooler", pooler); };
+    return with_int<NR_POOL_MEAN, NR_POOL_LATENT>(pooler, miss, [&](auto pool) -> int {
+      return launch_pool_score<T, decltype(pool)::value>(table, ld, table, ld, nullptr, nullptr, off, nullptr, nullptr,
+                                                         n_seg, nullptr, users, s);
+    });
+  });
 }
 
 }  // namespace nr
@@ -297,7 +297,7 @@ extern "C" int nr_pool_score(int pooler, int dtype, int64_t dim, const void* his
   }
   NR_CHECK_ARG(pooler == NR_POOL_FINAL || pooler == NR_POOL_LATENT || pooler == NR_POOL_MEAN,
                "nr_pool_score: bad pooler %d", pooler);
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "nr_pool_score: bad dtype %d", dtype);
+  NR_CHECK_ARG(nr::ok_dtype(dtype), "nr_pool_score: bad dtype %d", dtype);
   NR_CHECK_ARG(n_imp >= 0, "nr_pool_score: n_imp < 0");
   if (n_imp == 0) return NR_OK;
   const bool score = cand_off != nullptr;
@@ -316,19 +316,15 @@ extern "C" int nr_pool_score(int pooler, int dtype, int64_t dim, const void* his
                    ((uintptr_t)hist_table & 15) == 0 && ((uintptr_t)cand_table & 15) == 0,
                "nr_pool_score: tables must be 16-byte aligned with 16-byte row strides");
   hipStream_t s = (hipStream_t)stream;
-  if (pooler == NR_POOL_MEAN) {
-    if (dtype == NR_F32)
-      return nr::launch_pool_score<float, NR_POOL_MEAN>(hist_table, hist_ld, cand_table, cand_ld, cand_inv_norm, hist_idx, hist_off, cand_idx, cand_off, n_imp, scores, users, s);
-    return nr::launch_pool_score<__bf16, NR_POOL_MEAN>(hist_table, hist_ld, cand_table, cand_ld, cand_inv_norm, hist_idx, hist_off, cand_idx, cand_off, n_imp, scores, users, s);
-  }
-  if (dtype == NR_F32) {
-    if (pooler == NR_POOL_FINAL)
-      return nr::launch_pool_score<float, NR_POOL_FINAL>(hist_table, hist_ld, cand_table, cand_ld, cand_inv_norm, hist_idx, hist_off, cand_idx, cand_off, n_imp, scores, users, s);
-    return nr::launch_pool_score<float, NR_POOL_LATENT>(hist_table, hist_ld, cand_table, cand_ld, cand_inv_norm, hist_idx, hist_off, cand_idx, cand_off, n_imp, scores, users, s);
-  }
-  if (pooler == NR_POOL_FINAL)
-    return nr::launch_pool_score<__bf16, NR_POOL_FINAL>(hist_table, hist_ld, cand_table, cand_ld, cand_inv_norm, hist_idx, hist_off, cand_idx, cand_off, n_imp, scores, users, s);
-  return nr::launch_pool_score<__bf16, NR_POOL_LATENT>(hist_table, hist_ld, cand_table, cand_ld, cand_inv_norm, hist_idx, hist_off, cand_idx, cand_off, n_imp, scores, users, s);
+  return nr::with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    const auto miss = [&] { return nr::unvalidated_code("pooler", pooler); };
+    return nr::with_int<NR_POOL_MEAN, NR_POOL_FINAL, NR_POOL_LATENT>(pooler, miss, [&](auto pool) -> int {
+      return nr::launch_pool_score<T, decltype(pool)::value>(hist_table, hist_ld, cand_table, cand_ld, cand_inv_norm,
+                                                             hist_idx, hist_off, cand_idx, cand_off, n_imp, scores,
+                                                             users, s);
+    });
+  });
 }
 
 extern "C" int nr_score_users(int dtype, int64_t dim, const float* users, const int32_t* user_idx,
@@ -340,7 +336,7 @@ extern "C" int nr_score_users(int dtype, int64_t dim, const float* users, const 
     nr::set_error("nr_score_users: dim %lld unsupported (1024 only)", (long long)dim);
     return NR_ERR_UNSUPPORTED;
   }
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "nr_score_users: bad dtype %d", dtype);
+  NR_CHECK_ARG(nr::ok_dtype(dtype), "nr_score_users: bad dtype %d", dtype);
   NR_CHECK_ARG(n_imp >= 0, "nr_score_users: n_imp < 0");
   if (n_imp == 0) return NR_OK;
   NR_CHECK_ARG(users && user_idx && cand_table && cand_inv_norm && cand_idx && cand_off && scores,
@@ -350,11 +346,10 @@ extern "C" int nr_score_users(int dtype, int64_t dim, const float* users, const 
                "nr_score_users: cand_table must be 16-byte aligned with 16-byte row strides");
   hipStream_t s = (hipStream_t)stream;
   // the pooler only shaped the stored user vectors; the scoring pass is pooler-independent
-  if (dtype == NR_F32)
-    return nr::launch_pool_score<float, NR_POOL_MEAN, true>(nullptr, 0, cand_table, cand_ld, cand_inv_norm, nullptr,
-                                                            nullptr, cand_idx, cand_off, n_imp, scores,
-                                                            const_cast<float*>(users), s, user_idx);
-  return nr::launch_pool_score<__bf16, NR_POOL_MEAN, true>(nullptr, 0, cand_table, cand_ld, cand_inv_norm, nullptr,
-                                                           nullptr, cand_idx, cand_off, n_imp, scores,
-                                                           const_cast<float*>(users), s, user_idx);
+  return nr::with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    return nr::launch_pool_score<T, NR_POOL_MEAN, true>(nullptr, 0, cand_table, cand_ld, cand_inv_norm, nullptr,
+                                                        nullptr, cand_idx, cand_off, n_imp, scores,
+                                                        const_cast<float*>(users), s, user_idx);
+  });
 }

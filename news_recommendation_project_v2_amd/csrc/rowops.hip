@@ -147,88 +147,72 @@ __global__ __launch_bounds__(256) void inv_norm_kernel(int64_t rows, const T* __
   if (lane == 0) out[row] = 1.0f / fmaxf(sqrtf(q), eps);
 }
 
-template <typename TI, typename TO>
-static int launch_ln(int64_t rows, int64_t dim, const void* x, int64_t ldx, const float* g,
-                     const float* b, float eps, void* y, int64_t ldy, hipStream_t s) {
-  const int64_t nb = (rows + 3) / 4;
-  constexpr int64_t cap = 1024;  // grid cap (measured best for bf16 at 72k rows)
-  const dim3 grid((unsigned)(cap > 0 && nb > cap ? cap : nb));  // rows grid-strided over <= cap blocks
-#define NR_LN_CASE(D)                                                                      \
-  case D:                                                                                  \
-    hipLaunchKernelGGL((layernorm_kernel<TI, TO, D>), grid, dim3(256), 0, s, rows,        \
-                       (const TI*)x, ldx, g, b, eps, (TO*)y, ldy);                          \
-    break;
-  switch (dim) {
-    NR_LN_CASE(256) NR_LN_CASE(512) NR_LN_CASE(768) NR_LN_CASE(1024) NR_LN_CASE(2048)
-    default: set_error("nr_layernorm: dim %lld unsupported", (long long)dim); return NR_ERR_UNSUPPORTED;
-  }
-#undef NR_LN_CASE
-  NR_CHECK_LAUNCH("nr_layernorm");
-  return NR_OK;
+// the miss path of the row-width dispatch (with_int) of entry point fn
+static int dim_unsupported(const char* fn, int64_t dim, int rc) {
+  set_error("%s: dim %lld unsupported", fn, (long long)dim);
+  return rc;
 }
 
 int layernorm_dispatch(int dti, int dto, int64_t rows, int64_t dim, const void* x, int64_t ldx,
                        const float* g, const float* b, float eps, void* y, int64_t ldy,
                        hipStream_t s) {
-  NR_CHECK_ARG((dti == NR_F32 || dti == NR_BF16) && (dto == NR_F32 || dto == NR_BF16), "nr_layernorm: bad dtype");
+  NR_CHECK_ARG(ok_dtype(dti) && ok_dtype(dto), "nr_layernorm: bad dtype");
   NR_CHECK_ARG(rows >= 0 && ldx >= dim && ldy >= dim, "nr_layernorm: bad strides");
   NR_CHECK_ARG((ldx * (dti == NR_F32 ? 4 : 2)) % 16 == 0 && (ldy * (dto == NR_F32 ? 4 : 2)) % 16 == 0 &&
                    ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0,
                "nr_layernorm: rows must be 16-byte aligned");
   if (rows == 0) return NR_OK;
   NR_CHECK_ARG(x && y, "nr_layernorm: null pointer");
-  if (dti == NR_F32) {
-    if (dto == NR_F32) return launch_ln<float, float>(rows, dim, x, ldx, g, b, eps, y, ldy, s);
-    return launch_ln<float, __bf16>(rows, dim, x, ldx, g, b, eps, y, ldy, s);
-  }
-  if (dto == NR_F32) return launch_ln<__bf16, float>(rows, dim, x, ldx, g, b, eps, y, ldy, s);
-  return launch_ln<__bf16, __bf16>(rows, dim, x, ldx, g, b, eps, y, ldy, s);
+  const int64_t nb = (rows + 3) / 4;
+  constexpr int64_t cap = 1024;  // grid cap (measured best for bf16 at 72k rows)
+  const dim3 grid((unsigned)(cap > 0 && nb > cap ? cap : nb));  // rows grid-strided over <= cap blocks
+  const auto miss = [&] { return dim_unsupported("nr_layernorm", dim, NR_ERR_UNSUPPORTED); };
+  return with_dtypes(dti, dto, [&](auto ti, auto to) -> int {
+    using TI = typename decltype(ti)::type;
+    using TO = typename decltype(to)::type;
+    return with_int<256, 512, 768, 1024, 2048>(dim, miss, [&](auto d) -> int {
+      hipLaunchKernelGGL((layernorm_kernel<TI, TO, decltype(d)::value>), grid, dim3(256), 0, s, rows, (const TI*)x,
+                         ldx, g, b, eps, (TO*)y, ldy);
+      NR_CHECK_LAUNCH("nr_layernorm");
+      return NR_OK;
+    });
+  });
 }
 
 int softmax64_dispatch(int64_t rows, int64_t groups, const float* x, int64_t ldx, int dto, void* y,
                        int64_t ldy, hipStream_t s) {
   NR_CHECK_ARG(rows >= 0 && groups > 0 && ldx >= groups * 64 && ldy >= groups * 64, "nr_softmax64: bad shape");
-  NR_CHECK_ARG(dto == NR_F32 || dto == NR_BF16, "nr_softmax64: bad dtype");
+  NR_CHECK_ARG(ok_dtype(dto), "nr_softmax64: bad dtype");
   if (rows == 0) return NR_OK;
   NR_CHECK_ARG(x && y, "nr_softmax64: null pointer");
   const int64_t items = rows * groups;
   const dim3 grid((unsigned)((items + 3) / 4));
-  if (dto == NR_F32)
-    hipLaunchKernelGGL((softmax64_kernel<float>), grid, dim3(256), 0, s, items, groups, x, ldx, (float*)y, ldy);
-  else
-    hipLaunchKernelGGL((softmax64_kernel<__bf16>), grid, dim3(256), 0, s, items, groups, x, ldx, (__bf16*)y, ldy);
-  NR_CHECK_LAUNCH("nr_softmax64");
-  return NR_OK;
+  return with_dtype(dto, [&](auto to) -> int {
+    using TO = typename decltype(to)::type;
+    hipLaunchKernelGGL((softmax64_kernel<TO>), grid, dim3(256), 0, s, items, groups, x, ldx, (TO*)y, ldy);
+    NR_CHECK_LAUNCH("nr_softmax64");
+    return NR_OK;
+  });
 }
 
 int inv_norm_dispatch(int dtype, int64_t rows, int64_t dim, const void* x, int64_t ldx, float eps,
                       float* out, hipStream_t s) {
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "nr_row_inv_norm: bad dtype");
+  NR_CHECK_ARG(ok_dtype(dtype), "nr_row_inv_norm: bad dtype");
   NR_CHECK_ARG(rows >= 0 && ldx >= dim && ldx % 4 == 0, "nr_row_inv_norm: bad strides");
   if (rows == 0) return NR_OK;
   NR_CHECK_ARG(x && out, "nr_row_inv_norm: null pointer");
   const dim3 grid((unsigned)((rows + 3) / 4));
-#define NR_IN_CASE(T, D)                                                                        \
-  case D:                                                                                       \
-    hipLaunchKernelGGL((inv_norm_kernel<T, D>), grid, dim3(256), 0, s, rows, (const T*)x, ldx,  \
-                       eps, out);                                                               \
-    break;
-  if (dtype == NR_F32) {
-    switch (dim) {
-      NR_IN_CASE(float, 256) NR_IN_CASE(float, 512) NR_IN_CASE(float, 768) NR_IN_CASE(float, 1024) NR_IN_CASE(float, 2048)
-      default: set_error("nr_row_inv_norm: dim %lld unsupported", (long long)dim); return NR_ERR_UNSUPPORTED;
-    }
-  } else {
-    switch (dim) {
-      NR_IN_CASE(__bf16, 256) NR_IN_CASE(__bf16, 512) NR_IN_CASE(__bf16, 768) NR_IN_CASE(__bf16, 1024) NR_IN_CASE(__bf16, 2048)
-      default: set_error("nr_row_inv_norm: dim %lld unsupported", (long long)dim); return NR_ERR_UNSUPPORTED;
-    }
-  }
-#undef NR_IN_CASE
-  NR_CHECK_LAUNCH("nr_row_inv_norm");
-  return NR_OK;
+  const auto miss = [&] { return dim_unsupported("nr_row_inv_norm", dim, NR_ERR_UNSUPPORTED); };
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    return with_int<256, 512, 768, 1024, 2048>(dim, miss, [&](auto d) -> int {
+      hipLaunchKernelGGL((inv_norm_kernel<T, decltype(d)::value>), grid, dim3(256), 0, s, rows, (const T*)x, ldx,
+                         eps, out);
+      NR_CHECK_LAUNCH("nr_row_inv_norm");
+      return NR_OK;
+    });
+  });
 }
-
 
 // Gathered chain of LayerNorms: out[i] = LN_{n-1}(...LN_0(x[row_idx[i]])...),
 // f32 math and output.  The token-attention encoder's effective forward
@@ -273,27 +257,22 @@ int gather_ln_dispatch(int dti, int64_t n, int64_t dim, const void* x, int64_t l
                "nr_gather_layernorm: bad shape/strides");
   if (n == 0) return NR_OK;
   NR_CHECK_ARG(x && y, "nr_gather_layernorm: null pointer");
-  NR_CHECK_ARG(dim == 1024 || dim == 512 || dim == 2048 || dim == 256, "nr_gather_layernorm: dim %lld unsupported",
-               (long long)dim);
   const dim3 grid((unsigned)((n + 3) / 4));
-#define NR_GL(T, D)                                                                                   \
-  if (dim == D) {                                                                                     \
-    hipLaunchKernelGGL((gather_ln_kernel<T, D>), grid, dim3(256), 0, s, n, (const T*)x, ldx, row_idx, \
-                       n_ln, g, b, eps, y, ldy);                                                      \
-  }
-#define NR_GL_ALL(T) NR_GL(T, 256) NR_GL(T, 512) NR_GL(T, 1024) NR_GL(T, 2048)
-  if (dti == NR_F32) { NR_GL_ALL(float) }
-  else if (dti == NR_BF16) { NR_GL_ALL(__bf16) }
-  else { NR_GL_ALL(_Float16) }
-#undef NR_GL_ALL
-#undef NR_GL
-  NR_CHECK_LAUNCH("nr_gather_layernorm");
-  return NR_OK;
+  const auto miss = [&] { return dim_unsupported("nr_gather_layernorm", dim, NR_ERR_INVALID); };
+  return with_tok_dtype(dti, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    return with_int<256, 512, 1024, 2048>(dim, miss, [&](auto d) -> int {
+      hipLaunchKernelGGL((gather_ln_kernel<T, decltype(d)::value>), grid, dim3(256), 0, s, n, (const T*)x, ldx,
+                         row_idx, n_ln, g, b, eps, y, ldy);
+      NR_CHECK_LAUNCH("nr_gather_layernorm");
+      return NR_OK;
+    });
+  });
 }
 
 int row_stats_dispatch(int dtype, int64_t rows, int64_t dim, const void* x, int64_t ldx, float eps, float* out,
                        hipStream_t s) {
-  NR_CHECK_ARG(dtype == NR_F32 || dtype == NR_BF16, "nr_row_stats: bad dtype");
+  NR_CHECK_ARG(ok_dtype(dtype), "nr_row_stats: bad dtype");
   NR_CHECK_ARG(dim == 1024, "nr_row_stats: dim %lld unsupported (1024 only)", (long long)dim);
   NR_CHECK_ARG(rows >= 0 && ldx >= dim && (ldx * (dtype == NR_F32 ? 4 : 2)) % 16 == 0 && ((uintptr_t)x & 15) == 0 &&
                    ((uintptr_t)out & 7) == 0,
@@ -302,14 +281,12 @@ int row_stats_dispatch(int dtype, int64_t rows, int64_t dim, const void* x, int6
   NR_CHECK_ARG(x && out, "nr_row_stats: null pointer");
   const int64_t nb = (rows + 3) / 4;
   const dim3 grid((unsigned)(nb > 2048 ? 2048 : nb));
-  if (dtype == NR_F32)
-    hipLaunchKernelGGL((row_stats_kernel<float, 1024>), grid, dim3(256), 0, s, rows, (const float*)x, ldx, eps,
-                       (float2*)out);
-  else
-    hipLaunchKernelGGL((row_stats_kernel<__bf16, 1024>), grid, dim3(256), 0, s, rows, (const __bf16*)x, ldx, eps,
-                       (float2*)out);
-  NR_CHECK_LAUNCH("nr_row_stats");
-  return NR_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((row_stats_kernel<T, 1024>), grid, dim3(256), 0, s, rows, (const T*)x, ldx, eps, (float2*)out);
+    NR_CHECK_LAUNCH("nr_row_stats");
+    return NR_OK;
+  });
 }
 
 }  // namespace nr

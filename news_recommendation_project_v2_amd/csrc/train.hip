@@ -554,13 +554,6 @@ int train_side_streams(hipStream_t st, const char* fn, TrainSide& out) {
 
 using namespace nr;
 
-#define NR_DT2(dti, dto, ...)                                                              \
-  do {                                                                                     \
-    if (dti == NR_F32 && dto == NR_F32) { typedef float TI; typedef float TO; __VA_ARGS__; } \
-    else if (dti == NR_F32) { typedef float TI; typedef __bf16 TO; __VA_ARGS__; }           \
-    else if (dto == NR_F32) { typedef __bf16 TI; typedef float TO; __VA_ARGS__; }           \
-    else { typedef __bf16 TI; typedef __bf16 TO; __VA_ARGS__; }                            \
-  } while (0)
 // ----------------------------------------------------------------- split-K fixup
 // C[r][c] = epi(sum_s P[s][r][c] + bias[c]) for the rows of a GEMM that were
 // computed as `parts` K-slices (nr_gemm_grouped, f32 partials), with the
@@ -591,32 +584,28 @@ __global__ __launch_bounds__(256) void splitk_fixup_kernel(int64_t rows, int64_t
   }
 }
 
-#define NR_DT1(dt, ...)                                       \
-  do {                                                        \
-    if (dt == NR_F32) { typedef float T; __VA_ARGS__; }       \
-    else { typedef __bf16 T; __VA_ARGS__; }                   \
-  } while (0)
-#define NR_OKDT(d) ((d) == NR_F32 || (d) == NR_BF16)
-
 extern "C" int nr_gather_rows(int dtype_in, int dtype_out, int64_t n, int64_t dim, const void* src, int64_t lds,
                               const int32_t* idx, void* dst, int64_t ldd, void* stream) {
   clear_error();
-  NR_CHECK_ARG(NR_OKDT(dtype_in) && NR_OKDT(dtype_out), "nr_gather_rows: bad dtype");
+  NR_CHECK_ARG(ok_dtype(dtype_in) && ok_dtype(dtype_out), "nr_gather_rows: bad dtype");
   NR_CHECK_ARG(n >= 0 && dim > 0 && lds >= dim && ldd >= dim, "nr_gather_rows: bad shape");
   if (n == 0) return NR_OK;
   NR_CHECK_ARG(src && dst, "nr_gather_rows: null pointer");
   NR_CHECK_DEVICE("nr_gather_rows", src, idx, dst);
-  NR_DT2(dtype_in, dtype_out,
-         hipLaunchKernelGGL((gather_rows_kernel<TI, TO>), dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, n,
-                            dim, (const TI*)src, lds, idx, (TO*)dst, ldd));
-  NR_CHECK_LAUNCH("nr_gather_rows");
-  return NR_OK;
+  return with_dtypes(dtype_in, dtype_out, [&](auto ti, auto to) -> int {
+    using TI = typename decltype(ti)::type;
+    using TO = typename decltype(to)::type;
+    hipLaunchKernelGGL((gather_rows_kernel<TI, TO>), dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, n, dim,
+                       (const TI*)src, lds, idx, (TO*)dst, ldd);
+    NR_CHECK_LAUNCH("nr_gather_rows");
+    return NR_OK;
+  });
 }
 
 extern "C" int nr_transpose(int dtype_in, int dtype_out, int64_t rows, int64_t cols, const void* src, int64_t lds,
                             void* dst, int64_t ldd, void* stream) {
   clear_error();
-  NR_CHECK_ARG(NR_OKDT(dtype_in) && NR_OKDT(dtype_out), "nr_transpose: bad dtype");
+  NR_CHECK_ARG(ok_dtype(dtype_in) && ok_dtype(dtype_out), "nr_transpose: bad dtype");
   NR_CHECK_ARG(rows >= 0 && cols >= 0 && lds >= cols && ldd >= rows, "nr_transpose: bad shape");
   if (rows == 0 || cols == 0) return NR_OK;
   NR_CHECK_ARG(src && dst, "nr_transpose: null pointer");
@@ -638,32 +627,38 @@ extern "C" int nr_transpose(int dtype_in, int dtype_out, int64_t rows, int64_t c
     NR_CHECK_LAUNCH("nr_transpose");
     return NR_OK;
   }
-  NR_DT2(dtype_in, dtype_out,
-         hipLaunchKernelGGL((transpose_kernel<TI, TO>), grid, dim3(256), 0, (hipStream_t)stream, rows, cols,
-                            (const TI*)src, lds, (TO*)dst, ldd));
-  NR_CHECK_LAUNCH("nr_transpose");
-  return NR_OK;
+  return with_dtypes(dtype_in, dtype_out, [&](auto ti, auto to) -> int {
+    using TI = typename decltype(ti)::type;
+    using TO = typename decltype(to)::type;
+    hipLaunchKernelGGL((transpose_kernel<TI, TO>), grid, dim3(256), 0, (hipStream_t)stream, rows, cols,
+                       (const TI*)src, lds, (TO*)dst, ldd);
+    NR_CHECK_LAUNCH("nr_transpose");
+    return NR_OK;
+  });
 }
 
 extern "C" int nr_final_pool_fwd(int dtype, int64_t n_seg, const int64_t* off, const void* xp, int64_t ld,
                                  float* users, float* z, void* stream) {
   clear_error();
-  NR_CHECK_ARG(NR_OKDT(dtype) && n_seg >= 0 && ld >= 2048, "nr_final_pool_fwd: bad args");
+  NR_CHECK_ARG(ok_dtype(dtype) && n_seg >= 0 && ld >= 2048, "nr_final_pool_fwd: bad args");
   if (n_seg == 0) return NR_OK;
   NR_CHECK_ARG(off && xp && users && z, "nr_final_pool_fwd: null pointer");
   NR_CHECK_DEVICE("nr_final_pool_fwd", off, xp, users, z);
   NR_CHECK_ARG(((uintptr_t)xp & 15) == 0 && ld % 4 == 0, "nr_final_pool_fwd: xp must be 16-byte aligned, ld %% 4 == 0");
-  NR_DT1(dtype, hipLaunchKernelGGL((final_pool_fwd_kernel<T>), dim3((unsigned)n_seg, 4), dim3(64 * kPoolWaves), 0,
-                                   (hipStream_t)stream, n_seg, off, (const T*)xp, ld, users, z));
-  NR_CHECK_LAUNCH("nr_final_pool_fwd");
-  return NR_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((final_pool_fwd_kernel<T>), dim3((unsigned)n_seg, 4), dim3(64 * kPoolWaves), 0,
+                       (hipStream_t)stream, n_seg, off, (const T*)xp, ld, users, z);
+    NR_CHECK_LAUNCH("nr_final_pool_fwd");
+    return NR_OK;
+  });
 }
 
 extern "C" int nr_final_pool_bwd(int dtype, int64_t n_seg, const int64_t* off, int64_t n_rows, const void* xp,
                                  int64_t ld, const float* users, const float* z, const float* du, void* dx,
                                  int64_t lddx, void* dl, int64_t lddl, void* stream) {
   clear_error();
-  NR_CHECK_ARG(NR_OKDT(dtype) && n_seg >= 0 && n_rows >= 0 && ld >= 2048 && lddx >= 1024 && lddl >= 1024,
+  NR_CHECK_ARG(ok_dtype(dtype) && n_seg >= 0 && n_rows >= 0 && ld >= 2048 && lddx >= 1024 && lddl >= 1024,
                "nr_final_pool_bwd: bad args");
   if (n_seg == 0 && n_rows == 0) return NR_OK;
   NR_CHECK_ARG(off && xp && users && z && du && dx && dl, "nr_final_pool_bwd: null pointer");
@@ -674,10 +669,13 @@ extern "C" int nr_final_pool_bwd(int dtype, int64_t n_seg, const int64_t* off, i
   if (n_rows == 0) return NR_OK;
   NR_CHECK_ARG((n_rows + 15) / 16 <= 0x7fffffff, "nr_final_pool_bwd: too many rows");
   const unsigned grid = (unsigned)((n_rows + 15) / 16);  // 16 rows per block
-  NR_DT1(dtype, hipLaunchKernelGGL((final_pool_bwd_kernel<T>), dim3(grid, 4), dim3(256), 0, (hipStream_t)stream,
-                                   n_seg, off, n_rows, (const T*)xp, ld, users, z, du, (T*)dx, lddx, (T*)dl, lddl));
-  NR_CHECK_LAUNCH("nr_final_pool_bwd");
-  return NR_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((final_pool_bwd_kernel<T>), dim3(grid, 4), dim3(256), 0, (hipStream_t)stream, n_seg, off, n_rows,
+                       (const T*)xp, ld, users, z, du, (T*)dx, lddx, (T*)dl, lddl);
+    NR_CHECK_LAUNCH("nr_final_pool_bwd");
+    return NR_OK;
+  });
 }
 
 extern "C" int nr_cosine_margin(int64_t B, const float* users, const float* E, int64_t lde, const int32_t* pos,
@@ -697,20 +695,23 @@ extern "C" int nr_cosine_margin(int64_t B, const float* users, const float* E, i
 extern "C" int nr_scatter_add_rows(int dtype, int64_t n, int64_t dim, const void* src, int64_t lds,
                                    const int32_t* idx, float* dst, int64_t ldd, void* stream) {
   clear_error();
-  NR_CHECK_ARG(NR_OKDT(dtype) && n >= 0 && dim > 0 && lds >= dim && ldd >= dim, "nr_scatter_add_rows: bad args");
+  NR_CHECK_ARG(ok_dtype(dtype) && n >= 0 && dim > 0 && lds >= dim && ldd >= dim, "nr_scatter_add_rows: bad args");
   if (n == 0) return NR_OK;
   NR_CHECK_ARG(src && idx && dst, "nr_scatter_add_rows: null pointer");
   NR_CHECK_DEVICE("nr_scatter_add_rows", src, idx, dst);
-  NR_DT1(dtype, hipLaunchKernelGGL((scatter_add_rows_kernel<T>), dim3((unsigned)n), dim3(256), 0,
-                                   (hipStream_t)stream, n, dim, (const T*)src, lds, idx, dst, ldd));
-  NR_CHECK_LAUNCH("nr_scatter_add_rows");
-  return NR_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((scatter_add_rows_kernel<T>), dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, n, dim,
+                       (const T*)src, lds, idx, dst, ldd);
+    NR_CHECK_LAUNCH("nr_scatter_add_rows");
+    return NR_OK;
+  });
 }
 
 extern "C" int nr_col_sum(int dtype, int64_t rows, int64_t cols, const void* src, int64_t lds, float* out,
                           void* stream) {
   clear_error();
-  NR_CHECK_ARG(NR_OKDT(dtype) && rows >= 0 && cols > 0 && lds >= cols, "nr_col_sum: bad args");
+  NR_CHECK_ARG(ok_dtype(dtype) && rows >= 0 && cols > 0 && lds >= cols, "nr_col_sum: bad args");
   if (rows == 0) return NR_OK;
   NR_CHECK_ARG(src && out, "nr_col_sum: null pointer");
   NR_CHECK_DEVICE("nr_col_sum", src, out);
@@ -720,10 +721,13 @@ extern "C" int nr_col_sum(int dtype, int64_t rows, int64_t cols, const void* src
   rpb = rpb < 32 ? 32 : (rpb + 3) / 4 * 4;
   NR_CHECK_ARG((rows + rpb - 1) / rpb <= 65535 && rpb <= 0x7fffffff, "nr_col_sum: too many rows");
   const dim3 grid((unsigned)cgroups, (unsigned)((rows + rpb - 1) / rpb));
-  NR_DT1(dtype, hipLaunchKernelGGL((col_sum_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, rows, cols,
-                                   (const T*)src, lds, (int)rpb, out));
-  NR_CHECK_LAUNCH("nr_col_sum");
-  return NR_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((col_sum_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, rows, cols, (const T*)src, lds,
+                       (int)rpb, out);
+    NR_CHECK_LAUNCH("nr_col_sum");
+    return NR_OK;
+  });
 }
 
 extern "C" int nr_ln_param_grad(int dtype_in, int64_t n, int64_t dim, const void* x, int64_t ldx,
@@ -739,18 +743,13 @@ extern "C" int nr_ln_param_grad(int dtype_in, int64_t n, int64_t dim, const void
   NR_CHECK_ARG(lddy % 4 == 0 && ((uintptr_t)dy & 15) == 0, "nr_ln_param_grad: dy rows must be 16-byte aligned");
   const int64_t g16 = (n + 15) / 16;  // ~16 rows per block: few enough blocks that the final atomics stay cheap
   const unsigned grid = (unsigned)(g16 < 256 ? g16 : 256);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype_in == NR_F32)
-    hipLaunchKernelGGL((ln_param_grad_kernel<float>), dim3(grid), dim3(256), 0, s, n, (const float*)x, ldx, row_idx,
-                       eps, dy, lddy, dgamma, dbeta);
-  else if (dtype_in == NR_BF16)
-    hipLaunchKernelGGL((ln_param_grad_kernel<__bf16>), dim3(grid), dim3(256), 0, s, n, (const __bf16*)x, ldx,
+  return with_tok_dtype(dtype_in, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((ln_param_grad_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, n, (const T*)x, ldx,
                        row_idx, eps, dy, lddy, dgamma, dbeta);
-  else
-    hipLaunchKernelGGL((ln_param_grad_kernel<_Float16>), dim3(grid), dim3(256), 0, s, n, (const _Float16*)x, ldx,
-                       row_idx, eps, dy, lddy, dgamma, dbeta);
-  NR_CHECK_LAUNCH("nr_ln_param_grad");
-  return NR_OK;
+    NR_CHECK_LAUNCH("nr_ln_param_grad");
+    return NR_OK;
+  });
 }
 
 extern "C" int nr_sumsq(int64_t n, const float* x, float* out, void* stream) {
@@ -786,7 +785,7 @@ extern "C" int nr_splitk_fixup(int dtype_out, int epilogue, int64_t rows, int64_
                                const float* bias, const void* R, int64_t ldr, void* C, int64_t ldc, int64_t row0,
                                uint64_t seed, float p, float scale, void* stream) {
   clear_error();
-  NR_CHECK_ARG(NR_OKDT(dtype_out) && rows >= 0 && N > 0 && N % 4 == 0 && parts >= 1 && ldc >= N && row0 >= 0,
+  NR_CHECK_ARG(ok_dtype(dtype_out) && rows >= 0 && N > 0 && N % 4 == 0 && parts >= 1 && ldc >= N && row0 >= 0,
                "nr_splitk_fixup: bad args");
   NR_CHECK_ARG(epilogue == NR_EPI_NONE || epilogue == NR_EPI_RELU_DROPOUT || epilogue == NR_EPI_DRELU ||
                    epilogue == NR_EPI_RESADD || epilogue == NR_EPI_EXP,
@@ -804,17 +803,17 @@ extern "C" int nr_splitk_fixup(int dtype_out, int epilogue, int64_t rows, int64_
   NR_CHECK_ARG((quads + 255) / 256 <= 0x7fffffff, "nr_splitk_fixup: too many rows");
   const dim3 grid((unsigned)((quads + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
-#define NR_FIX(E)                                                                                                   \
-  NR_DT1(dtype_out, hipLaunchKernelGGL((splitk_fixup_kernel<E, T>), grid, dim3(256), 0, s, rows, N, parts, partials, \
-                                       bias, (const T*)R, ldr, (T*)C, ldc, row0, seed, thr, scale))
-  if (epilogue == NR_EPI_RELU_DROPOUT) NR_FIX(NR_EPI_RELU_DROPOUT);
-  else if (epilogue == NR_EPI_DRELU) NR_FIX(NR_EPI_DRELU);
-  else if (epilogue == NR_EPI_RESADD) NR_FIX(NR_EPI_RESADD);
-  else if (epilogue == NR_EPI_EXP) NR_FIX(NR_EPI_EXP);
-  else NR_FIX(NR_EPI_NONE);
-#undef NR_FIX
-  NR_CHECK_LAUNCH("nr_splitk_fixup");
-  return NR_OK;
+  return with_dtype(dtype_out, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    const auto miss = [&] { return unvalidated_code("epilogue", epilogue); };
+    const auto launch = [&](auto e) -> int {
+      hipLaunchKernelGGL((splitk_fixup_kernel<decltype(e)::value, T>), grid, dim3(256), 0, s, rows, N, parts, partials,
+                         bias, (const T*)R, ldr, (T*)C, ldc, row0, seed, thr, scale);
+      NR_CHECK_LAUNCH("nr_splitk_fixup");
+      return NR_OK;
+    };
+    return with_int<NR_EPI_NONE, NR_EPI_RELU_DROPOUT, NR_EPI_DRELU, NR_EPI_RESADD, NR_EPI_EXP>(epilogue, miss, launch);
+  });
 }
 
 static unsigned rowwave_grid(int64_t units) {  // 4 waves (units) per block, <= 2048 blocks, grid-strided
@@ -843,21 +842,20 @@ extern "C" int nr_layernorm_bwd(int64_t n, int64_t dim, const float* x, int64_t 
 extern "C" int nr_softmax64_bwd(int dtype_out, int64_t rows, int64_t cols, const float* p, int64_t ldp, const float* dp,
                                 int64_t lddp, void* ds, int64_t ldds, void* stream) {
   clear_error();
-  NR_CHECK_ARG(dtype_out == NR_F32 || dtype_out == NR_BF16, "nr_softmax64_bwd: dtype_out must be f32 or bf16");
+  NR_CHECK_ARG(ok_dtype(dtype_out), "nr_softmax64_bwd: dtype_out must be f32 or bf16");
   NR_CHECK_ARG(rows >= 0 && cols > 0 && cols % 64 == 0 && ldp >= cols && lddp >= cols && ldds >= cols,
                "nr_softmax64_bwd: bad args (cols must be a multiple of 64)");
   if (rows == 0) return NR_OK;
   NR_CHECK_ARG(p && dp && ds, "nr_softmax64_bwd: null pointer");
   NR_CHECK_DEVICE("nr_softmax64_bwd", p, dp, ds);
   const int64_t gpr = cols / 64, ng = rows * gpr;
-  if (dtype_out == NR_F32)
-    hipLaunchKernelGGL((softmax64_bwd_kernel<float, float>), dim3(rowwave_grid(ng)), dim3(256), 0, (hipStream_t)stream, ng,
-                       gpr, p, ldp, dp, lddp, (float*)ds, ldds);
-  else
-    hipLaunchKernelGGL((softmax64_bwd_kernel<float, __bf16>), dim3(rowwave_grid(ng)), dim3(256), 0, (hipStream_t)stream, ng,
-                       gpr, p, ldp, dp, lddp, (__bf16*)ds, ldds);
-  NR_CHECK_LAUNCH("nr_softmax64_bwd");
-  return NR_OK;
+  return with_dtype(dtype_out, [&](auto to) -> int {
+    using TO = typename decltype(to)::type;
+    hipLaunchKernelGGL((softmax64_bwd_kernel<float, TO>), dim3(rowwave_grid(ng)), dim3(256), 0, (hipStream_t)stream, ng,
+                       gpr, p, ldp, dp, lddp, (TO*)ds, ldds);
+    NR_CHECK_LAUNCH("nr_softmax64_bwd");
+    return NR_OK;
+  });
 }
 
 static unsigned elem4_grid(int64_t total) {
@@ -868,27 +866,26 @@ static unsigned elem4_grid(int64_t total) {
 extern "C" int nr_geglu_fwd(int dtype_out, int64_t rows, int64_t f, const float* g, int64_t ldg, void* z, int64_t ldz,
                             void* stream) {
   clear_error();
-  NR_CHECK_ARG(dtype_out == NR_F32 || dtype_out == NR_BF16, "nr_geglu_fwd: dtype_out must be f32 or bf16");
+  NR_CHECK_ARG(ok_dtype(dtype_out), "nr_geglu_fwd: dtype_out must be f32 or bf16");
   NR_CHECK_ARG(rows >= 0 && f > 0 && f % 4 == 0 && ldg >= 2 * f && ldz >= f && ldg % 4 == 0 && ldz % 4 == 0,
                "nr_geglu_fwd: bad args");
   if (rows == 0) return NR_OK;
   NR_CHECK_ARG(g && z, "nr_geglu_fwd: null pointer");
   NR_CHECK_DEVICE("nr_geglu_fwd", g, z);
   NR_CHECK_ARG((((uintptr_t)g | (uintptr_t)z) & 15) == 0, "nr_geglu_fwd: 16-byte alignment required");
-  if (dtype_out == NR_F32)
-    hipLaunchKernelGGL((geglu_fwd_kernel<float>), dim3(elem4_grid(rows * f)), dim3(256), 0, (hipStream_t)stream, rows,
-                       f, g, ldg, (float*)z, ldz);
-  else
-    hipLaunchKernelGGL((geglu_fwd_kernel<__bf16>), dim3(elem4_grid(rows * f)), dim3(256), 0, (hipStream_t)stream, rows,
-                       f, g, ldg, (__bf16*)z, ldz);
-  NR_CHECK_LAUNCH("nr_geglu_fwd");
-  return NR_OK;
+  return with_dtype(dtype_out, [&](auto to) -> int {
+    using TO = typename decltype(to)::type;
+    hipLaunchKernelGGL((geglu_fwd_kernel<TO>), dim3(elem4_grid(rows * f)), dim3(256), 0, (hipStream_t)stream, rows, f,
+                       g, ldg, (TO*)z, ldz);
+    NR_CHECK_LAUNCH("nr_geglu_fwd");
+    return NR_OK;
+  });
 }
 
 extern "C" int nr_geglu_bwd(int dtype_out, int64_t rows, int64_t f, const float* g, int64_t ldg, const float* dz,
                             int64_t lddz, void* dg, int64_t lddg, void* stream) {
   clear_error();
-  NR_CHECK_ARG(dtype_out == NR_F32 || dtype_out == NR_BF16, "nr_geglu_bwd: dtype_out must be f32 or bf16");
+  NR_CHECK_ARG(ok_dtype(dtype_out), "nr_geglu_bwd: dtype_out must be f32 or bf16");
   NR_CHECK_ARG(rows >= 0 && f > 0 && f % 4 == 0 && ldg >= 2 * f && lddz >= f && lddg >= 2 * f && ldg % 4 == 0 &&
                    lddz % 4 == 0 && lddg % 4 == 0,
                "nr_geglu_bwd: bad args");
@@ -896,12 +893,11 @@ extern "C" int nr_geglu_bwd(int dtype_out, int64_t rows, int64_t f, const float*
   NR_CHECK_ARG(g && dz && dg, "nr_geglu_bwd: null pointer");
   NR_CHECK_DEVICE("nr_geglu_bwd", g, dz, dg);
   NR_CHECK_ARG((((uintptr_t)g | (uintptr_t)dz | (uintptr_t)dg) & 15) == 0, "nr_geglu_bwd: 16-byte alignment required");
-  if (dtype_out == NR_F32)
-    hipLaunchKernelGGL((geglu_bwd_kernel<float>), dim3(elem4_grid(rows * f)), dim3(256), 0, (hipStream_t)stream, rows,
-                       f, g, ldg, dz, lddz, (float*)dg, lddg);
-  else
-    hipLaunchKernelGGL((geglu_bwd_kernel<__bf16>), dim3(elem4_grid(rows * f)), dim3(256), 0, (hipStream_t)stream, rows,
-                       f, g, ldg, dz, lddz, (__bf16*)dg, lddg);
-  NR_CHECK_LAUNCH("nr_geglu_bwd");
-  return NR_OK;
+  return with_dtype(dtype_out, [&](auto to) -> int {
+    using TO = typename decltype(to)::type;
+    hipLaunchKernelGGL((geglu_bwd_kernel<TO>), dim3(elem4_grid(rows * f)), dim3(256), 0, (hipStream_t)stream, rows, f,
+                       g, ldg, dz, lddz, (TO*)dg, lddg);
+    NR_CHECK_LAUNCH("nr_geglu_bwd");
+    return NR_OK;
+  });
 }

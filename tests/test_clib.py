@@ -99,3 +99,150 @@ def test_host_pointers_are_refused_not_launched():
     assert rc == -1 and b"`hist_table`" in lib.nr_last_error() and b"not device memory" in lib.nr_last_error()
     rc = lib.nr_gemm(_lib.NR_F32, _lib.NR_F32, 0, 4, 128, 32, P(t), 1024, P(t), 1024, None, None, 0, P(t), 1024, None)
     assert rc == -1 and b"`A`" in lib.nr_last_error()
+
+
+# ---------------------------------------------------------------------------
+# Host behaviour of the code dispatch: every entry that takes a dtype, row
+# width, epilogue or pooler code, called with valid sizes, null pointers (no
+# device here) and ONE code replaced by an invalid value.  The (return code,
+# message) pairs were recorded from the library before the dispatch helpers of
+# nr_common.h replaced the per-file macros and ladders; they pin each entry's
+# error text and code and the order of its host checks.
+_BAD_DTYPE, _BAD_DIM, _BAD_EPI, _BAD_POOL = 7, 300, 99, 7
+
+
+def _code_calls():
+    """name -> (valid argument tuple with null pointers, {argument index: invalid code})."""
+    f = ctypes.c_float
+    L1 = lambda v: (ctypes.c_int64 * 1)(v)  # noqa: E731
+    null1 = (ctypes.c_void_p * 1)(None)
+    F32, BF16 = _lib.NR_F32, _lib.NR_BF16
+    dt, dim, epi, pool = _BAD_DTYPE, _BAD_DIM, _BAD_EPI, _BAD_POOL
+    return {
+        "nr_gemm": ((F32, F32, 0, 4, 128, 32, None, 32, None, 32, None, None, 0, None, 128, None), {0: dt, 1: dt, 2: epi}),
+        "nr_gemm_relu_dropout": ((BF16, BF16, 4, 256, 64, None, 64, None, 64, None, None, 256, 7, f(0.1), None),
+                                 {0: dt, 1: dt}),
+        "nr_gemm_drelu": ((BF16, BF16, 4, 256, 64, None, 64, None, 64, None, 256, None, 256, f(1.0), None),
+                          {0: dt, 1: dt}),
+        "nr_gemm_grouped": ((BF16, F32, 1, L1(256), L1(256), L1(64), null1, L1(64), null1, L1(64), null1, L1(256), None),
+                            {0: dt, 1: dt}),
+        "nr_gemm_grouped_tn": ((F32, 1, L1(256), L1(256), L1(64), null1, L1(256), null1, L1(256), null1, L1(256), None,
+                                None), {0: dt}),
+        "nr_layernorm": ((F32, F32, 2, 1024, None, 1024, None, None, f(1e-5), None, 1024, None), {0: dt, 1: dt, 3: dim}),
+        "nr_gather_layernorm": ((F32, 2, 1024, None, 1024, None, 1, None, None, f(1e-12), None, 1024, None),
+                                {0: dt, 2: dim}),
+        "nr_softmax64": ((2, 2, None, 128, F32, None, 128, None), {4: dt}),
+        "nr_row_inv_norm": ((F32, 2, 1024, None, 1024, f(1e-8), None, None), {0: dt, 2: dim}),
+        "nr_row_stats": ((F32, 2, 1024, None, 1024, f(1e-5), None, None), {0: dt, 2: dim}),
+        "nr_pool_score": ((_lib.NR_POOL_LATENT, F32, 1024, None, 1024, None, 1024, None, None, None, None, None, 2, None,
+                           None, None), {0: pool, 1: dt, 2: dim}),
+        "nr_score_users": ((F32, 1024, None, None, None, 1024, None, None, None, 2, None, None), {0: dt, 1: dim}),
+        "nr_final_attn_transform": ((F32, 2, None, 1024) + (None,) * 11 + (1 << 24, None), {0: dt}),
+        "nr_latent_transform": ((F32, 2, None, 1024) + (None,) * 12 + (1 << 24, None), {0: dt}),
+        "nr_latent_transform_lnfold": ((BF16, 2, None, 1024) + (None,) * 9 + (1 << 24, None), {0: dt}),
+        "nr_embed_ln": ((F32, 4) + (None,) * 7 + (f(1e-5), None, None), {0: dt}),
+        "nr_attention_varlen": ((F32, 1, 1, None, None, None, None, None), {0: dt}),
+        "nr_encoder_forward": ((F32, 0, None, None, 100, None, 514, None, None, None, f(1e-5), 1, 4, None, None,
+                                _lib.NR_POOL_MEAN, None, None, None, None, 1 << 24, None), {0: dt, 15: pool}),
+        "nr_gather_rows": ((F32, F32, 2, 1024, None, 1024, None, None, 1024, None), {0: dt, 1: dt}),
+        "nr_transpose": ((F32, F32, 64, 64, None, 64, None, 64, None), {0: dt, 1: dt}),
+        "nr_final_pool_fwd": ((F32, 2, None, None, 2048, None, None, None), {0: dt}),
+        "nr_final_pool_bwd": ((F32, 2, None, 64, None, 2048, None, None, None, None, 1024, None, 1024, None), {0: dt}),
+        "nr_scatter_add_rows": ((F32, 2, 1024, None, 1024, None, None, 1024, None), {0: dt}),
+        "nr_col_sum": ((F32, 4, 128, None, 128, None, None), {0: dt}),
+        "nr_ln_param_grad": ((F32, 2, 1024, None, 1024, None, f(1e-12), None, 1024, None, None, None), {0: dt, 2: dim}),
+        "nr_layernorm_bwd": ((2, 1024, None, 1024, None, f(1e-5), None, 1024, None, 0, None, 1024, None), {1: dim}),
+        "nr_softmax64_bwd": ((F32, 2, 128, None, 128, None, 128, None, 128, None), {0: dt}),
+        "nr_geglu_fwd": ((BF16, 2, 64, None, 128, None, 64, None), {0: dt}),
+        "nr_geglu_bwd": ((F32, 2, 64, None, 128, None, 64, None, 128, None), {0: dt}),
+        "nr_splitk_fixup": ((F32, _lib.NR_EPI_NONE, 2, 256, 2, None, None, None, 0, None, 256, 0, 0, f(0.0), f(1.0), None),
+                            {0: dt, 1: epi}),
+    }
+
+
+_CODE_CASES = [(name, i) for name, (_, bad) in _code_calls().items() for i in bad]
+_CODE_CASES += [("nr_final_train_step", "dtype"), ("nr_final_train_step", "tok_dtype"),
+                ("nr_latent_train_step", "dtype"), ("nr_latent_train_step", "tok_dtype"),
+                ("nr_final_train_workspace_bytes", 0), ("nr_latent_train_workspace_bytes", 0)]
+
+# (where a width or epilogue is checked after the null-pointer check, the null pointers
+# of this GPU-less call are what is reported: that order is part of the record)
+_CODE_EXPECT = {
+    "nr_gemm-0": (-1, 'nr_gemm: bad dtype_in 7'),
+    "nr_gemm-1": (-1, 'nr_gemm: bad dtype_out 7'),
+    "nr_gemm-2": (-1, 'nr_gemm: null operand'),
+    "nr_gemm_relu_dropout-0": (-1, 'nr_gemm: bad dtype_in 7'),
+    "nr_gemm_relu_dropout-1": (-1, 'nr_gemm: bad dtype_out 7'),
+    "nr_gemm_drelu-0": (-1, 'nr_gemm: bad dtype_in 7'),
+    "nr_gemm_drelu-1": (-1, 'nr_gemm: bad dtype_out 7'),
+    "nr_gemm_grouped-0": (-1, 'gemm_group: bad dtype_in 7'),
+    "nr_gemm_grouped-1": (-1, 'gemm_group: bad dtype_out 7'),
+    "nr_gemm_grouped_tn-0": (-1, 'gemm_group_tn: bad dtype_out 7'),
+    "nr_layernorm-0": (-1, 'nr_layernorm: bad dtype'),
+    "nr_layernorm-1": (-1, 'nr_layernorm: bad dtype'),
+    "nr_layernorm-3": (-1, 'nr_layernorm: null pointer'),
+    "nr_gather_layernorm-0": (-1, 'nr_gather_layernorm: bad dtype'),
+    "nr_gather_layernorm-2": (-1, 'nr_gather_layernorm: null pointer'),
+    "nr_softmax64-4": (-1, 'nr_softmax64: bad dtype'),
+    "nr_row_inv_norm-0": (-1, 'nr_row_inv_norm: bad dtype'),
+    "nr_row_inv_norm-2": (-1, 'nr_row_inv_norm: null pointer'),
+    "nr_row_stats-0": (-1, 'nr_row_stats: bad dtype'),
+    "nr_row_stats-2": (-1, 'nr_row_stats: dim 300 unsupported (1024 only)'),
+    "nr_pool_score-0": (-1, 'nr_pool_score: bad pooler 7'),
+    "nr_pool_score-1": (-1, 'nr_pool_score: bad dtype 7'),
+    "nr_pool_score-2": (-3, 'nr_pool_score: dim 300 unsupported (1024 only)'),
+    "nr_score_users-0": (-1, 'nr_score_users: bad dtype 7'),
+    "nr_score_users-1": (-3, 'nr_score_users: dim 300 unsupported (1024 only)'),
+    "nr_final_attn_transform-0": (-1, 'nr_final_attn_transform: bad dtype'),
+    "nr_latent_transform-0": (-1, 'nr_latent_transform: bad dtype'),
+    "nr_latent_transform_lnfold-0": (-3, 'nr_latent_transform_lnfold: bf16 only (f32 uses nr_latent_transform)'),
+    "nr_embed_ln-0": (-1, 'nr_embed_ln: bad dtype'),
+    "nr_attention_varlen-0": (-1, 'nr_attention_varlen: bad dtype'),
+    "nr_encoder_forward-0": (-1, 'nr_encoder_forward: bad dtype 7'),
+    "nr_encoder_forward-15": (-1, 'nr_encoder_forward: bad pool 7'),
+    "nr_gather_rows-0": (-1, 'nr_gather_rows: bad dtype'),
+    "nr_gather_rows-1": (-1, 'nr_gather_rows: bad dtype'),
+    "nr_transpose-0": (-1, 'nr_transpose: bad dtype'),
+    "nr_transpose-1": (-1, 'nr_transpose: bad dtype'),
+    "nr_final_pool_fwd-0": (-1, 'nr_final_pool_fwd: bad args'),
+    "nr_final_pool_bwd-0": (-1, 'nr_final_pool_bwd: bad args'),
+    "nr_scatter_add_rows-0": (-1, 'nr_scatter_add_rows: bad args'),
+    "nr_col_sum-0": (-1, 'nr_col_sum: bad args'),
+    "nr_ln_param_grad-0": (-1, 'nr_ln_param_grad: bad dtype'),
+    "nr_ln_param_grad-2": (-1, 'nr_ln_param_grad: dim 300 unsupported'),
+    "nr_layernorm_bwd-1": (-1, 'nr_layernorm_bwd: dim 300 unsupported'),
+    "nr_softmax64_bwd-0": (-1, 'nr_softmax64_bwd: dtype_out must be f32 or bf16'),
+    "nr_geglu_fwd-0": (-1, 'nr_geglu_fwd: dtype_out must be f32 or bf16'),
+    "nr_geglu_bwd-0": (-1, 'nr_geglu_bwd: dtype_out must be f32 or bf16'),
+    "nr_splitk_fixup-0": (-1, 'nr_splitk_fixup: bad args'),
+    "nr_splitk_fixup-1": (-1, 'nr_splitk_fixup: epilogue 99 unsupported'),
+    "nr_final_train_step-dtype": (-1, 'nr_final_train_step: dtype must be NR_F32 or NR_BF16'),
+    "nr_final_train_step-tok_dtype": (-1, 'nr_final_train_step: bad tok_dtype'),
+    "nr_latent_train_step-dtype": (-1, 'nr_latent_train_step: dtype must be NR_F32 or NR_BF16'),
+    "nr_latent_train_step-tok_dtype": (-1, 'nr_latent_train_step: bad tok_dtype'),
+    "nr_final_train_workspace_bytes-0": (-1, ''),
+    "nr_latent_train_workspace_bytes-0": (-1, ''),
+}
+
+
+def _call_with_bad_code(lib, name, which):
+    if name.endswith("_workspace_bytes"):
+        return int(getattr(lib, name)(_BAD_DTYPE, 4, 8, 16)), ""
+    if name.endswith("_train_step"):
+        a = _lib.FinalTrainArgs() if name == "nr_final_train_step" else _lib.LatentTrainArgs()
+        a.dtype, a.tok_dtype, a.B, a.U, a.Hs, a.margin = _lib.NR_BF16, _lib.NR_F16, 4, 8, 16, 2.0
+        setattr(a, which, _BAD_DTYPE)
+        rc = getattr(lib, name)(ctypes.byref(a), None, 1 << 24, None)
+    else:
+        args, bad = _code_calls()[name]
+        args = list(args)
+        args[which] = bad[which]
+        rc = getattr(lib, name)(*args)
+    return int(rc), lib.nr_last_error().decode()
+
+
+@pytest.mark.parametrize("name,which", _CODE_CASES, ids=[f"{n}-{w}" for n, w in _CODE_CASES])
+def test_invalid_code_is_refused_with_its_own_message(name, which):
+    if not _lib.LIB_PATH.is_file():
+        pytest.skip("libnewsrec_hip.so not built (run __graft_entry__.build())")
+    assert _call_with_bad_code(_lib.load(), name, which) == _CODE_EXPECT[f"{name}-{which}"]

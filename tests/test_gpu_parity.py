@@ -513,9 +513,9 @@ def test_gemm_softmax64_epilogue(gpu_device, dt):
     assert torch.allclose(out.double().reshape(M, 8, 64).sum(-1), torch.ones(M, 8, dtype=torch.float64, device=gpu_device), atol=1e-5)
 
 
-@pytest.mark.parametrize("dim", [256, 768, 1024, 2048])
+@pytest.mark.parametrize("dim", [256, 512, 768, 1024, 2048])
 @pytest.mark.parametrize("dti,dto", [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
-                                     (torch.float32, torch.bfloat16)])
+                                     (torch.float32, torch.bfloat16), (torch.bfloat16, torch.float32)])
 def test_layernorm_shapes(gpu_device, dim, dti, dto):
     x = (torch.randn(3001, dim, device=gpu_device) * 3 + 1).to(dti)
     gm = torch.rand(dim, device=gpu_device) + 0.5
