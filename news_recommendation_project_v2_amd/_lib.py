@@ -18,9 +18,10 @@ CSRC = Path(__file__).resolve().with_name("csrc")
 INCLUDE = Path(__file__).resolve().parent.parent / "include"
 # translation units of libnewsrec_hip.so, in link order (also the hash order)
 HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip", "encoder.hip", "train.hip",
-               "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip")
+               "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip", "contrastive.hip")
 # the headers they include (every object is rebuilt when one changes), hashed after the sources
-HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", INCLUDE / "newsrec.h")
+HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", INCLUDE / "newsrec.h",
+               INCLUDE / "newsrec_contrastive.h")
 
 
 def hip_source_files() -> list:
@@ -134,6 +135,21 @@ SIGNATURES = {
                                 _p]),
 }
 
+# the InfoNCE entries (include/newsrec_contrastive.h), bound by load() like SIGNATURES
+CONTRASTIVE_SIGNATURES = {
+    "nr_cosine_infonce_workspace_bytes": (_l, [_l, _l]),
+    "nr_cosine_infonce": (_i, [_l, _l, _p, _p, _l, _p, _p, _p, _f, _p, _p, _p, _p, _p, _l, _p]),
+    "nr_final_train_step_contrastive_workspace_bytes": (_l, [_i, _l, _l, _l, _l]),
+    "nr_final_train_step_contrastive": (_i, [_p, _p, _p, _l, _p]),
+    "nr_latent_train_step_contrastive_workspace_bytes": (_l, [_i, _l, _l, _l, _l]),
+    "nr_latent_train_step_contrastive": (_i, [_p, _p, _p, _l, _p]),
+}
+
+
+class ContrastiveSpec(ctypes.Structure):
+    """struct nr_contrastive_spec (include/newsrec_contrastive.h)."""
+    _fields_ = [("Cn", _l), ("cand", _p), ("target", _p), ("mask", _p), ("inv_tau", _f)]
+
 
 class EncoderLayer(ctypes.Structure):
     """struct nr_encoder_layer (include/newsrec.h): device pointers of one layer."""
@@ -185,7 +201,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no CPU fallback for the MI355X hot path)")
     lib = ctypes.CDLL(os.fspath(LIB_PATH))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -39,6 +39,8 @@
 // grads.
 #include "nr_train.h"
 
+#include "../../include/newsrec_contrastive.h"
+
 namespace nr {
 namespace ft {
 
@@ -172,6 +174,20 @@ __global__ __launch_bounds__(256) void sq_total_kernel(int64_t n, const float* _
   for (int64_t i = threadIdx.x; i < n; i += 256) s += part[i];
   const float t = block_sum4(s, red);
   if (threadIdx.x == 0) *out = t;
+}
+
+// part[blockIdx.x] = this block's share of sum x^2 (no atomics: sq_total_kernel sums the
+// partials in a fixed order).  The contrastive f32 step's grad norm: kSqF32Blocks partials
+// per gradient array keep every f32 chain short (<= 64 elements per thread, 4 + 44 per
+// partial sum), where nr_sumsq's up to 1,024 atomics per array onto ONE float left the
+// margin f32 step's norm 2e-6 - 8e-6 low of its own gradients' float64 norm.
+constexpr int kSqF32Blocks = 1024, kSqF32Arrays = 11;
+__global__ __launch_bounds__(256) void sumsq_parts_kernel(int64_t n, const float* __restrict__ x,
+                                                          float* __restrict__ part) {
+  __shared__ float red[4];
+  const float s = sumsq_range(x, n, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256);
+  const float t = block_sum4(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
 // F.cosine_similarity(u, E[pos / neg]) with the per-vector 1e-8 clamp and
@@ -355,6 +371,11 @@ __device__ __forceinline__ void rowsum_body(const RSum& r, int bid, float* __res
   }
 }
 
+// f32 contrastive step: out[c] = sum_r C[r][c] of one f32 matrix read as rowsum_body's
+// "partials" (rows = Hp), in its fixed order: the bias gradients without nr_col_sum's float
+// atomics, so that two runs of the step give the same bits (the margin step keeps nr_col_sum).
+__global__ __launch_bounds__(256) void rowsum_kernel(RSum r) { rowsum_body(r, (int)blockIdx.x, nullptr); }
+
 // bf16: the bias grads (rowsum blocks 0 .. nrs - 1) and the W1 fold (the rest, D / 64 x
 // H / 64 blocks) as one launch.  A fold block needs g_b1 over its 64 rows h: it sums
 // them from cs1 itself with rowsum_body's arithmetic for b1's block h / 64 (the same
@@ -475,10 +496,18 @@ static int ncu_current() {
   return ncu_of_device(ok, dev);
 }
 
+// the contrastive entry's bytes after the margin layout: the stage's workspace, then the
+// f32 grad norm's partials
+static int64_t contrastive_extra(int64_t B, int64_t Cn) {
+  return contrastive_ws_bytes(B, Cn, true, true) + align256((int64_t)kSqF32Arrays * kSqF32Blocks * 4);
+}
+
 constexpr const char* kFn = "nr_final_train_step";
 
+// cs: the InfoNCE loss of nr_final_train_step_contrastive (its workspace after the
+// margin layout's), nullptr: the margin loss
 template <typename TA, typename TT>  // activation / weight type, token-state type
-int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
+int step(const nr_final_train_args& a, const CnSpec* cs, char* ws, hipStream_t st) {
   constexpr bool BF = sizeof(TA) == 2;
   const int dt = a.dtype;
   const int ncu = ncu_of(st);
@@ -562,26 +591,45 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
   NR_TRY(gemm_dispatch(dt, dt, NR_EPI_EXP, Hp, D, H, Y, H, W5, H, nullptr, nullptr, 0, Pexp, 2 * D, st));
   NR_TRY(nr_final_pool_fwd(dt, B, a.hist_off, XP, 2 * D, users, z, st));
   // ---- loss and its gradient into the pooled users and E[pos] / E[neg]
-  {
-    const dim3 grid((unsigned)((B + 3) / 4));
-    hipLaunchKernelGGL((cos_pairs_kernel<TT>), grid, dim3(256), 0, st, B, users, (const TT*)a.tok_last, xpair, a.tok_g,
-                       a.tok_b, a.pos, a.neg, a.margin, lrow, du, gpair);
+  if (cs) {
+    // InfoNCE over the candidate columns: du, the candidates' token LN grad partials
+    // (in the pairs' place: the same kPairChunks chunks) and the loss
+    static_assert(kCnLnChunks == kPairChunks, "the candidates' LN partials take the pairs' chunks");
+    NR_TRY(contrastive_stage("nr_final_train_step_contrastive (loss)", *cs, users, nullptr, 0, a.tok_last, a.tok_dtype,
+                             a.tok_g, a.tok_b, nullptr, a.loss, du, nullptr, (float*)P_(L.w1p) + (H / 64) * 2 * D,
+                             ws + L.total, st));
+  } else {
+    {
+      const dim3 grid((unsigned)((B + 3) / 4));
+      hipLaunchKernelGGL((cos_pairs_kernel<TT>), grid, dim3(256), 0, st, B, users, (const TT*)a.tok_last, xpair,
+                         a.tok_g, a.tok_b, a.pos, a.neg, a.margin, lrow, du, gpair);
+    }
+    NR_CHECK_LAUNCH("nr_final_train_step (cosine)");
+    // the pairs' token LN grad partials (after the W1 fold's chunks) and the loss
+    hipLaunchKernelGGL(pair_ln_kernel, dim3((unsigned)(D / 64), kPairChunks), dim3(256), 0, st, B, gpair, xpair, lrow,
+                       (float*)P_(L.w1p) + (H / 64) * 2 * D, a.loss);
+    NR_CHECK_LAUNCH("nr_final_train_step (pair LN grads)");
   }
-  NR_CHECK_LAUNCH("nr_final_train_step (cosine)");
-  // the pairs' token LN grad partials (after the W1 fold's chunks) and the loss
-  hipLaunchKernelGGL(pair_ln_kernel, dim3((unsigned)(D / 64), kPairChunks), dim3(256), 0, st, B, gpair, xpair, lrow,
-                     (float*)P_(L.w1p) + (H / 64) * 2 * D, a.loss);
-  NR_CHECK_LAUNCH("nr_final_train_step (pair LN grads)");
   NR_TRY(nr_final_pool_bwd(dt, B, a.hist_off, Hp, XP, 2 * D, users, z, du, dXp, D, dL, D, st));
   // ---- data-grad chain (weights transposed on the side stream)
   NR_TRY_HIP(hipStreamWaitEvent(st, side.wt, 0), kFn, "transpose wait");
   float *cs4 = (float*)P_(L.cs4), *cs3 = (float*)P_(L.cs3), *cs2 = (float*)P_(L.cs2), *cs1 = (float*)P_(L.cs1);
+  // f32: a bias gradient = the column sums of its [Hp][cols] data gradient (contrastive: ordered)
+  auto col_sum_f32 = [&](int64_t cols, const TA* C, float* gbias) -> int {
+    if (!cs) return nr_col_sum(dt, Hp, cols, C, cols, gbias, st);
+    RSum r{};
+    r.n = 1;
+    r.part[0] = (const float*)C; r.out[0] = gbias; r.rows[0] = Hp; r.cols[0] = cols;
+    hipLaunchKernelGGL(rowsum_kernel, dim3((unsigned)(cols / 64)), dim3(256), 0, st, r);
+    NR_CHECK_LAUNCH("nr_final_train_step_contrastive (bias grads)");
+    return NR_OK;
+  };
   // drop'(A W^T) against the forward output Yf; bf16: column sums into cs
   auto drelu_gemm = [&](const TA* A, int64_t K, const TA* Wt, const TA* Yf, TA* C, float* cs, float* gbias) -> int {
     if constexpr (!BF) {
       NR_TRY(gemm_dispatch_ex(dt, dt, NR_EPI_DRELU, Hp, H, K, A, K, Wt, K, nullptr, Yf, H, C, H,
                              EpiArgs{0, 0, scale}, st));
-      return nr_col_sum(dt, Hp, H, C, H, gbias, st);
+      return col_sum_f32(H, C, gbias);
     } else {
       EpiArgs ea{0, 0, scale};
       ea.colsum = cs;
@@ -605,7 +653,7 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
     EpiArgs ea{0, 0, 1.f};
     if constexpr (BF) ea.colsum = cs3;
     NR_TRY(gemm_dispatch_ex(dt, dt, NR_EPI_RESADD, Hp, D, H, dY, H, W4t, H, nullptr, dXp, D, dX, D, ea, st));
-    if constexpr (!BF) NR_TRY(nr_col_sum(dt, Hp, D, dX, D, a.g_b3, st));
+    if constexpr (!BF) NR_TRY(col_sum_f32(D, dX, a.g_b3));
   }
   NR_TRY(drelu_gemm(dX, D, W3t, X2, dZ2, cs2, a.g_b2));
   NR_TRY(drelu_gemm(dZ2, H, W2t, X1, dZ1, cs1, a.g_b1));
@@ -673,10 +721,23 @@ int step(const nr_final_train_args& a, char* ws, hipStream_t st) {
       hipLaunchKernelGGL(sq_total_kernel, dim3(1), dim3(256), 0, st, (int64_t)kSqParts, sqp, a.sumsq);
       NR_CHECK_LAUNCH("nr_final_train_step (grad norm)");
     } else if (a.sumsq) {  // f32 mode: over the gradient arrays
-      NR_TRY(zero_ranges(ZList{1, {a.sumsq}, {1}}, 1, st));
       float* gs[11] = {a.g_tok_g, a.g_tok_b, a.g_W1, a.g_b1, a.g_W2, a.g_b2, a.g_W3, a.g_b3, a.g_W4, a.g_b4, a.g_W5};
       const int64_t gn[11] = {D, D, H * D, H, H * H, H, D * H, D, H * D, H, D * H};
-      for (int i = 0; i < 11; ++i) NR_TRY(nr_sumsq(gn[i], gs[i], a.sumsq, st));
+      static_assert(kSqF32Arrays == 11, "one partial row per gradient array");
+      if (cs) {  // ordered: partials after the stage's workspace, then one fixed-order sum
+        float* part = (float*)(ws + L.total + contrastive_ws_bytes(cs->B, cs->Cn, true, true));
+        for (int i = 0; i < 11; ++i) {
+          hipLaunchKernelGGL(sumsq_parts_kernel, dim3(kSqF32Blocks), dim3(256), 0, st, gn[i], gs[i],
+                             part + i * kSqF32Blocks);
+          NR_CHECK_LAUNCH("nr_final_train_step_contrastive (grad norm partials)");
+        }
+        hipLaunchKernelGGL(sq_total_kernel, dim3(1), dim3(256), 0, st, (int64_t)kSqF32Arrays * kSqF32Blocks, part,
+                           a.sumsq);
+        NR_CHECK_LAUNCH("nr_final_train_step_contrastive (grad norm)");
+      } else {
+        NR_TRY(zero_ranges(ZList{1, {a.sumsq}, {1}}, 1, st));
+        for (int i = 0; i < 11; ++i) NR_TRY(nr_sumsq(gn[i], gs[i], a.sumsq, st));
+      }
     }
   }
   return NR_OK;
@@ -692,31 +753,58 @@ extern "C" int64_t nr_final_train_workspace_bytes(int dtype, int64_t B, int64_t 
   return nr::ft::layout(dtype, B, U, Hs, nr::ft::ncu_current()).total;
 }
 
-extern "C" int nr_final_train_step(const nr_final_train_args* args, void* ws, int64_t ws_bytes, void* stream) {
+// the argument checks of both entries, then the step (cs as ft::step's); fn names the entry
+static int final_train_entry(const char* fn, const nr_final_train_args* args, const nr_contrastive_spec* spec,
+                             bool contrastive, void* ws, int64_t ws_bytes, void* stream) {
   nr::clear_error();
-  NR_CHECK_ARG(args, "nr_final_train_step: null args");
+  NR_CHECK_ARG(args, "%s: null args", fn);
+  NR_CHECK_ARG(!contrastive || spec, "%s: null spec", fn);
   const nr_final_train_args& a = *args;
-  NR_TRY(nr::check_step_args("nr_final_train_step", a.dtype, a.tok_dtype, a.B, a.U, a.Hs));
-  NR_CHECK_ARG(a.p >= 0.f && a.p < 1.f, "nr_final_train_step: dropout p outside [0, 1)");
+  NR_TRY(nr::check_step_args(fn, a.dtype, a.tok_dtype, a.B, a.U, a.Hs));
+  NR_CHECK_ARG(a.p >= 0.f && a.p < 1.f, "%s: dropout p outside [0, 1)", fn);
   // bf16: the persistent GEMM (the column-sum epilogues have no other kernel) addresses
   // its [Hp][4096] operands through 32-bit buffer offsets; refuse before any launch
   NR_CHECK_ARG(a.dtype != NR_BF16 || nr::pad64(a.Hs) * nr::ft::H * 2 <= 0xFFFFFFFFll,
-               "nr_final_train_step: bf16 batch of %lld history slots exceeds the persistent GEMM's 4 GiB operand "
-               "range (at most %lld)", (long long)a.Hs, 0xFFFFFFFFll / (2 * nr::ft::H) / 64 * 64);
-  NR_CHECK_DEVICE("nr_final_train_step", a.tok_last, a.hist_idx, a.hist_off, a.pos, a.neg, a.tok_g, a.tok_b, a.W1,
-                  a.b1, a.W2, a.b2, a.W3, a.b3, a.W4, a.b4, a.W5);
-  NR_CHECK_DEVICE("nr_final_train_step", a.g_tok_g, a.g_tok_b, a.g_W1, a.g_b1, a.g_W2, a.g_b2, a.g_W3, a.g_b3, a.g_W4,
-                  a.g_b4, a.g_W5, a.loss, a.users, a.sumsq, ws);
-  NR_CHECK_ARG(a.tok_last && a.hist_idx && a.hist_off && a.pos && a.neg && a.loss && ws && a.tok_g && a.tok_b &&
-                   a.W1 && a.b1 && a.W2 && a.b2 && a.W3 && a.b3 && a.W4 && a.b4 && a.W5 && a.g_W1 && a.g_W2 && a.g_W3 && a.g_W4 && a.g_W5 && a.g_b1 && a.g_b2 && a.g_b3 &&
-                   a.g_b4 && a.g_tok_g && a.g_tok_b,
-               "nr_final_train_step: null pointer");
+               "%s: bf16 batch of %lld history slots exceeds the persistent GEMM's 4 GiB operand "
+               "range (at most %lld)", fn, (long long)a.Hs, 0xFFFFFFFFll / (2 * nr::ft::H) / 64 * 64);
   hipStream_t s = (hipStream_t)stream;
-  const int64_t need = nr::ft::layout(a.dtype, a.B, a.U, a.Hs, nr::ft::ncu_of(s)).total;
-  NR_CHECK_ARG(ws_bytes >= need, "nr_final_train_step: workspace too small (%lld < %lld)", (long long)ws_bytes,
-               (long long)need);
-  NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "nr_final_train_step: workspace must be 256-byte aligned");
+  nr::CnSpec cs{};
+  if (contrastive) {
+    NR_CHECK_ARG(spec->Cn >= 1, "%s: Cn = %lld < 1", fn, (long long)spec->Cn);
+    cs = nr::CnSpec{a.B, spec->Cn, a.U, spec->cand, spec->target, spec->mask, spec->inv_tau};
+  }
+  NR_CHECK_DEVICE(fn, a.tok_last, a.hist_idx, a.hist_off, a.tok_g, a.tok_b, a.W1, a.b1, a.W2, a.b2, a.W3, a.b3, a.W4,
+                  a.b4, a.W5);
+  if (!contrastive) NR_CHECK_DEVICE(fn, a.pos, a.neg);
+  NR_CHECK_DEVICE(fn, a.g_tok_g, a.g_tok_b, a.g_W1, a.g_b1, a.g_W2, a.g_b2, a.g_W3, a.g_b3, a.g_W4, a.g_b4, a.g_W5,
+                  a.loss, a.users, a.sumsq, ws);
+  NR_CHECK_ARG(a.tok_last && a.hist_idx && a.hist_off && (contrastive || (a.pos && a.neg)) && a.loss && ws &&
+                   a.tok_g && a.tok_b && a.W1 && a.b1 && a.W2 && a.b2 && a.W3 && a.b3 && a.W4 && a.b4 && a.W5 &&
+                   a.g_W1 && a.g_W2 && a.g_W3 && a.g_W4 && a.g_W5 && a.g_b1 && a.g_b2 && a.g_b3 && a.g_b4 &&
+                   a.g_tok_g && a.g_tok_b,
+               "%s: null pointer", fn);
+  int64_t need = nr::ft::layout(a.dtype, a.B, a.U, a.Hs, nr::ft::ncu_of(s)).total;
+  if (contrastive) need += nr::ft::contrastive_extra(a.B, spec->Cn);
+  NR_CHECK_ARG(ws_bytes >= need, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes, (long long)need);
+  NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+  if (contrastive) NR_TRY(nr::contrastive_check(fn, cs, s));
   return nr::with_dtypes_tok(a.dtype, a.tok_dtype, [&](auto ta, auto tt) {
-    return nr::ft::step<typename decltype(ta)::type, typename decltype(tt)::type>(a, (char*)ws, s);
+    return nr::ft::step<typename decltype(ta)::type, typename decltype(tt)::type>(a, contrastive ? &cs : nullptr,
+                                                                                  (char*)ws, s);
   });
+}
+
+extern "C" int nr_final_train_step(const nr_final_train_args* args, void* ws, int64_t ws_bytes, void* stream) {
+  return final_train_entry("nr_final_train_step", args, nullptr, false, ws, ws_bytes, stream);
+}
+
+extern "C" int64_t nr_final_train_step_contrastive_workspace_bytes(int dtype, int64_t B, int64_t U, int64_t Hs,
+                                                                   int64_t Cn) {
+  if (!nr::ok_dtype(dtype) || B < 1 || U < 0 || Hs < 0 || Cn < 1) return -1;
+  return nr::ft::layout(dtype, B, U, Hs, nr::ft::ncu_current()).total + nr::ft::contrastive_extra(B, Cn);
+}
+
+extern "C" int nr_final_train_step_contrastive(const nr_final_train_args* args, const nr_contrastive_spec* spec,
+                                               void* ws, int64_t ws_bytes, void* stream) {
+  return final_train_entry("nr_final_train_step_contrastive", args, spec, true, ws, ws_bytes, stream);
 }

@@ -32,6 +32,8 @@
 // everything else here is HBM-bound row work (one wave per row, 16-B lanes).
 #include "nr_train.h"
 
+#include "../../include/newsrec_contrastive.h"
+
 namespace nr {
 namespace lt {
 
@@ -313,7 +315,13 @@ __global__ __launch_bounds__(512) void segmean_kernel(int64_t B, int64_t Bp, con
 // gb2 += dm, and the pos / neg rows' cosine grads g straight into the token LN's
 // parameter grads: gtg += g xhat (Xpn), gtb += g (lane-contiguous atomics: 256 B per
 // wave instruction).
-template <typename TA>
+// PH splits the kernel at the user vector for the contrastive step (InfoNCE over the
+// batch's candidate columns, contrastive.hip, between the two halves): PH = 1 stops after
+// writing users = u (required); PH = 2 recomputes m and u with the same arithmetic, takes
+// du [B][D] from memory (`dux`) in place of the margin loss's, and runs the backward half
+// (no loss, no pos / neg rows: the stage wrote the loss and the candidates' token LN
+// part).  PH = 0, the margin step, compiles to the code it had before the split.
+template <typename TA, int PH = 0>
 __global__ __launch_bounds__(256) void head_kernel(int64_t B, int64_t Bp, int nparts, const float* __restrict__ parts,
                                                    const float* __restrict__ b2, const float* __restrict__ h1bar,
                                                    const int64_t* __restrict__ off, const float* __restrict__ Epn,
@@ -322,12 +330,13 @@ __global__ __launch_bounds__(256) void head_kernel(int64_t B, int64_t Bp, int np
                                                    TA* __restrict__ dmA, TA* __restrict__ dmc,
                                                    float* __restrict__ dmc32, const float* __restrict__ Xpn,
                                                    float* __restrict__ gtg, float* __restrict__ gtb,
-                                                   float* __restrict__ gb2) {
+                                                   float* __restrict__ gb2, const float* __restrict__ dux = nullptr) {
   constexpr float NEPS = 1e-12f;
   __shared__ float red[4];
   const int64_t b = blockIdx.x;
   const int tid = threadIdx.x;
   if (b >= B) {
+    if constexpr (PH == 1) return;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       dmA[b * D + j * 256 + tid] = (TA)0.f;
@@ -337,8 +346,6 @@ __global__ __launch_bounds__(256) void head_kernel(int64_t B, int64_t Bp, int np
     return;
   }
   float m[4], ep[4], en[4];
-  const float* pr = Epn + b * D;         // E[pos[b]]
-  const float* nr_ = Epn + (B + b) * D;  // E[neg[b]]
   float mm = 0.f;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -346,34 +353,48 @@ __global__ __launch_bounds__(256) void head_kernel(int64_t B, int64_t Bp, int np
     float v = h1bar[b * D + c] + b2[c];
     for (int s = 0; s < nparts; ++s) v += parts[((int64_t)s * Bp + b) * D + c];
     m[j] = v;
-    ep[j] = pr[c];
-    en[j] = nr_[c];
+    if constexpr (PH == 0) {
+      ep[j] = Epn[b * D + c];        // E[pos[b]]
+      en[j] = Epn[(B + b) * D + c];  // E[neg[b]]
+    }
     mm = fmaf(v, v, mm);
   }
   const float nm = sqrtf(block_sum4(mm, red));
   const float den = fmaxf(nm, NEPS);
   float u[4];
-  CosDots dots;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    u[j] = m[j] / den;
-    dots.add(u[j], ep[j], en[j]);
+  for (int j = 0; j < 4; ++j) u[j] = m[j] / den;
+  if constexpr (PH == 1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) users[b * D + j * 256 + tid] = u[j];
+    return;
   }
-  dots.reduce([&](float x) { return block_sum4(x, red); });
-  const CosMargin cm(dots, margin, B);
-  if (tid == 0) atomicAdd(loss, cm.loss_term());
-  const float* xp = Xpn + b * D;         // xhat of E[pos[b]]'s token LN
-  const float* xn = Xpn + (B + b) * D;   // and of E[neg[b]]'s
   float g[4];
   float ug = 0.f;
+  if constexpr (PH == 0) {
+    CosDots dots;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int c = j * 256 + tid;
-    g[j] = cm.du(u[j], ep[j], en[j]);
-    ug = fmaf(u[j], g[j], ug);
-    const float gp = cm.dpos(u[j], ep[j]), gn = cm.dneg(u[j], en[j]);
-    atomicAdd(gtg + c, fmaf(gp, xp[c], gn * xn[c]));
-    atomicAdd(gtb + c, gp + gn);
+    for (int j = 0; j < 4; ++j) dots.add(u[j], ep[j], en[j]);
+    dots.reduce([&](float x) { return block_sum4(x, red); });
+    const CosMargin cm(dots, margin, B);
+    if (tid == 0) atomicAdd(loss, cm.loss_term());
+    const float* xp = Xpn + b * D;         // xhat of E[pos[b]]'s token LN
+    const float* xn = Xpn + (B + b) * D;   // and of E[neg[b]]'s
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = j * 256 + tid;
+      g[j] = cm.du(u[j], ep[j], en[j]);
+      ug = fmaf(u[j], g[j], ug);
+      const float gp = cm.dpos(u[j], ep[j]), gn = cm.dneg(u[j], en[j]);
+      atomicAdd(gtg + c, fmaf(gp, xp[c], gn * xn[c]));
+      atomicAdd(gtb + c, gp + gn);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      g[j] = dux[b * D + j * 256 + tid];
+      ug = fmaf(u[j], g[j], ug);
+    }
   }
   ug = block_sum4(ug, red);
   const float icnt = 1.0f / (float)(off[b + 1] - off[b]);
@@ -383,11 +404,30 @@ __global__ __launch_bounds__(256) void head_kernel(int64_t B, int64_t Bp, int np
     const int c = j * 256 + tid;
     const float dm = (live ? g[j] - u[j] * ug : g[j]) / den;
     atomicAdd(gb2 + c, dm);
-    if (users) users[b * D + c] = u[j];
+    if constexpr (PH == 0) {
+      if (users) users[b * D + c] = u[j];
+    }
     dmA[b * D + c] = (TA)dm;
     dmc[b * D + c] = (TA)(dm * icnt);
     dmc32[b * D + c] = dm * icnt;
   }
+}
+
+// gtg[c] += sum_k part[k][0][c], gtb[c] += sum_k part[k][1][c] over the contrastive stage's
+// kCnLnChunks chunk partials, in chunk order: the candidates' part of the token LN parameter
+// grads (the margin head adds its pos / neg part itself).  Launched on the step's stream
+// between the zeroing and the slot rows' atomics, so a plain add.
+__global__ __launch_bounds__(256) void cand_ln_add_kernel(const float* __restrict__ part, float* __restrict__ gtg,
+                                                          float* __restrict__ gtb) {
+  const int c = (int)blockIdx.x * 256 + threadIdx.x;
+  float sg = 0.f, sb = 0.f;
+#pragma unroll
+  for (int k = 0; k < kCnLnChunks; ++k) {
+    sg += part[(int64_t)k * 2 * D + c];
+    sb += part[(int64_t)k * 2 * D + D + c];
+  }
+  gtg[c] += sg;
+  gtb[c] += sb;
 }
 
 // ------------------------------------------------------------------ backward rows
@@ -855,8 +895,26 @@ static int grid_rows(int64_t rows, int cap = 1024) {
   return (int)(g < cap ? (g > 0 ? g : 1) : cap);
 }
 
+// the contrastive entry's buffers after the margin layout: users and du [Bp][D] f32, the
+// candidates' LN chunk partials, then the stage's workspace
+struct CnExtra {
+  int64_t users, du, part, stage, total;
+};
+static CnExtra contrastive_extra(int64_t B, int64_t Cn) {
+  CnExtra x{};
+  WsCursor w;
+  x.users = w.take(pad64(B) * D * 4);
+  x.du = w.take(pad64(B) * D * 4);
+  x.part = w.take((int64_t)kCnLnChunks * 2 * D * 4);
+  x.stage = w.take(contrastive_ws_bytes(B, Cn, true, true));
+  x.total = w.o;
+  return x;
+}
+
+// cs: the InfoNCE loss of nr_latent_train_step_contrastive (its buffers after the margin
+// layout's), nullptr: the margin loss
 template <typename TA, typename TT>  // activation / weight type, token-state type
-int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
+int step(const nr_latent_train_args& a, const CnSpec* cs, char* ws, hipStream_t st) {
   const int dt = a.dtype;
   const Layout L = layout(dt, a.B, a.U, a.Hs);
   const int64_t B = a.B, Hp = L.Hp, Hpp = L.Hpp, Bp = L.Bp;
@@ -971,9 +1029,12 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
   }
   NR_TRY_HIP(hipEventRecord(side.join, fs), kFn, "join 0 record");
   // ---- E[pos] / E[neg] rows for the head (the token LN of those news' last tokens) and their xhat
-  hipLaunchKernelGGL((pn_rows_kernel<TT>), dim3((unsigned)((2 * B + 3) / 4)), dim3(256), 0, st, B,
-                     (const TT*)a.tok_last, a.pos, a.neg, a.tok_g, a.tok_b, Epn, Xpn);
-  NR_LT_CHECK("pos / neg rows");
+  // (the contrastive step forms its candidate rows in its loss stage)
+  if (!cs) {
+    hipLaunchKernelGGL((pn_rows_kernel<TT>), dim3((unsigned)((2 * B + 3) / 4)), dim3(256), 0, st, B,
+                       (const TT*)a.tok_last, a.pos, a.neg, a.tok_g, a.tok_b, Epn, Xpn);
+    NR_LT_CHECK("pos / neg rows");
+  }
   // ---- per-slot forward
   hipLaunchKernelGGL((gather_ln_kernel<TA, TT>), dim3(grid_rows(Hp)), dim3(256), 0, st, Hp, a.Hs,
                      (const TT*)a.tok_last, a.tok_g, a.tok_b, a.hist_idx, a.nq_g, a.nq_b, 1e-5f, Sx, X);
@@ -994,9 +1055,28 @@ int step(const nr_latent_train_args& a, char* ws, hipStream_t st) {
     // the split-K partials summed in parallel (the head reads one row per batch row)
     NR_TRY(sum_parts(hparts, kHParts, Bp * D, hsum, Bp * D, st));
   }
-  hipLaunchKernelGGL((head_kernel<TA>), dim3((unsigned)Bp), dim3(256), 0, st, B, Bp, 1, hsum, a.b2, h1bar,
-                     a.hist_off, Epn, a.margin, a.loss, a.users, dmA, dmc, dmc32, Xpn, a.g_tok_g, a.g_tok_b, a.g_b2);
-  NR_LT_CHECK("head");
+  if (cs) {
+    const CnExtra X_ = contrastive_extra(B, cs->Cn);
+    char* xw = ws + L.total;
+    float* users = a.users ? a.users : (float*)(xw + X_.users);
+    float *du = (float*)(xw + X_.du), *part = (float*)(xw + X_.part);
+    hipLaunchKernelGGL((head_kernel<TA, 1>), dim3((unsigned)Bp), dim3(256), 0, st, B, Bp, 1, hsum, a.b2, h1bar,
+                       a.hist_off, nullptr, 0.f, nullptr, users, dmA, dmc, dmc32, nullptr, nullptr, nullptr, nullptr,
+                       nullptr);
+    NR_LT_CHECK("head forward");
+    NR_TRY(contrastive_stage("nr_latent_train_step_contrastive (loss)", *cs, users, nullptr, 0, a.tok_last,
+                             a.tok_dtype, a.tok_g, a.tok_b, nullptr, a.loss, du, nullptr, part, xw + X_.stage, st));
+    hipLaunchKernelGGL(cand_ln_add_kernel, dim3((unsigned)(D / 256)), dim3(256), 0, st, part, a.g_tok_g, a.g_tok_b);
+    NR_LT_CHECK("candidates' token LN grads");
+    hipLaunchKernelGGL((head_kernel<TA, 2>), dim3((unsigned)Bp), dim3(256), 0, st, B, Bp, 1, hsum, a.b2, h1bar,
+                       a.hist_off, nullptr, 0.f, nullptr, nullptr, dmA, dmc, dmc32, nullptr, nullptr, nullptr, a.g_b2,
+                       du);
+    NR_LT_CHECK("head backward");
+  } else {
+    hipLaunchKernelGGL((head_kernel<TA>), dim3((unsigned)Bp), dim3(256), 0, st, B, Bp, 1, hsum, a.b2, h1bar,
+                       a.hist_off, Epn, a.margin, a.loss, a.users, dmA, dmc, dmc32, Xpn, a.g_tok_g, a.g_tok_b, a.g_b2);
+    NR_LT_CHECK("head");
+  }
   // ---- backward
   // dZ_b = (dm_b / h_b) W2 (f32, split-K partials [kZParts, Bp, 4096]): C = dmc . W2T^T
   {
@@ -1167,24 +1247,49 @@ extern "C" int64_t nr_latent_train_workspace_bytes(int dtype, int64_t B, int64_t
   return nr::lt::layout(dtype, B, U, Hs).total;
 }
 
-extern "C" int nr_latent_train_step(const nr_latent_train_args* args, void* ws, int64_t ws_bytes, void* stream) {
+// the argument checks of both entries, then the step (cs as lt::step's); fn names the entry
+static int latent_train_entry(const char* fn, const nr_latent_train_args* args, const nr_contrastive_spec* spec,
+                              bool contrastive, void* ws, int64_t ws_bytes, void* stream) {
   nr::clear_error();
-  NR_CHECK_ARG(args, "nr_latent_train_step: null args");
+  NR_CHECK_ARG(args, "%s: null args", fn);
+  NR_CHECK_ARG(!contrastive || spec, "%s: null spec", fn);
   const nr_latent_train_args& a = *args;
-  NR_TRY(nr::check_step_args("nr_latent_train_step", a.dtype, a.tok_dtype, a.B, a.U, a.Hs));
-  NR_CHECK_DEVICE("nr_latent_train_step", a.tok_last, a.hist_idx, a.hist_off, a.pos, a.neg, a.tok_g, a.tok_b,
-                  a.latents, a.nq_g, a.nq_b, a.nc_g, a.nc_b, a.Wq, a.Wkv, a.Wo, a.nf_g, a.nf_b, a.W1, a.b1, a.W2, a.b2);
-  NR_CHECK_DEVICE("nr_latent_train_step", a.g_tok_g, a.g_tok_b, a.g_latents, a.g_nq_g, a.g_nq_b, a.g_nc_g, a.g_nc_b,
-                  a.g_Wq, a.g_Wkv, a.g_Wo, a.g_nf_g, a.g_nf_b, a.g_W1, a.g_b1, a.g_W2, a.g_b2, a.loss, a.users, a.sumsq,
-                  ws);
-  NR_CHECK_ARG(a.tok_last && a.hist_idx && a.hist_off && a.pos && a.neg && a.loss && ws,
-               "nr_latent_train_step: null pointer");
-  const int64_t need = nr::lt::layout(a.dtype, a.B, a.U, a.Hs).total;
-  NR_CHECK_ARG(ws_bytes >= need, "nr_latent_train_step: workspace too small (%lld < %lld)", (long long)ws_bytes,
-               (long long)need);
-  NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "nr_latent_train_step: workspace must be 256-byte aligned");
+  NR_TRY(nr::check_step_args(fn, a.dtype, a.tok_dtype, a.B, a.U, a.Hs));
   hipStream_t s = (hipStream_t)stream;
+  nr::CnSpec cs{};
+  if (contrastive) {
+    NR_CHECK_ARG(spec->Cn >= 1, "%s: Cn = %lld < 1", fn, (long long)spec->Cn);
+    cs = nr::CnSpec{a.B, spec->Cn, a.U, spec->cand, spec->target, spec->mask, spec->inv_tau};
+  }
+  NR_CHECK_DEVICE(fn, a.tok_last, a.hist_idx, a.hist_off, a.tok_g, a.tok_b, a.latents, a.nq_g, a.nq_b, a.nc_g, a.nc_b,
+                  a.Wq, a.Wkv, a.Wo, a.nf_g, a.nf_b, a.W1, a.b1, a.W2, a.b2);
+  if (!contrastive) NR_CHECK_DEVICE(fn, a.pos, a.neg);
+  NR_CHECK_DEVICE(fn, a.g_tok_g, a.g_tok_b, a.g_latents, a.g_nq_g, a.g_nq_b, a.g_nc_g, a.g_nc_b, a.g_Wq, a.g_Wkv,
+                  a.g_Wo, a.g_nf_g, a.g_nf_b, a.g_W1, a.g_b1, a.g_W2, a.g_b2, a.loss, a.users, a.sumsq, ws);
+  NR_CHECK_ARG(a.tok_last && a.hist_idx && a.hist_off && (contrastive || (a.pos && a.neg)) && a.loss && ws,
+               "%s: null pointer", fn);
+  int64_t need = nr::lt::layout(a.dtype, a.B, a.U, a.Hs).total;
+  if (contrastive) need += nr::lt::contrastive_extra(a.B, spec->Cn).total;
+  NR_CHECK_ARG(ws_bytes >= need, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes, (long long)need);
+  NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+  if (contrastive) NR_TRY(nr::contrastive_check(fn, cs, s));
   return nr::with_dtypes_tok(a.dtype, a.tok_dtype, [&](auto ta, auto tt) {
-    return nr::lt::step<typename decltype(ta)::type, typename decltype(tt)::type>(a, (char*)ws, s);
+    return nr::lt::step<typename decltype(ta)::type, typename decltype(tt)::type>(a, contrastive ? &cs : nullptr,
+                                                                                  (char*)ws, s);
   });
+}
+
+extern "C" int nr_latent_train_step(const nr_latent_train_args* args, void* ws, int64_t ws_bytes, void* stream) {
+  return latent_train_entry("nr_latent_train_step", args, nullptr, false, ws, ws_bytes, stream);
+}
+
+extern "C" int64_t nr_latent_train_step_contrastive_workspace_bytes(int dtype, int64_t B, int64_t U, int64_t Hs,
+                                                                    int64_t Cn) {
+  if (!nr::ok_dtype(dtype) || B < 1 || U < 0 || Hs < 0 || Cn < 1) return -1;
+  return nr::lt::layout(dtype, B, U, Hs).total + nr::lt::contrastive_extra(B, Cn).total;
+}
+
+extern "C" int nr_latent_train_step_contrastive(const nr_latent_train_args* args, const nr_contrastive_spec* spec,
+                                                void* ws, int64_t ws_bytes, void* stream) {
+  return latent_train_entry("nr_latent_train_step_contrastive", args, spec, true, ws, ws_bytes, stream);
 }

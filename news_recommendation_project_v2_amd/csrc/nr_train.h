@@ -77,6 +77,61 @@ struct CosMargin {
   }
 };
 
+// ----------------------------------------------------------------- cosine + InfoNCE loss
+// The contrastive stage (contrastive.hip) keeps the same cosine as CosMargin in
+// factored form: a row v becomes its unit vector vh = v * inv with inv = 1 /
+// max(|v|, 1e-8) and the clamp indicator live = [|v| > 1e-8] (CosMargin's iu / cu),
+// the logits are products of unit vectors, and a gradient dvh into the unit vector
+// goes back as dv = inv (dvh - live (dvh . vh) vh) -- CosMargin::du / dpos summed
+// over the row's columns.
+struct CosUnit {
+  float inv, live;
+  __device__ __forceinline__ explicit CosUnit(float sumsq) {
+    constexpr float EPS = 1e-8f;
+    const float n = sqrtf(sumsq);
+    inv = 1.0f / fmaxf(n, EPS);
+    live = n > EPS ? 1.f : 0.f;
+  }
+  __device__ __forceinline__ CosUnit(float inv_, float live_) : inv(inv_), live(live_) {}
+  // dot = dvh . vh over the whole row
+  __device__ __forceinline__ float bwd(float dvh, float vh, float dot) const { return inv * (dvh - live * dot * vh); }
+};
+// One row of CrossEntropyLoss (mean over B rows) over logits z with the row maximum
+// m and s = sum exp(z - m) over the included columns: the row's loss term and
+// dz = (softmax - onehot) / B.  A row whose only included column is its target has
+// s = 1 and m = z_target: term 0 and dz 0 exactly.
+struct SoftmaxCE {
+  float m, inv_s, log_s, fB;
+  __device__ __forceinline__ SoftmaxCE(float m_, float s, int64_t B) : m(m_), inv_s(1.0f / s), log_s(logf(s)), fB((float)B) {}
+  __device__ __forceinline__ float loss_term(float z_target) const { return (log_s + (m - z_target)) / fB; }
+  __device__ __forceinline__ float dz(float z, bool is_target) const {
+    return (expf(z - m) * inv_s - (is_target ? 1.f : 0.f)) / fB;
+  }
+};
+
+// The stage itself (contrastive.hip), shared by nr_cosine_infonce and the
+// contrastive train steps.  Candidate rows E_c come either from an f32 table
+// (E, lde) or, with tok, as the token LN of tok[cand[c]] (tok_dtype; tg / tb its
+// affine), in which case the candidates' part of the token LN parameter grads is
+// written as kCnLnChunks chunk partials [k][2][1024] into ln_part (pair_ln_kernel's
+// layout: ln_reduce_kernel sums them).  loss, du [B][1024] and (nullable) dE_cols
+// [Cn][1024], logits_out [B][Cn] are written whole.
+constexpr int kCnLnChunks = 8;
+struct CnSpec {
+  int64_t B, Cn, U;  // U: rows the candidates index (0 = not known: cand is not range-checked)
+  const int32_t* cand;
+  const int32_t* target;
+  const uint8_t* mask;
+  float inv_tau;
+};
+int64_t contrastive_ws_bytes(int64_t B, int64_t Cn, bool from_tokens, bool own_dE);
+// range checks of B / Cn, null and device checks of the spec's pointers, then target / cand /
+// mask read back and every target (and, with U, every candidate) checked; no launch
+int contrastive_check(const char* fn, const CnSpec& sp, hipStream_t st);
+int contrastive_stage(const char* fn, const CnSpec& sp, const float* users, const float* E, int64_t lde,
+                      const void* tok, int tok_dtype, const float* tg, const float* tb, float* logits_out,
+                      float* loss, float* du, float* dE_cols, float* ln_part, char* ws, hipStream_t st);
+
 // ----------------------------------------------------------------- LayerNorm backward
 // dx = rstd (dxh - mean(dxh) - xhat mean(dxh xhat)) of a row held as row_stats4
 // holds it (one wave per row, NJ groups of 4 columns per lane), without the

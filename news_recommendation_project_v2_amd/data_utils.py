@@ -617,17 +617,163 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     store_processed_data(args.data_dir, NewsDataset[args.news_dataset])
 
 
-# The InfoNCE / classification experiments' data helpers:
+# --------------------------------------------------------------- InfoNCE training data
+def split_impressions_pos_neg_infonce(rng: np.random.Generator, grouped_news_rev_index, labels,
+                                      num_neg_per_pos: int = 5) -> np.ndarray:
+    """One row per POSITIVE of every impression with ``num_neg_per_pos`` negatives of
+    the same impression (data_utils.py:275-334).
+
+    An impression with at least K = num_neg_per_pos negatives draws K of them
+    without replacement for each positive (one ``rng.choice`` per positive, in
+    order: the reference's generator calls); one with fewer lists all of them
+    and pads with -1, drawing nothing.  Returns int32 [K + 2, rows]: the positive,
+    the K negatives (-1 = pad), the impression row.
+    """
+    K = num_neg_per_pos
+    pos_all, counts = [], []
+    neg_cols = [[] for _ in range(K)]
+    for i, row in enumerate(labels):
+        cand = grouped_news_rev_index[i]
+        pos = [cand[j] for j, y in enumerate(row) if y != 0]
+        neg = [cand[j] for j, y in enumerate(row) if y == 0]
+        n_neg = len(row) - sum(row)
+        drawn = []
+        for _ in pos:
+            if n_neg >= K:
+                drawn.extend(rng.choice(neg, size=K, replace=False).tolist())
+            else:
+                drawn.extend(neg + [-1] * (K - n_neg))
+        pos_all.extend(pos)
+        for j in range(K):
+            neg_cols[j].extend(drawn[j::K])
+        counts.append(sum(row))
+    rows = np.repeat(np.arange(len(counts)), counts).astype(np.int32)
+    return np.stack([np.array(pos_all, dtype=np.int32), *(np.array(c, dtype=np.int32) for c in neg_cols), rows])
+
+
+class FinalAttentionTrainInfoNCEDataset(Dataset):
+    """(history group, [positive, K negatives]) training rows (data_utils.py:512-578).
+
+    ``reset`` permutes impressions, draws the negatives and permutes whole batches
+    except the last one, with the reference's generator call order;
+    ``batches`` / ``positives_of`` are this package's additions (the DataLoader
+    batch ranges, and the clicked news of a row's impression for the in-batch
+    form's false-negative mask)."""
+
+    def __init__(self, history_rev_index, history_len_list, news_rev_index, impression_len_list, labels,
+                 batch_size: int, num_neg_per_pos: int = 5, rng=None):
+        assert len(history_len_list) == len(impression_len_list), "Number of rows should match between history and news"
+        assert sum(impression_len_list) == len(news_rev_index), \
+            "Number of impressions should match length of impression list"
+        self.group_history = group_items(history_rev_index, history_len_list)
+        self.batch_size = batch_size
+        self.labels = labels
+        self.news_rev_index = news_rev_index
+        self.impression_len_list = impression_len_list
+        self.rng = rng if rng is not None else np.random.default_rng(1234)
+        self.num_neg_per_pos = num_neg_per_pos
+        self.reset()
+
+    def __len__(self):
+        return len(self.pos_neg_indices)
+
+    def __getitem__(self, idx):
+        return self.group_history[self.pos_neg_indices[idx, -1]], self.pos_neg_indices[idx, :-1]
+
+    def reset(self):
+        perm = self.rng.permutation(len(self.labels))
+        pni = split_impressions_pos_neg_infonce(
+            self.rng, group_items(self.news_rev_index, self.impression_len_list)[perm], self.labels[perm],
+            self.num_neg_per_pos)
+        pni[-1] = perm[pni[-1]]
+        total = pni.shape[1]
+        n_batches = -(total // -self.batch_size)
+        order = self.rng.permutation(n_batches - 1).tolist() + [n_batches - 1]
+        sel = (np.asarray(order, dtype=np.int64)[:, None] * self.batch_size
+               + np.arange(self.batch_size)[None, :]).ravel()[:total]
+        self.pos_neg_indices = pni[:, sel].T
+
+    def batches(self):
+        """Row ranges of the DataLoader batches (shuffle=False, in order)."""
+        n = len(self)
+        return [(s, min(n, s + self.batch_size)) for s in range(0, n, self.batch_size)]
+
+    def positives_of(self, idx) -> np.ndarray:
+        """Every clicked news of row ``idx``'s impression."""
+        imp = int(self.pos_neg_indices[idx, -1])
+        cand = group_items(self.news_rev_index, self.impression_len_list)[imp]
+        return np.asarray([cand[j] for j, y in enumerate(self.labels[imp]) if y != 0], dtype=np.int64)
+
+
+def final_attention_train_infonce_collate_fn(input):
+    """Batch -> (padded unique histories, their mask, each row's unique-history index,
+    [B, 1 + K] positive ‖ negatives news indices) (data_utils.py:794-817; histories
+    are made unique through their comma-joined text, so they come sorted as strings)."""
+    grouped_history, news_ind_pos_neg = zip(*input)
+    uniq, rev = np.unique([",".join(np.asarray(h).astype(str)) for h in grouped_history], return_inverse=True)
+    padded = pad_to_maxlen([[int(i) for i in s.split(",")] for s in uniq])
+    return (torch.tensor(padded["indices"], dtype=torch.int32),
+            torch.tensor(padded["attention_mask"], dtype=torch.int32),
+            torch.tensor(rev, dtype=torch.int32),
+            torch.tensor(np.array(news_ind_pos_neg), dtype=torch.int32))
+
+
+def contrastive_batch_csr(conn, rows, negatives: str = "sampled", positives_of_row=None, maxlen: Optional[int] = None):
+    """A batch of ``FinalAttentionTrainInfoNCEDataset`` rows in the CSR form of
+    train_step.ContrastiveBatch: ``train_batch_csr``'s (last token rows [U, D],
+    history indices [Hs], offsets [B + 1]) plus the InfoNCE stage's inputs
+
+      cand   int32 [B (1 + K)]   the row-major [B, 1 + K] block of positive ‖ negatives
+                                 as indices into the U rows, -1 for a pad
+      target int32 [B]           row b's positive: column b (1 + K)
+      mask   uint8 [B, B (1 + K)]  1 = the column is left out of row b's softmax
+
+    ``negatives="sampled"`` is the reference's commented loss (trainer.py:612-625):
+    row b sees its own block only.  ``"in_batch"``: row b sees every column but the
+    pads and the false negatives -- columns other than its target whose news is a
+    clicked candidate of row b's impression (``positives_of_row[b]``, news ids)."""
+    from .config import NEWS_TEXT_MAXLEN
+    if negatives not in ("sampled", "in_batch"):
+        raise ValueError("negatives must be 'sampled' or 'in_batch'")
+    maxlen = maxlen or NEWS_TEXT_MAXLEN
+    grouped_history, pos_neg = zip(*rows)
+    lens = np.array([len(h) for h in grouped_history], dtype=np.int64)
+    news = np.array(pos_neg, dtype=np.int64)                      # [B, 1 + K], -1 pads
+    B, width = news.shape
+    flat = news.ravel()
+    real = flat >= 0
+    uniq, rev = np.unique(np.concatenate(list(grouped_history) + [flat[real]]), return_inverse=True)
+    ids = ",".join(str(int(i) + 1) for i in uniq)
+    res = conn.execute(f"SELECT data FROM tensors WHERE id IN ({ids}) ORDER BY id;").fetchall()
+    if len(res) != len(uniq):
+        raise IndexError(f"token DB returned {len(res)} rows for {len(uniq)} requested news ids")
+    last = torch.stack([t[min(len(t), maxlen) - 1] for t in (read_token_blob(r[0]) for r in res)])
+    Hs = int(lens.sum())
+    cand = np.full(B * width, -1, dtype=np.int32)
+    cand[real] = rev[Hs:]
+    target = (np.arange(B) * width).astype(np.int32)
+    if negatives == "sampled":
+        mask = np.ones((B, B * width), dtype=np.uint8)
+        for b in range(B):
+            mask[b, b * width:(b + 1) * width] = 0
+        mask[:, ~real] = 1
+    else:
+        if positives_of_row is None or len(positives_of_row) != B:
+            raise ValueError("in-batch negatives need positives_of_row: each row's clicked news")
+        mask = np.zeros((B, B * width), dtype=np.uint8)
+        mask[:, ~real] = 1
+        for b in range(B):
+            mask[b, np.isin(flat, np.asarray(positives_of_row[b], dtype=np.int64)) & real] = 1
+            mask[b, target[b]] = 0
+    return last, rev[:Hs].astype(np.int32), lengths_to_offsets(lens), cand, target, mask
+
+
+# The classification experiments' data helpers (SURVEY §8(f)4):
 # import-level placeholders only.
 from .out_of_scope import placeholder_class as _oos_cls, placeholder_function as _oos_fn  # noqa: E402
 
 split_impressions = _oos_fn("split_impressions", "data_utils.py:235-272", __name__)
-split_impressions_pos_neg_infonce = _oos_fn("split_impressions_pos_neg_infonce", "data_utils.py:275-334", __name__)
-final_attention_train_infonce_collate_fn = _oos_fn("final_attention_train_infonce_collate_fn", "data_utils.py:794-817",
-                                                   __name__)
 final_attention_train_collate_fn = _oos_fn("final_attention_train_collate_fn", "data_utils.py:820-843", __name__)
-FinalAttentionTrainInfoNCEDataset = _oos_cls("FinalAttentionTrainInfoNCEDataset", "data_utils.py:512-578", __name__,
-                                             Dataset)
 ClassificationTrainInfoNCEDataset = _oos_cls("ClassificationTrainInfoNCEDataset", "data_utils.py:648-685", __name__,
                                              Dataset)
 ClassificationTrainDataset = _oos_cls("ClassificationTrainDataset", "data_utils.py:688-720", __name__, Dataset)

@@ -611,6 +611,44 @@ def cosine_margin(users: torch.Tensor, E: torch.Tensor, pos: torch.Tensor, neg: 
               ctypes.c_float(margin), _ptr(s_out), _ptr(loss), _ptr(du), _ptr(dE), _stream(dev))
 
 
+def _check_contrastive(cand, target, mask, B: int):
+    """dtype / shape checks of the InfoNCE stage's index tensors; returns Cn."""
+    if cand.dtype != torch.int32 or target.dtype != torch.int32 or not cand.is_contiguous() or not target.is_contiguous():
+        raise _lib.NewsRecHIPError("cand and target must be contiguous int32")
+    Cn = cand.numel()
+    if target.numel() != B:
+        raise _lib.NewsRecHIPError(f"target must have one column per batch row ({target.numel()} != {B})")
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or tuple(mask.shape) != (B, Cn)):
+        raise _lib.NewsRecHIPError(f"mask must be a contiguous uint8 [{B}, {Cn}] tensor")
+    return Cn
+
+
+def cosine_infonce(users: torch.Tensor, E: torch.Tensor, cand: torch.Tensor, target: torch.Tensor,
+                   mask: Optional[torch.Tensor] = None, temperature: float = 1.0, want_logits: bool = False):
+    """InfoNCE over in-batch candidate columns (nr_cosine_infonce, the sibling of
+    ``cosine_margin``; trainer.py:612-625): users [B, 1024] f32, E [U, >= 1024] f32,
+    cand [Cn] int32 (-1 = pad), target [B] int32, mask None or uint8 [B, Cn] (1 =
+    left out).  Returns (loss [1], du [B, 1024], dE_cols [Cn, 1024] -- per column,
+    not scattered -- and the logits [B, Cn] with -inf where excluded, or None)."""
+    dev = _dev(users, E, cand, target, mask)
+    if users.dtype != torch.float32 or E.dtype != torch.float32 or not users.is_contiguous() or users.shape[1] != 1024:
+        raise _lib.NewsRecHIPError("users must be contiguous float32 [B, 1024] and E float32")
+    B = users.shape[0]
+    Cn = _check_contrastive(cand, target, mask, B)
+    need = int(_lib.load().nr_cosine_infonce_workspace_bytes(B, Cn))
+    if need < 0:
+        raise _lib.NewsRecHIPError(f"nr_cosine_infonce: bad shape B = {B}, Cn = {Cn}")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    du = torch.empty((B, 1024), dtype=torch.float32, device=dev)
+    dE = torch.empty((Cn, 1024), dtype=torch.float32, device=dev)
+    logits = torch.empty((B, Cn), dtype=torch.float32, device=dev) if want_logits else None
+    _lib.call("nr_cosine_infonce", B, Cn, _ptr(users), _ptr(E), _rowmajor(E, "E"), _ptr(cand), _ptr(target), _ptr(mask),
+              ctypes.c_float(1.0 / temperature), _ptr(logits), _ptr(loss), _ptr(du), _ptr(dE), _ptr(ws), ws.numel(),
+              _stream(dev))
+    return loss, du, dE, logits
+
+
 def scatter_add_rows(src: torch.Tensor, idx: torch.Tensor, dst: torch.Tensor) -> None:
     dev = _dev(src, idx, dst)
     _lib.call("nr_scatter_add_rows", _dtype(src, "src"), idx.numel(), src.shape[1], _ptr(src), _rowmajor(src, "src"),

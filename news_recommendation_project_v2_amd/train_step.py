@@ -76,6 +76,21 @@ class TrainBatch:
         return self.pos.numel()
 
 
+@dataclass
+class ContrastiveBatch:
+    """A ``TrainBatch`` (its ``pos`` / ``neg`` are not read; ``None`` is fine) plus the
+    InfoNCE loss's inputs (data_utils.contrastive_batch_csr):
+
+    cand    [Cn] int32        candidate columns, indices into the U rows, -1 = pad
+    target  [B] int32         the column of each row's positive
+    mask    [B, Cn] uint8     1 = the column is left out for that row; None = no mask
+    """
+    batch: TrainBatch
+    cand: torch.Tensor
+    target: torch.Tensor
+    mask: Optional[torch.Tensor] = None
+
+
 def _check_loss_out(t: torch.Tensor, dev) -> torch.Tensor:
     d = torch.device(dev)
     if (t.dtype != torch.float32 or t.numel() < 1 or not t.is_contiguous() or t.device.type != d.type
@@ -96,12 +111,17 @@ class _FlatTrainStep:
     _args: type           # the native step's args struct (_lib.*TrainArgs)
     _step_fn: str         # library entry points: the step and its workspace size
     _workspace_fn: str
+    _contrastive_fn: Optional[str] = None  # the step with the InfoNCE loss (ContrastiveBatch), when it has one
     _pmap: dict           # struct field -> parameter name (``g_`` + field is its gradient)
     _mirrored: tuple      # the fields read in the compute dtype (``cviews``), the GEMM weights
 
-    def __init__(self, token_model, pooler, dtype, lr, betas, eps, weight_decay, max_norm, seed, device):
+    def __init__(self, token_model, pooler, dtype, lr, betas, eps, weight_decay, max_norm, seed, device,
+                 temperature: float = 1.0):
         if dtype not in (torch.float32, torch.bfloat16):
             raise NewsRecHIPError(f"{self._what} dtype must be float32 or bfloat16")
+        if not temperature > 0:
+            raise NewsRecHIPError("temperature must be positive")
+        self.temperature = float(temperature)  # tau of the InfoNCE loss (ContrastiveBatch steps)
         layers = list(token_model.encoder.layer)
         if len(layers) != 1:
             raise NewsRecHIPError("training supports NUM_HIDDEN_LAYERS == 1 (config.py:35)")
@@ -154,39 +174,68 @@ class _FlatTrainStep:
                 self.flat16.copy_(self.flat)
         self._mirror_version = v
 
-    def forward_backward(self, batch: TrainBatch, loss_out: torch.Tensor | None = None):
+    def forward_backward(self, batch: "TrainBatch | ContrastiveBatch", loss_out: torch.Tensor | None = None):
         """Loss (device scalar, written to ``loss_out`` when given) and gradients
-        into ``self.grad`` as ONE library call: the forward, the margin loss and the
-        whole backward of the batch.  The step rewrites every gradient slice, so there
-        is no ``grad.zero_()`` (the alignment gaps stay zero from construction).
+        into ``self.grad`` as ONE library call: the forward, the loss -- the margin
+        loss of a ``TrainBatch``, InfoNCE at ``self.temperature`` over the candidate
+        columns of a ``ContrastiveBatch`` -- and the whole backward of the batch.  The
+        step rewrites every gradient slice, so there is no ``grad.zero_()`` (the
+        alignment gaps stay zero from construction).
         Returns (loss, users, None): users = the pooled users [B, D] f32.  Both are
         views of buffers the next call overwrites in place (on the stream); clone
         them to keep a step's values."""
-        U, B, Hs = batch.tok_last.shape[0], batch.B, batch.hist_idx.numel()
+        spec = None
+        if isinstance(batch, ContrastiveBatch):
+            if self._contrastive_fn is None:
+                raise NewsRecHIPError(f"the {self._what} has no contrastive entry")
+            cb, batch = batch, batch.batch
+            B = batch.hist_off.numel() - 1
+            spec = _lib.ContrastiveSpec()
+            spec.Cn = ops._check_contrastive(cb.cand, cb.target, cb.mask, B)
+            ops._dev(cb.cand, cb.target, cb.mask, batch.tok_last)
+            spec.cand, spec.target = cb.cand.data_ptr(), cb.target.data_ptr()
+            spec.mask = cb.mask.data_ptr() if cb.mask is not None else None
+            spec.inv_tau = 1.0 / self.temperature
+        else:
+            B = batch.B
+        U, Hs = batch.tok_last.shape[0], batch.hist_idx.numel()
         lib = _lib.load()
         self._refresh_mirror()
         dt = ops.TOKEN_DT[self.dtype]
         with torch.cuda.device(self.device):  # the native layout depends on the current device's CU count
-            need = int(getattr(lib, self._workspace_fn)(dt, B, U, Hs))
+            if spec is None:
+                need = int(getattr(lib, self._workspace_fn)(dt, B, U, Hs))
+            else:
+                need = int(getattr(lib, self._contrastive_fn + "_workspace_bytes")(dt, B, U, Hs, spec.Cn))
         self._ws = ops.grow_workspace(self._ws, need, self.device)
         if self._users is None or self._users.shape[0] < B:
             self._users = torch.empty((B, D), dtype=torch.float32, device=self.device)
         tok = batch.tok_last.contiguous()
         hi, ho = batch.hist_idx.to(torch.int32).contiguous(), batch.hist_off.to(torch.int64).contiguous()
-        pos, neg = batch.pos.to(torch.int32).contiguous(), batch.neg.to(torch.int32).contiguous()
+        if spec is None:
+            pos, neg = batch.pos.to(torch.int32).contiguous(), batch.neg.to(torch.int32).contiguous()
+        else:
+            pos = neg = None  # (not read by the contrastive entry)
         a = self._args()
         a.dtype, a.tok_dtype, a.B, a.U, a.Hs, a.margin = dt, ops.TOKEN_DT[tok.dtype], B, U, Hs, MARGIN
         self._fill_args(a)
-        a.tok_last, a.hist_idx, a.hist_off, a.pos, a.neg = (t.data_ptr() for t in (tok, hi, ho, pos, neg))
+        a.tok_last, a.hist_idx, a.hist_off = (t.data_ptr() for t in (tok, hi, ho))
+        a.pos, a.neg = (t.data_ptr() if t is not None else None for t in (pos, neg))
         for f, name in self._pmap.items():
             src = self.cviews if f in self._mirrored else self.views
             setattr(a, f, src[name].data_ptr())
             setattr(a, "g_" + f, self.gviews[name].data_ptr())
         loss = self.loss if loss_out is None else _check_loss_out(loss_out, self.device)
         a.loss, a.users, a.sumsq = loss.data_ptr(), self._users.data_ptr(), self.sumsq.data_ptr()
-        _lib.check(getattr(lib, self._step_fn)(ctypes.byref(a), self._ws.data_ptr(), self._ws.numel(),
-                                               torch.cuda.current_stream(self.device).cuda_stream), self._step_fn)
-        self._keep = (tok, hi, ho, pos, neg)  # alive until the stream has run the step
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if spec is None:
+            _lib.check(getattr(lib, self._step_fn)(ctypes.byref(a), self._ws.data_ptr(), self._ws.numel(), stream),
+                       self._step_fn)
+        else:
+            _lib.check(getattr(lib, self._contrastive_fn)(ctypes.byref(a), ctypes.byref(spec), self._ws.data_ptr(),
+                                                          self._ws.numel(), stream), self._contrastive_fn)
+        # alive until the stream has run the step
+        self._keep = (tok, hi, ho, pos, neg, cb if spec is not None else None)
         return loss, self._users[:B], None
 
     def optimizer_step(self) -> None:
@@ -199,7 +248,7 @@ class _FlatTrainStep:
         if hasattr(self.pooler, "_hip_cache"):
             self.pooler._hip_cache = {}  # keyed on data_ptr() and _version, which AdamW moved neither of
 
-    def step(self, batch: TrainBatch) -> torch.Tensor:
+    def step(self, batch: "TrainBatch | ContrastiveBatch") -> torch.Tensor:
         """One full step; returns this step's loss as its own device scalar (a
         fresh allocation the step writes, so no copy launch)."""
         out = torch.empty(1, dtype=torch.float32, device=self.device)
@@ -215,6 +264,7 @@ class FinalAttentionTrainStep(_FlatTrainStep):
     """The module docstring's step: ``FinalAttention`` pools (``nr_final_train_step``, csrc/final_train.hip)."""
 
     _args, _step_fn, _workspace_fn = _lib.FinalTrainArgs, "nr_final_train_step", "nr_final_train_workspace_bytes"
+    _contrastive_fn = "nr_final_train_step_contrastive"
     _pmap = {"tok_g": "ln.weight", "tok_b": "ln.bias", "W5": "linear5.weight",
              **{f"W{i}": f"linear{i}.weight" for i in range(1, 5)},
              **{f"b{i}": f"linear{i}.bias" for i in range(1, 5)}}
@@ -222,8 +272,9 @@ class FinalAttentionTrainStep(_FlatTrainStep):
 
     def __init__(self, token_model, final_attention, dtype: torch.dtype = torch.bfloat16, lr: float = 1e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01, max_norm: float = 0.5,
-                 dropout: float = DROP_P, seed: int = 1234, device=None):
-        super().__init__(token_model, final_attention, dtype, lr, betas, eps, weight_decay, max_norm, seed, device)
+                 dropout: float = DROP_P, seed: int = 1234, device=None, temperature: float = 1.0):
+        super().__init__(token_model, final_attention, dtype, lr, betas, eps, weight_decay, max_norm, seed, device,
+                         temperature)
         # CUs the persistent GEMMs spread one 256x256 tile round over (multiple of the 8 XCDs)
         self._ncu = torch.cuda.get_device_properties(self.device).multi_processor_count // 8 * 8
         self.p = dropout
@@ -337,6 +388,7 @@ class LatentAttentionTrainStep(_FlatTrainStep):
 
     _what, _prefix = "latent-attention train step", "latent."
     _args, _step_fn, _workspace_fn = _lib.LatentTrainArgs, "nr_latent_train_step", "nr_latent_train_workspace_bytes"
+    _contrastive_fn = "nr_latent_train_step_contrastive"
     _pmap = {"tok_g": "ln.weight", "tok_b": "ln.bias", "latents": "latent.latents",
              "nq_g": _BLK + "0.norm.weight", "nq_b": _BLK + "0.norm.bias",
              "nc_g": _BLK + "0.norm_context.weight", "nc_b": _BLK + "0.norm_context.bias",
@@ -348,9 +400,10 @@ class LatentAttentionTrainStep(_FlatTrainStep):
 
     def __init__(self, token_model, latent_model, dtype: torch.dtype = torch.float32, lr: float = 1e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01, max_norm: float = 0.5,
-                 seed: int = 1234, device=None):
+                 seed: int = 1234, device=None, temperature: float = 1.0):
         # (no dropout argument: LatentAttentionModel has no dropout, latent_attention.py:77-171)
-        super().__init__(token_model, latent_model, dtype, lr, betas, eps, weight_decay, max_norm, seed, device)
+        super().__init__(token_model, latent_model, dtype, lr, betas, eps, weight_decay, max_norm, seed, device,
+                         temperature)
         self.model = latent_model
         if abs(self.ln_eps - 1e-12) > 1e-18:
             raise NewsRecHIPError("the token LayerNorm of MyLayer has eps 1e-12 (attention.py:155)")

@@ -12,6 +12,19 @@ batch rows, trainer.py:1073-1074) is appended to
 saved as ``{ckpt_dir}/Epoch_{i}.pt`` (locally: the Azure blob upload of
 trainer.py:1172-1197 is out of scope).
 
+``loss="infonce"`` trains with the reference's other loss for this data, the
+commented cross-entropy over cosine logits of trainer.py:612-625: the training set
+is ``FinalAttentionTrainInfoNCEDataset`` (one row per positive with
+``num_neg_per_pos`` sampled negatives of its impression), and every row's softmax
+runs over its own block (``negatives="sampled"``, the commented code exactly) or
+over every candidate column of the batch but the pads and the row's other clicked
+news (``negatives="in_batch"``), at ``temperature``.  The default ``loss="margin"``
+is the run described above, unchanged.  Unlike the margin step, every InfoNCE step
+synchronises the host with the device once: the native entry reads ``cand``, ``target``
+and ``mask`` back (B x Cn mask bytes, 393 KB at B = 256, K = 5) to refuse a bad target
+before it launches anything, so with ``loss="infonce"`` the host does not run ahead of
+the device between batches (the losses still stay on the device until the NaN check).
+
 The reference sizes the batch with a GPU OOM probe
 (batch_size_finder.get_attention_attention_train_batch_size); here it is an
 argument (HBM is not the constraint at these shapes).
@@ -29,8 +42,9 @@ import numpy as np
 import torch
 
 from .config import DEVICE
-from .data_utils import FinalAttentionTrainDataset, lengths_to_offsets, train_batch_csr
-from .train_step import FinalAttentionTrainStep, LatentAttentionTrainStep, TrainBatch
+from .data_utils import (FinalAttentionTrainDataset, FinalAttentionTrainInfoNCEDataset, contrastive_batch_csr,
+                         lengths_to_offsets, train_batch_csr)
+from .train_step import ContrastiveBatch, FinalAttentionTrainStep, LatentAttentionTrainStep, TrainBatch
 
 DEFAULT_TRAIN_BATCH = 256
 
@@ -44,7 +58,13 @@ class AttentionAttentionTrainer:
                  max_neg_ratio: Optional[float] = None, max_pos_ratio: Optional[float] = None,
                  rng: Optional[np.random.Generator] = None, batch_size: int = DEFAULT_TRAIN_BATCH,
                  dtype: torch.dtype = torch.float32, lr: float = 1e-6, dropout: float = 0.1, seed: int = 1234,
-                 nan_check_every: Optional[int] = None):
+                 nan_check_every: Optional[int] = None, loss: str = "margin", negatives: str = "sampled",
+                 num_neg_per_pos: int = 5, temperature: float = 1.0):
+        if loss not in ("margin", "infonce"):
+            raise ValueError("loss must be 'margin' or 'infonce'")
+        if negatives not in ("sampled", "in_batch"):
+            raise ValueError("negatives must be 'sampled' or 'in_batch'")
+        self.loss, self.negatives = loss, negatives
         if nan_check_every is not None:
             if int(nan_check_every) < 1:
                 raise ValueError("nan_check_every must be >= 1")
@@ -60,21 +80,45 @@ class AttentionAttentionTrainer:
         if getattr(final_attention_model, "pooler_kind", "final") == "latent":
             # BASELINE configs[4]'s pairing: token encoder + LatentAttentionModel
             self.engine = LatentAttentionTrainStep(token_attention_model, final_attention_model, dtype=dtype, lr=lr,
-                                                   seed=seed, device=DEVICE)
+                                                   seed=seed, device=DEVICE, temperature=temperature)
         else:
             self.engine = FinalAttentionTrainStep(token_attention_model, final_attention_model, dtype=dtype, lr=lr,
-                                                  dropout=dropout, seed=seed, device=DEVICE)
-        self.train_dataset = FinalAttentionTrainDataset(
+                                                  dropout=dropout, seed=seed, device=DEVICE, temperature=temperature)
+        if loss == "infonce":
+            self.train_dataset = FinalAttentionTrainInfoNCEDataset(
+                history_rev_index=train_history_rev_index, history_len_list=train_history_len_list,
+                news_rev_index=train_news_rev_index, impression_len_list=train_impression_len_list,
+                labels=train_labels, batch_size=batch_size, num_neg_per_pos=num_neg_per_pos, rng=self.rng)
+        else:
+            self.train_dataset = self._margin_dataset(train_history_rev_index, train_history_len_list,
+                                                      train_news_rev_index, train_impression_len_list, train_labels,
+                                                      batch_size, max_neg_ratio, max_pos_ratio)
+        self.connection = sqlite3.connect(str(db_name))
+
+    def _margin_dataset(self, train_history_rev_index, train_history_len_list, train_news_rev_index,
+                        train_impression_len_list, train_labels, batch_size, max_neg_ratio, max_pos_ratio):
+        return FinalAttentionTrainDataset(
             history_rev_index=train_history_rev_index, history_len_list=train_history_len_list,
             news_rev_index=train_news_rev_index, impression_len_list=train_impression_len_list,
             labels=train_labels, batch_size=batch_size, max_neg_raio=max_neg_ratio, max_pos_ratio=max_pos_ratio,
             rng=self.rng)
-        self.connection = sqlite3.connect(str(db_name))
 
-    def device_batch(self, lo: int, hi: int) -> TrainBatch:
+    def host_batch(self, lo: int, hi: int):
+        """Rows lo..hi-1 as contrastive_batch_csr returns them (``loss="infonce"``)."""
+        rows = [self.train_dataset[i] for i in range(lo, hi)]
+        clicks = [self.train_dataset.positives_of(i) for i in range(lo, hi)] if self.negatives == "in_batch" else None
+        return contrastive_batch_csr(self.connection, rows, self.negatives, clicks)
+
+    def device_batch(self, lo: int, hi: int) -> "TrainBatch | ContrastiveBatch":
+        d = DEVICE
+        if self.loss == "infonce":
+            last, hidx, hoff, cand, target, mask = self.host_batch(lo, hi)
+            tb = TrainBatch(tok_last=last.to(d).contiguous(), hist_idx=torch.as_tensor(hidx).to(d),
+                            hist_off=torch.as_tensor(hoff).to(d), pos=None, neg=None)
+            return ContrastiveBatch(tb, torch.as_tensor(cand).to(d), torch.as_tensor(target).to(d),
+                                    torch.as_tensor(mask).to(d))
         rows = [self.train_dataset[i] for i in range(lo, hi)]
         last, hidx, hoff, pos, neg = train_batch_csr(self.connection, rows)
-        d = DEVICE
         return TrainBatch(tok_last=last.to(d).contiguous(), hist_idx=torch.as_tensor(hidx).to(d),
                           hist_off=torch.as_tensor(hoff).to(d), pos=torch.as_tensor(pos).to(d),
                           neg=torch.as_tensor(neg).to(d))

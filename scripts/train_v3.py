@@ -8,7 +8,11 @@ logs/train_final_history_score.jsonl.
 Flags (the reference hard-codes them): --data-dir --db-name --log-dir --ckpt-dir
 --epochs --batch-size --dtype {fp32,bf16} --num-impressions --store-db
 (--model-path) to (re)build the sqlite token-state DB with the title encoder
-first.  --synthetic: seeded MIND-shaped behaviours and a synthetic token DB
+first.  --loss infonce trains with the reference's commented loss (trainer.py:612-625:
+cross-entropy over cosine logits of one positive and --num-neg-per-pos sampled
+negatives) instead of the margin loss; --negatives in_batch widens each row's
+softmax to every candidate of the batch but the pads and the row's other clicks;
+--temperature is its tau.  --synthetic: seeded MIND-shaped behaviours and a synthetic token DB
 (fp16 N(0,1) states, 20 +- 6 tokens per title), no data or checkpoints needed.
 """
 from __future__ import annotations
@@ -60,6 +64,10 @@ def main():
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--pooler", choices=["final", "latent"], default="final",
                     help="latent: LatentAttentionModel in FinalAttention's slot (BASELINE configs[4])")
+    ap.add_argument("--loss", choices=["margin", "infonce"], default="margin")
+    ap.add_argument("--negatives", choices=["sampled", "in_batch"], default="sampled", help="with --loss infonce")
+    ap.add_argument("--temperature", type=float, default=1.0, help="with --loss infonce")
+    ap.add_argument("--num-neg-per-pos", type=int, default=5, help="with --loss infonce")
     args = ap.parse_args()
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     rng = np.random.default_rng(1234)
@@ -83,7 +91,8 @@ def main():
                                        token_ckpt_dir=args.ckpt_dir / "token_attn",
                                        final_attn_ckpt_dir=args.ckpt_dir / "final_attn", exp_name=args.exp_name,
                                        num_epochs=args.epochs, rng=rng, batch_size=args.batch_size, dtype=dtype,
-                                       pooler=args.pooler)
+                                       pooler=args.pooler, loss=args.loss, negatives=args.negatives,
+                                       temperature=args.temperature, num_neg_per_pos=args.num_neg_per_pos)
     steps.append(("attn_attn", comp))
     t0 = time.time()
     Pipeline("train_subset", steps).train(ctx)
