@@ -58,6 +58,9 @@ int gather_ln_dispatch(int dti, int64_t n, int64_t dim, const void* x, int64_t l
                        int n_ln, const float* g, const float* b, float eps, float* y, int64_t ldy, hipStream_t s);
 int pool_rows_dispatch(int pooler, int dtype, const void* table, int64_t ld, const int64_t* off, int64_t n_seg,
                        float* users, hipStream_t s);
+int score_users_dispatch(int dtype, const float* users, const int32_t* user_idx, const void* cand_table,
+                         int64_t cand_ld, const float* cand_inv_norm, const int32_t* cand_idx,
+                         const int64_t* cand_off, int64_t n_imp, float* scores, hipStream_t s);
 int row_stats_dispatch(int dtype, int64_t rows, int64_t dim, const void* x, int64_t ldx, float eps, float* out,
                        hipStream_t s);
 // bf16 persistent GEMM with a LayerNorm folded into its epilogue (epi NR_EPI_SOFTMAX64 or

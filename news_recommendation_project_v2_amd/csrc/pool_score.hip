@@ -282,6 +282,21 @@ int pool_rows_dispatch(int pooler, int dtype, const void* table, int64_t ld, con
   });
 }
 
+// The evaluation path's candidate scoring over stored user rows (nr_score_users, and
+// the exact re-score of nr_topk_users' survivors): impression i scores candidates
+// cand_idx[cand_off[i] .. cand_off[i+1]) against users[user_idx[i]].
+int score_users_dispatch(int dtype, const float* users, const int32_t* user_idx, const void* cand_table,
+                         int64_t cand_ld, const float* cand_inv_norm, const int32_t* cand_idx,
+                         const int64_t* cand_off, int64_t n_imp, float* scores, hipStream_t s) {
+  // the pooler only shaped the stored user vectors; the scoring pass is pooler-independent
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    return launch_pool_score<T, NR_POOL_MEAN, true>(nullptr, 0, cand_table, cand_ld, cand_inv_norm, nullptr, nullptr,
+                                                    cand_idx, cand_off, n_imp, scores, const_cast<float*>(users), s,
+                                                    user_idx);
+  });
+}
+
 }  // namespace nr
 
 extern "C" int nr_pool_score(int pooler, int dtype, int64_t dim, const void* hist_table,
@@ -344,12 +359,6 @@ extern "C" int nr_score_users(int dtype, int64_t dim, const float* users, const 
   NR_CHECK_DEVICE("nr_score_users", users, user_idx, cand_table, cand_inv_norm, cand_idx, cand_off, scores);
   NR_CHECK_ARG(cand_ld >= dim && cand_ld % (dtype == NR_F32 ? 4 : 8) == 0 && ((uintptr_t)cand_table & 15) == 0,
                "nr_score_users: cand_table must be 16-byte aligned with 16-byte row strides");
-  hipStream_t s = (hipStream_t)stream;
-  // the pooler only shaped the stored user vectors; the scoring pass is pooler-independent
-  return nr::with_dtype(dtype, [&](auto t) -> int {
-    using T = typename decltype(t)::type;
-    return nr::launch_pool_score<T, NR_POOL_MEAN, true>(nullptr, 0, cand_table, cand_ld, cand_inv_norm, nullptr,
-                                                        nullptr, cand_idx, cand_off, n_imp, scores,
-                                                        const_cast<float*>(users), s, user_idx);
-  });
+  return nr::score_users_dispatch(dtype, users, user_idx, cand_table, cand_ld, cand_inv_norm, cand_idx, cand_off, n_imp,
+                                  scores, (hipStream_t)stream);
 }

@@ -1,0 +1,572 @@
+// Top-K news retrieval over the whole table (include/newsrec_topk.h): users x table
+// as an MFMA GEMM whose U x N score matrix never reaches memory.
+//
+//   prep     NR_BF16 only: users f32 -> bf16 rows in the workspace (round to nearest even)
+//   stage 1  grid (user blocks of 128, runs of chunks of kChunk news rows).  A workgroup walks its
+//            chunks in 128-row tiles: gemm_kernel's main loop (gemm.hip: 128 x 128 tile, K in
+//            128-byte row slices through a two-stage LDS ring, the next slice's global loads
+//            in flight over the MFMAs; f32 on v_mfma_f32_32x32x2_f32, bf16 on
+//            v_mfma_f32_16x16x32_bf16) with the NEWS rows as the A operand, so a lane's
+//            accumulator registers are 4 consecutive news of one user.  Epilogue, per tile:
+//            scale by cand_inv (-inf past N), 16-byte stores into an LDS score tile that
+//            aliases the operand ring, then two threads per user scan the row against the
+//            user's running K-th best (-inf until K are kept) and the first of them keeps
+//            the few that pass and are not excluded in the user's list in LDS, a binary
+//            heap with the worst kept entry at the root.  A user's excluded rows inside
+//            the current chunk are staged in LDS once per chunk and looked up per passing
+//            candidate; a user with more than XCAP of them has its rows set to -inf in
+//            every score tile by the whole workgroup instead.  The list goes out
+//            rank-sorted as K (score, row) pairs per (user, run of chunks).
+//   stage 2  one wave per user: a K-round merge of the chunk lists' heads (ties by row),
+//            the survivors' rows (0 in place of a missing one: never row -1) to top_idx;
+//            the evaluation path's scoring kernel over them (score_users_dispatch) into
+//            top_scores; a rank sort of each row's <= 64 (score, row) pairs.
+//
+// Every comparison is on the strict total order (score descending, row ascending), so no
+// result depends on the order in which lanes or workgroups ran.
+#include "nr_common.h"
+
+#include "../../include/newsrec_topk.h"
+
+namespace nr {
+namespace tk {
+
+constexpr int64_t D = 1024;
+constexpr int64_t kChunk = 16384;  // news rows per stage-1 partial (< 2^16: exclusions are staged as 16-bit offsets)
+constexpr int kMaxChunks = 256;   // chunk heads the merge keeps per user (N <= 2^22)
+constexpr int kFillWorkgroups = 1024;  // stage-1 workgroups wanted before chunks are walked in sequence
+constexpr int XCAP = 32;          // excluded rows of one chunk staged in LDS per user (more: the global list is searched)
+constexpr int TS = 128;           // tile side: users and news rows per tile
+constexpr int ROWW = 36;          // LDS words per staged 128-byte row slice (144 B: conflict-free b128 reads)
+constexpr int TILE_WORDS = TS * ROWW;
+constexpr int TLD = 132;          // score tile row stride, floats
+constexpr int KMAX = NR_TOPK_MAX;
+static_assert(kChunk % 256 == 0 && kChunk <= 65536 && TS * TLD <= 4 * TILE_WORDS, "score tile must fit the operand ring");
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+struct alignas(8) Pair {
+  float s;
+  int32_t r;
+};
+
+// (score descending, row ascending)
+__device__ __forceinline__ bool better(float s, int32_t r, float s2, int32_t r2) {
+  return s > s2 || (s == s2 && r < r2);
+}
+
+__global__ __launch_bounds__(256) void topk_bf16_users_kernel(int64_t n8, const float* __restrict__ x,
+                                                              __bf16* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  const float4 a = reinterpret_cast<const float4*>(x)[2 * i], b = reinterpret_cast<const float4*>(x)[2 * i + 1];
+  bf16x8 o;
+  o[0] = (__bf16)a.x; o[1] = (__bf16)a.y; o[2] = (__bf16)a.z; o[3] = (__bf16)a.w;
+  o[4] = (__bf16)b.x; o[5] = (__bf16)b.y; o[6] = (__bf16)b.z; o[7] = (__bf16)b.w;
+  reinterpret_cast<bf16x8*>(y)[i] = o;
+}
+
+template <typename TI> struct Acc { typedef f32x16 type[2][2]; };  // [news 32-block][user 32-block]
+template <> struct Acc<__bf16> { typedef f32x4 type[4][4]; };      // [news 16-block][user 16-block]
+
+template <typename TI>
+__global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, const TI* __restrict__ users,
+                                                          const TI* __restrict__ tab, int64_t ldt,
+                                                          const float* __restrict__ cinv,
+                                                          const int32_t* __restrict__ excl_idx,
+                                                          const int64_t* __restrict__ excl_off, int K,
+                                                          int64_t span_rows, Pair* __restrict__ part) {
+  constexpr int BK = 128 / (int)sizeof(TI);
+  constexpr int NKT = (int)D / BK;  // K tiles per product (even: a tile starts on ring stage 0)
+  __shared__ __attribute__((aligned(16))) uint32_t smem[4 * TILE_WORDS];  // ring [2][news | users]; score tile
+  __shared__ float ls[KMAX * TS];  // the users' sorted lists, [rank][user]
+  __shared__ int32_t li[KMAX * TS];
+  __shared__ __attribute__((aligned(16))) float cinv_s[TS];
+  __shared__ int cnt_s[TS];
+  __shared__ uint16_t ex_s[XCAP * TS];  // the users' excluded rows inside the current chunk, [slot][user], minus its first row
+  __shared__ uint32_t ov_mask[TS / 32];  // users with more than XCAP of them: knocked out of every score tile instead
+  float* T = reinterpret_cast<float*>(smem);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;  // news half, user half
+  const int64_t m0 = (int64_t)blockIdx.x * TS;
+  // this workgroup's news rows: span_rows = a whole number of chunks, one running list over them
+  const int64_t c0 = (int64_t)blockIdx.y * span_rows;
+  const int64_t c1 = min(N, c0 + span_rows);
+  const int ntiles = (int)((c1 - c0 + TS - 1) / TS);
+  const float NINF = -__builtin_inff();
+
+  // global -> register staging map: 4 chunks of 16 B per operand per thread; rows past U / N
+  // are clamped for the loads (their scores are never selected)
+  int soff[4];
+  const u32x4* gu[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int id = tid + 256 * p;
+    soff[p] = (id >> 3) * ROWW + (id & 7) * 4;
+    gu[p] = reinterpret_cast<const u32x4*>(users + min(m0 + (id >> 3), U - 1) * D) + (id & 7);
+  }
+  u32x4 rn[4], ru[4];
+  auto gload = [&](int64_t n0, int kt) __attribute__((always_inline)) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int id = tid + 256 * p;
+      rn[p] = (reinterpret_cast<const u32x4*>(tab + min(n0 + (id >> 3), N - 1) * ldt) + (id & 7))[kt * 8];
+      ru[p] = gu[p][kt * 8];
+    }
+  };
+  auto lstore = [&](int buf) __attribute__((always_inline)) {
+    uint32_t* Ns = smem + buf * 2 * TILE_WORDS;
+    uint32_t* Us = Ns + TILE_WORDS;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      *reinterpret_cast<u32x4*>(Ns + soff[p]) = rn[p];
+      *reinterpret_cast<u32x4*>(Us + soff[p]) = ru[p];
+    }
+  };
+
+  typename Acc<TI>::type acc;
+  auto compute = [&](int buf) __attribute__((always_inline)) {
+    const uint32_t* Ns = smem + buf * 2 * TILE_WORDS;
+    const uint32_t* Us = Ns + TILE_WORDS;
+    if constexpr (sizeof(TI) == 4) {
+      // lane (r, h) covers k = 16h + 4q + t of the 32-deep slice (news and users alike)
+      const int fr = lane & 31, fh = lane >> 5;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        f32x4 nf[2], uf[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          nf[i] = *reinterpret_cast<const f32x4*>(Ns + (wm * 64 + 32 * i + fr) * ROWW + 16 * fh + 4 * q);
+          uf[i] = *reinterpret_cast<const f32x4*>(Us + (wn * 64 + 32 * i + fr) * ROWW + 16 * fh + 4 * q);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(nf[i][t], uf[j][t], acc[i][j], 0, 0, 0);
+      }
+    } else {
+      // lane (r, g) holds k = 32 ks + 8 g + j, j < 8, of row r (16x16x32 operand map)
+      const int fr = lane & 15, fg = lane >> 4;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        bf16x8 nf[4], uf[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          nf[i] = *reinterpret_cast<const bf16x8*>(Ns + (wm * 64 + 16 * i + fr) * ROWW + 16 * ks + 4 * fg);
+          uf[i] = *reinterpret_cast<const bf16x8*>(Us + (wn * 64 + 16 * i + fr) * ROWW + 16 * ks + 4 * fg);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nf[i], uf[j], acc[i][j], 0, 0, 0);
+      }
+    }
+  };
+  // one group of 4 consecutive news of one user: scaled, -inf past the table, into the score tile
+  auto put4 = [&](int ul, int nl, float a0, float a1, float a2, float a3, int nvalid) __attribute__((always_inline)) {
+    const float4 ci = *reinterpret_cast<const float4*>(cinv_s + nl);
+    float4 v;
+    v.x = nl + 0 < nvalid ? a0 * ci.x : NINF;
+    v.y = nl + 1 < nvalid ? a1 * ci.y : NINF;
+    v.z = nl + 2 < nvalid ? a2 * ci.z : NINF;
+    v.w = nl + 3 < nvalid ? a3 * ci.w : NINF;
+    *reinterpret_cast<float4*>(T + ul * TLD + nl) = v;
+  };
+
+  // selection state: threads 2u and 2u + 1 serve user u of the block; 2u owns its list
+  const int su = tid >> 1, sh = tid & 1;
+  const bool live = m0 + su < U;
+  int64_t e0 = 0, e1 = 0;
+  if (excl_off && live) {
+    e0 = excl_off[m0 + su];
+    e1 = excl_off[m0 + su + 1];
+  }
+  int cnt = 0;            // rows kept so far (a heap in LDS, the worst at slot 0)
+  float thr = NINF;       // the worst's score once K are kept; -inf until then (every finite score passes)
+  int xn = 0;             // the owner's excluded rows inside the current chunk (all of them; XCAP are staged)
+  int64_t cb = c0;        // the current chunk's first row
+  auto stage_excluded = [&]() __attribute__((always_inline)) {  // (between the two barriers of a chunk start)
+    xn = 0;
+#pragma unroll 4
+    for (int64_t e = e0; e < e1; ++e) {
+      const int64_t d = (int64_t)excl_idx[e] - cb;
+      if (d >= 0 && d < kChunk) {
+        if (xn < XCAP) ex_s[xn * TS + su] = (uint16_t)d;
+        ++xn;
+      }
+    }
+    if (xn > XCAP) atomicOr(&ov_mask[su >> 5], 1u << (su & 31));
+  };
+  auto excluded = [&](int32_t row) __attribute__((always_inline)) -> bool {
+    if (xn > XCAP) return false;  // such a user's excluded rows are -inf in the score tile already
+    const int d = (int)(row - cb);
+    bool hit = false;
+    for (int i = 0; i < xn; ++i) hit |= ex_s[i * TS + su] == d;
+    return hit;
+  };
+
+  gload(c0, 0);
+  for (int tile = 0; tile < ntiles; ++tile) {
+    const int64_t n0 = c0 + (int64_t)tile * TS;
+    if (tile == 0 || n0 == cb + kChunk) {  // a chunk starts: its excluded rows (read after this tile's first barrier)
+      cb = n0;
+      if (tid < TS / 32) ov_mask[tid] = 0;
+      __syncthreads();
+      if (sh == 0) stage_excluded();
+    }
+    const int nvalid = (int)min((int64_t)TS, N - n0);
+    if (tid < TS) cinv_s[tid] = tid < nvalid ? cinv[n0 + tid] : 0.f;
+    lstore(0);
+    __syncthreads();
+    if constexpr (sizeof(TI) == 4) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+    }
+    for (int kt = 0; kt < NKT; ++kt) {
+      const int cur = kt & 1;
+      if (kt + 1 < NKT) gload(n0, kt + 1);
+      else if (tile + 1 < ntiles) gload(n0 + TS, 0);  // lands over the epilogue
+      compute(cur);
+      if (kt + 1 < NKT) lstore(cur ^ 1);
+      __syncthreads();
+    }
+    // ---- score tile (aliases the ring: every wave is past its last fragment read)
+    if constexpr (sizeof(TI) == 4) {
+      // C/D map: col (user) = lane & 31, row (news) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            put4(wn * 64 + 32 * j + (lane & 31), wm * 64 + 32 * i + 8 * g + 4 * (lane >> 5), acc[i][j][4 * g],
+                 acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], nvalid);
+    } else {
+      // C/D map: col (user) = lane & 15, row (news) = 4 (lane >> 4) + reg
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          put4(wn * 64 + 16 * j + (lane & 15), wm * 64 + 16 * i + 4 * (lane >> 4), acc[i][j][0], acc[i][j][1],
+               acc[i][j][2], acc[i][j][3], nvalid);
+    }
+    __syncthreads();
+    // ---- users with too many excluded rows for the staged list: every thread walks their lists
+    {
+      bool any = false;
+#pragma unroll
+      for (int w = 0; w < TS / 32; ++w) {
+        uint32_t bits = ov_mask[w];  // block-uniform
+        while (bits) {
+          const int u = 32 * w + __builtin_ctz(bits);
+          bits &= bits - 1;
+          any = true;
+          const int64_t b = excl_off[m0 + u + 1];
+          for (int64_t e = excl_off[m0 + u] + tid; e < b; e += 256) {
+            const int64_t d = (int64_t)excl_idx[e] - n0;
+            if (d >= 0 && d < TS) T[u * TLD + (int)d] = NINF;
+          }
+        }
+      }
+      if (any) __syncthreads();
+    }
+    // ---- scan against the running K-th best; what passes and is not excluded is kept (ascending row)
+    uint32_t mlo = 0, mhi = 0;
+    {
+      const float* row = T + su * TLD + 64 * sh;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float4 v = *reinterpret_cast<const float4*>(row + 4 * i);
+        const uint32_t b = (v.x > thr ? 1u : 0u) | (v.y > thr ? 2u : 0u) | (v.z > thr ? 4u : 0u) | (v.w > thr ? 8u : 0u);
+        if (i < 8) mlo |= b << (4 * i);
+        else mhi |= b << (4 * (i - 8));
+      }
+    }
+    const uint32_t plo = __shfl_down(mlo, 1, 64), phi = __shfl_down(mhi, 1, 64);
+    if (sh == 0 && live) {
+      // 32 columns of the row at a time, in ascending row order
+      auto drain = [&](uint32_t bits, int col0) __attribute__((always_inline)) {
+        while (bits) {
+          const int col = col0 + __builtin_ctz(bits);
+          bits &= bits - 1;
+          const float s = T[su * TLD + col];
+          const int32_t row = (int32_t)(n0 + col);
+          // a later row never beats an equal score already kept, so the compare is strict
+          if (!(s > thr) || excluded(row)) continue;  // (the threshold may have risen since the scan)
+          // the list is a binary heap with the WORST kept entry (lowest score, then highest
+          // row) at slot 0: log2 K steps per kept row
+          int i;
+          if (cnt < K) {  // append, sift up while worse than the parent
+            i = cnt++;
+            while (i > 0) {
+              const int p = (i - 1) >> 1;
+              const float ps = ls[p * TS + su];
+              const int32_t pr = li[p * TS + su];
+              if (!better(ps, pr, s, row)) break;
+              ls[i * TS + su] = ps;
+              li[i * TS + su] = pr;
+              i = p;
+            }
+          } else {  // a full list drops its worst: sift down from the root past every worse child
+            i = 0;
+            for (int c = 1; c < K; c = 2 * i + 1) {
+              float cs = ls[c * TS + su];
+              int32_t cr = li[c * TS + su];
+              if (c + 1 < K) {
+                const float ds = ls[(c + 1) * TS + su];
+                const int32_t dr = li[(c + 1) * TS + su];
+                if (better(cs, cr, ds, dr)) {
+                  cs = ds;
+                  cr = dr;
+                  ++c;
+                }
+              }
+              if (!better(s, row, cs, cr)) break;
+              ls[i * TS + su] = cs;
+              li[i * TS + su] = cr;
+              i = c;
+            }
+          }
+          ls[i * TS + su] = s;
+          li[i * TS + su] = row;
+          if (cnt == K) thr = ls[su];
+        }
+      };
+      drain(mlo, 0);
+      drain(mhi, 32);
+      drain(plo, 64);
+      drain(phi, 96);
+    }
+    thr = __shfl(thr, lane & ~1, 64);
+    __syncthreads();  // the next tile's operands overwrite the score tile
+  }
+  // ---- K (score, row) pairs per (user, chunk), best first (a rank sort of the kept
+  // list); a short list ends in (-inf, -1)
+  if (sh == 0) cnt_s[su] = cnt;
+  __syncthreads();
+  for (int i = tid; i < TS * K; i += 256) {
+    const int u = i / K, j = i - u * K;
+    if (m0 + u >= U) break;
+    const int n = cnt_s[u];
+    Pair pr{NINF, -1};
+    int at = j;
+    if (j < n) {
+      pr.s = ls[j * TS + u];
+      pr.r = li[j * TS + u];
+      at = 0;
+      for (int t = 0; t < n; ++t) at += better(ls[t * TS + u], li[t * TS + u], pr.s, pr.r) ? 1 : 0;
+    }
+    part[((m0 + u) * gridDim.y + blockIdx.y) * K + at] = pr;
+  }
+}
+
+// One wave per user: K rounds over the heads of its chunk lists (each sorted).  Lane l
+// keeps the best head among chunks l, l + 64, ... and re-reads them only after it won.
+__global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int K, int nchunks, const Pair* __restrict__ part,
+                                                         int32_t* __restrict__ top_idx, int32_t* __restrict__ cnt_out,
+                                                         int32_t* __restrict__ uidx, int64_t* __restrict__ coff) {
+  __shared__ uint8_t head[4][kMaxChunks];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t u = (int64_t)blockIdx.x * 4 + wave;
+  if (u >= U) return;  // wave-uniform; no block-wide barrier below
+  const Pair* p = part + u * nchunks * K;
+  for (int c = lane; c < nchunks; c += 64) head[wave][c] = 0;
+  const float NINF = -__builtin_inff();
+  float bs;
+  int32_t br;
+  int bc;
+  auto refresh = [&]() {
+    bs = NINF;
+    br = INT32_MAX;
+    bc = -1;
+    for (int c = lane; c < nchunks; c += 64) {
+      const int h = head[wave][c];
+      if (h >= K) continue;
+      const Pair e = p[(int64_t)c * K + h];
+      if (e.r >= 0 && better(e.s, e.r, bs, br)) {
+        bs = e.s;
+        br = e.r;
+        bc = c;
+      }
+    }
+  };
+  refresh();
+  int32_t mine = 0;  // lane j: the j-th survivor
+  int cnt = 0;
+  for (int j = 0; j < K; ++j) {
+    float ws = bs;
+    int32_t wr = br;
+    int wl = lane;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const float os = __shfl_xor(ws, m, 64);
+      const int32_t orow = __shfl_xor(wr, m, 64);
+      const int ol = __shfl_xor(wl, m, 64);
+      // rows are distinct across chunks, so (score, row) alone orders every live head;
+      // two exhausted lanes (row INT32_MAX) tie and either may stand
+      if (better(os, orow, ws, wr)) {
+        ws = os;
+        wr = orow;
+        wl = ol;
+      }
+    }
+    wl = __shfl(wl, 0, 64);
+    wr = __shfl(wr, 0, 64);
+    if (wr == INT32_MAX) break;  // every list is exhausted
+    if (lane == j) mine = wr;
+    ++cnt;
+    if (lane == wl) {
+      head[wave][bc] += 1;
+      refresh();
+    }
+  }
+  if (lane < K) top_idx[u * K + lane] = lane < cnt ? mine : 0;  // never row -1 to the scoring gather
+  if (lane == 0) {
+    cnt_out[u] = cnt;
+    uidx[u] = (int32_t)u;
+    coff[u] = u * K;
+    if (u == U - 1) coff[U] = U * K;
+  }
+}
+
+// One wave per user: order its <= 64 (evaluation score, row) pairs, pad the tail.
+__global__ __launch_bounds__(256) void topk_sort_kernel(int64_t U, int K, const int32_t* __restrict__ cnt_in,
+                                                        int32_t* __restrict__ top_idx, float* __restrict__ top_scores) {
+  const int lane = threadIdx.x & 63;
+  const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= U) return;
+  const bool valid = lane < cnt_in[u];
+  const float s = valid ? top_scores[u * K + lane] : -__builtin_inff();
+  const int32_t r = valid ? top_idx[u * K + lane] : INT32_MAX;
+  int rank = 0;
+  for (int l = 0; l < 64; ++l) {
+    const float os = __shfl(s, l, 64);
+    const int32_t orow = __shfl(r, l, 64);
+    rank += (better(os, orow, s, r) || (os == s && orow == r && l < lane)) ? 1 : 0;
+  }
+  // (the shuffles above consumed every lane's loads: the row is rewritten in place)
+  if (rank < K) {
+    top_idx[u * K + rank] = valid ? r : -1;
+    top_scores[u * K + rank] = s;
+  }
+}
+
+struct Layout {
+  int64_t nchunks, ub, cnt, uidx, coff, part, total;
+};
+static Layout layout(int dtype, int64_t U, int64_t N, int64_t K) {
+  Layout L{};
+  L.nchunks = (N + kChunk - 1) / kChunk;
+  int64_t o = 0;
+  auto take = [&](int64_t bytes) {
+    const int64_t at = o;
+    o += align256(bytes);
+    return at;
+  };
+  L.ub = take(dtype == NR_BF16 ? U * D * 2 : 0);
+  L.cnt = take(U * 4);
+  L.uidx = take(U * 4);
+  L.coff = take((U + 1) * 8);
+  L.part = take(U * L.nchunks * K * (int64_t)sizeof(Pair));
+  L.total = o;
+  return L;
+}
+
+static bool shape_ok(int dtype, int64_t U, int64_t N, int64_t K) {
+  return ok_dtype(dtype) && U >= 1 && U < (1ll << 31) && N >= 1 && N <= kChunk * kMaxChunks && K >= 1 && K <= KMAX;
+}
+
+}  // namespace tk
+}  // namespace nr
+
+extern "C" int64_t nr_topk_chunk_rows(void) { return nr::tk::kChunk; }
+
+extern "C" int64_t nr_topk_workspace_bytes(int dtype, int64_t U, int64_t N, int64_t K) {
+  if (!nr::tk::shape_ok(dtype, U, N, K)) return -1;
+  return nr::tk::layout(dtype, U, N, K).total;
+}
+
+extern "C" int nr_topk_users(int dtype, int64_t dim, int64_t U, const float* users, int64_t N, const void* cand_table,
+                             int64_t cand_ld, const float* cand_inv_norm, const int32_t* excl_idx,
+                             const int64_t* excl_off, int64_t K, int32_t* top_idx, float* top_scores, void* ws,
+                             int64_t ws_bytes, void* stream) {
+  using namespace nr::tk;
+  constexpr const char* fn = "nr_topk_users";
+  nr::clear_error();
+  if (dim != 1024) {
+    nr::set_error("%s: dim %lld unsupported (1024 only)", fn, (long long)dim);
+    return NR_ERR_UNSUPPORTED;
+  }
+  NR_CHECK_ARG(nr::ok_dtype(dtype), "%s: bad dtype %d", fn, dtype);
+  NR_CHECK_ARG(K >= 1 && K <= KMAX, "%s: K = %lld outside [1, %d]", fn, (long long)K, KMAX);
+  NR_CHECK_ARG(U >= 1 && U < (1ll << 31), "%s: U = %lld outside [1, 2^31)", fn, (long long)U);
+  NR_CHECK_ARG(N >= 1, "%s: N = %lld < 1", fn, (long long)N);
+  if (N > kChunk * kMaxChunks) {
+    nr::set_error("%s: N = %lld unsupported (at most %lld rows)", fn, (long long)N, (long long)(kChunk * kMaxChunks));
+    return NR_ERR_UNSUPPORTED;
+  }
+  NR_CHECK_ARG(cand_ld >= dim, "%s: cand_ld = %lld < dim", fn, (long long)cand_ld);
+  NR_CHECK_ARG(cand_ld % (dtype == NR_F32 ? 4 : 8) == 0 && ((uintptr_t)cand_table & 15) == 0 &&
+                   ((uintptr_t)users & 15) == 0,
+               "%s: users and cand_table must be 16-byte aligned with 16-byte row strides", fn);
+  NR_CHECK_ARG((excl_idx == nullptr) == (excl_off == nullptr), "%s: excl_idx and excl_off go together", fn);
+  NR_CHECK_ARG(users && cand_table && cand_inv_norm && top_idx && top_scores && ws, "%s: null pointer", fn);
+  const Layout L = layout(dtype, U, N, K);
+  NR_CHECK_ARG(ws_bytes >= L.total, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes,
+               (long long)L.total);
+  NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+  NR_CHECK_DEVICE(fn, users, cand_table, cand_inv_norm, excl_idx, excl_off, top_idx, top_scores, ws);
+
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)ws;
+  int32_t* cnt = (int32_t*)(w + L.cnt);
+  int32_t* uidx = (int32_t*)(w + L.uidx);
+  int64_t* coff = (int64_t*)(w + L.coff);
+  Pair* part = (Pair*)(w + L.part);
+  // A workgroup keeps one running list over `span` consecutive chunks: the longer its walk, the
+  // fewer rows ever pass its threshold (K (1 + ln(rows / K)) of them), so chunks only run side
+  // by side while the user blocks alone do not fill the device.  The survivors do not depend on it.
+  const int64_t ublocks = (U + TS - 1) / TS;
+  int64_t span = L.nchunks;
+  while (span > 1 && ublocks * ((L.nchunks + span - 1) / span) < kFillWorkgroups) --span;
+  const int64_t nparts = (L.nchunks + span - 1) / span;
+  const dim3 g1((unsigned)ublocks, (unsigned)nparts);
+  if (dtype == NR_BF16) {
+    __bf16* ub = (__bf16*)(w + L.ub);
+    const int64_t n8 = U * D / 8;
+    hipLaunchKernelGGL(topk_bf16_users_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, n8, users, ub);
+    NR_CHECK_LAUNCH(fn);
+    hipLaunchKernelGGL(topk_stage1_kernel<__bf16>, g1, dim3(256), 0, st, U, N, (const __bf16*)ub,
+                       (const __bf16*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, (int)K, span * kChunk, part);
+  } else {
+    hipLaunchKernelGGL(topk_stage1_kernel<float>, g1, dim3(256), 0, st, U, N, users, (const float*)cand_table, cand_ld,
+                       cand_inv_norm, excl_idx, excl_off, (int)K, span * kChunk, part);
+  }
+  NR_CHECK_LAUNCH(fn);
+  const dim3 gw((unsigned)((U + 3) / 4));
+  hipLaunchKernelGGL(topk_merge_kernel, gw, dim3(256), 0, st, U, (int)K, (int)nparts, (const Pair*)part, top_idx, cnt,
+                     uidx, coff);
+  NR_CHECK_LAUNCH(fn);
+  const int rc = nr::score_users_dispatch(dtype, users, uidx, cand_table, cand_ld, cand_inv_norm, top_idx, coff, U,
+                                          top_scores, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(topk_sort_kernel, gw, dim3(256), 0, st, U, (int)K, (const int32_t*)cnt, top_idx, top_scores);
+  NR_CHECK_LAUNCH(fn);
+  return NR_OK;
+}

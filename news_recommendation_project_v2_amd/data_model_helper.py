@@ -138,6 +138,29 @@ def get_final_second_attention_score(history_rev_index: np.ndarray, history_len_
     return {"scores": scores, "grouped_scores": grouped}
 
 
+def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: np.ndarray,
+                              news_embeddings: torch.Tensor, attention_model: torch.nn.Module, k: int,
+                              exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
+                              dtype=None) -> dict:
+    """The k news of the WHOLE table that the model recommends per impression:
+    ``{"news_index": int32 [I, k], "scores": float32 [I, k]}`` on the host, score
+    descending, ties by ascending news row, ``(-1, -inf)`` where fewer than k news are
+    eligible.  The scores are get_cos_sim_scores' for that (impression, news) pair.
+    ``exclude_history`` leaves an impression's own history out of its list (the history
+    rows are taken as rows of ``news_embeddings``).
+
+    The reference has no counterpart: it only scores the candidates an impression
+    lists.  This is PoolScoreEngine.recommend (users x table as one MFMA GEMM with
+    the K best kept per user as the tiles are produced, include/newsrec_topk.h)."""
+    eng = _engine(attention_model, news_embeddings, query_news_embeddings if isinstance(query_news_embeddings,
+                                                                                        torch.Tensor) else None,
+                  dtype=dtype)
+    n = len(history_len_list)
+    eng.load_impressions(history_rev_index, history_len_list, np.zeros(0, np.int32), np.zeros(n, np.int32))
+    idx, scores = eng.recommend(k, exclude_history=exclude_history)
+    return {"news_index": _host(idx), "scores": _host(scores)}
+
+
 def get_embeddings(model_path: str, news_list: Iterable[str], news_text_dict: dict[str, str]):
     """Title encoder entry (data_model_helper.py:45-84): see encoder.py."""
     from .encoder import get_embeddings as _ge

@@ -203,5 +203,53 @@ class PoolScoreEngine:
         self.inv_norms()
         return self.pool_score(want_users=want_users, scores=scores)
 
+    def recommend(self, k: int, exclude_history: bool = True, user_block: Optional[int] = None):
+        """The k best news of the WHOLE table per impression (ops.topk_users over the
+        pooled users): (idx int32 [I, k], scores f32 [I, k]), score descending, ties by
+        ascending row, (-1, -inf) where fewer than k rows are eligible; the scores are
+        pool_score's for that (impression, news) pair bit for bit.  ``exclude_history``
+        leaves an impression's own history out of its list.  Distinct histories are
+        pooled and searched once (the deduplicated CSR when load_impressions built it).
+        ``user_block`` bounds the workspace by running the users in blocks of that many
+        rows; the results do not depend on it."""
+        self.hist_table = self.transform(out=self.hist_table)
+        self.inv_norms()
+        if self.user_idx is not None:
+            hidx, hoff = self.uhist_idx, self.uhist_off
+        else:
+            hidx, hoff = self.hist_idx, self.hist_off
+        n_u = hoff.numel() - 1
+        idx = torch.empty((n_u, k), dtype=torch.int32, device=self.device)
+        scores = torch.empty((n_u, k), dtype=torch.float32, device=self.device)
+        if n_u == 0:
+            return idx, scores
+        if self._users is None or self._users.shape[0] != n_u:
+            self._users = torch.empty((n_u, 1024), dtype=torch.float32, device=self.device)
+        users = ops.pool_users(self.pooler, self.hist_table, hidx, hoff, out=self._users)
+        blk = n_u if not user_block else max(1, min(int(user_block), n_u))
+        need = ops.topk_workspace_bytes(self.dtype, blk, self.cand_table.shape[0], k)
+        self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, self.device)
+        for u0 in range(0, n_u, blk):
+            u1 = min(u0 + blk, n_u)
+            eoff = None
+            if exclude_history:
+                # the block's own CSR: offsets rebased on the device, indices shared
+                eoff = hoff[u0:u1 + 1] - hoff[u0:u0 + 1] if u0 else hoff[:u1 + 1]
+                eidx = hidx[int(self._hoff_host(hoff)[u0]):] if u0 else hidx
+            ops.topk_users(users[u0:u1], self.cand_table, self.cand_inv, k,
+                           excl_idx=eidx if exclude_history else None, excl_off=eoff,
+                           out=(idx[u0:u1], scores[u0:u1]), workspace=self._topk_ws)
+        if self.user_idx is not None:
+            sel = self.user_idx.long()
+            return idx[sel], scores[sel]
+        return idx, scores
+
+    def _hoff_host(self, hoff: torch.Tensor) -> np.ndarray:
+        """Host copy of a history offset array (one read-back per loaded impression set)."""
+        cache = getattr(self, "_hoff_cache", None)
+        if cache is None or cache[0] is not hoff:
+            self._hoff_cache = cache = (hoff, hoff.cpu().numpy())
+        return cache[1]
+
     def rank(self, scores: torch.Tensor) -> torch.Tensor:
         return ops.dense_rank(scores, self.cand_off)

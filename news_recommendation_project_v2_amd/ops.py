@@ -300,6 +300,63 @@ def score_users(users: torch.Tensor, user_idx: torch.Tensor, cand_table: torch.T
     return scores
 
 
+def topk_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) -> int:
+    """nr_topk_workspace_bytes (include/newsrec_topk.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_topk_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, k))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"topk_users: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, k = {k}; "
+            f"k in [1, {_lib.NR_TOPK_MAX}], N <= 2^22)")
+    return need
+
+
+def topk_users(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int,
+               excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+               out=None, workspace: Optional[torch.Tensor] = None):
+    """The k best rows of ``cand_table`` per user row (nr_topk_users): returns
+    (idx int32 [U, k], scores f32 [U, k]), score descending, ties by ascending row,
+    a short tail as (-1, -inf); the scores are score_users' bit for bit.  The CSR
+    (excl_idx int32, excl_off int64 [U + 1]) lists rows a user must not get; its
+    entries are range-checked here (one small sync).  ``out`` = (idx, scores) to
+    write into."""
+    dev = _dev(users, cand_table, cand_inv_norm, excl_idx, excl_off, workspace, *(out or ()))
+    if users.dtype != torch.float32 or users.dim() != 2 or not users.is_contiguous():
+        raise _lib.NewsRecHIPError("topk_users: users must be contiguous f32 [U, D]")
+    n_users, dim = users.shape
+    n_news = cand_table.shape[0]
+    ld = _rowmajor(cand_table, "cand_table")
+    if cand_table.shape[1] != dim:
+        raise _lib.NewsRecHIPError("topk_users: users and cand_table must share their width")
+    if cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < n_news or not cand_inv_norm.is_contiguous():
+        raise _lib.NewsRecHIPError("cand_inv_norm must be contiguous f32 with one entry per candidate-table row")
+    if (excl_idx is None) != (excl_off is None):
+        raise _lib.NewsRecHIPError("topk_users: excl_idx and excl_off go together")
+    if excl_idx is not None:
+        _check_csr(excl_idx, excl_off, "excl")
+        if excl_off.numel() != n_users + 1:
+            raise _lib.NewsRecHIPError("topk_users: excl_off must have U + 1 entries")
+        if excl_idx.numel():
+            lo, hi = (int(v) for v in torch.aminmax(excl_idx))
+            if lo < 0 or hi >= n_news:
+                raise IndexError(f"topk_users: excluded row {lo if lo < 0 else hi} is outside the {n_news} table rows")
+        else:  # no storage behind an empty tensor; the kernel never reads it
+            excl_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+    k = int(k)
+    if out is None:
+        idx = torch.empty((n_users, k), dtype=torch.int32, device=dev)
+        scores = torch.empty((n_users, k), dtype=torch.float32, device=dev)
+    else:
+        idx, scores = out
+        if (idx.dtype != torch.int32 or scores.dtype != torch.float32 or idx.shape != (n_users, k)
+                or scores.shape != (n_users, k) or not idx.is_contiguous() or not scores.is_contiguous()):
+            raise _lib.NewsRecHIPError(f"topk_users: out must be contiguous (int32, f32) of shape {(n_users, k)}")
+    dt = _dtype(cand_table, "cand_table")
+    ws = grow_workspace(workspace, topk_workspace_bytes(cand_table.dtype, n_users, n_news, k), dev)
+    _lib.call("nr_topk_users", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm),
+              _ptr(excl_idx), _ptr(excl_off), k, _ptr(idx), _ptr(scores), _ptr(ws), ws.numel(), _stream(dev))
+    return idx, scores
+
+
 def dense_rank(scores: torch.Tensor, cand_off: torch.Tensor, check: bool = True) -> torch.Tensor:
     """Per-impression dense descending ranks (int32), scipy rankdata(-x, 'dense')."""
     dev = _dev(scores, cand_off)
