@@ -18,10 +18,12 @@ CSRC = Path(__file__).resolve().with_name("csrc")
 INCLUDE = Path(__file__).resolve().parent.parent / "include"
 # translation units of libnewsrec_hip.so, in link order (also the hash order)
 HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip", "encoder.hip", "train.hip",
-               "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip", "contrastive.hip", "topk.hip")
+               "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip", "contrastive.hip", "topk.hip",
+               "fullrank.hip")
 # the headers they include (every object is rebuilt when one changes), hashed after the sources
-HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", INCLUDE / "newsrec.h",
-               INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h")
+HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CSRC / "nr_score_tile.h",
+               INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
+               INCLUDE / "newsrec_fullrank.h")
 
 
 def hip_source_files() -> list:
@@ -153,6 +155,12 @@ TOPK_SIGNATURES = {
     "nr_topk_users": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _l, _p, _p, _p, _l, _p]),
 }
 
+# full-table ranks of target news (include/newsrec_fullrank.h), bound by load() like SIGNATURES
+FULLRANK_SIGNATURES = {
+    "nr_rank_targets_workspace_bytes": (_l, [_i, _l, _l, _l]),
+    "nr_rank_targets": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _l, _p]),
+}
+
 
 class ContrastiveSpec(ctypes.Structure):
     """struct nr_contrastive_spec (include/newsrec_contrastive.h)."""
@@ -209,7 +217,8 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no CPU fallback for the MI355X hot path)")
     lib = ctypes.CDLL(os.fspath(LIB_PATH))
-    for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES,
+                              **FULLRANK_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,289 @@
+// The users x news score tile that top-K retrieval (topk.hip) and the full-table ranks
+// (fullrank.hip) share: ONE copy of the tile main loop, so that the bits of a (user, news)
+// selection score are the same in both (include/newsrec_topk.h, "Selection scores" and
+// "Position independence"; include/newsrec_fullrank.h rests its consistency contract on it).
+//
+//   ScoreTile<TI>  gemm_kernel's main loop (gemm.hip: 128 x 128 tile, K in 128-byte row slices
+//                  through a two-stage LDS ring, the next slice's global loads in flight over
+//                  the MFMAs; f32 on v_mfma_f32_32x32x2_f32, bf16 on v_mfma_f32_16x16x32_bf16)
+//                  with the NEWS rows as the A operand, so a lane's accumulator registers are 4
+//                  consecutive news of one user; then scale by cand_inv (-inf past the valid
+//                  rows) and 16-byte stores into an LDS score tile [user][news] that aliases
+//                  the operand ring.  Which table row feeds news row r of the tile is the
+//                  caller's (a run of consecutive rows, or gathered rows).
+//   Excluded       a user's excluded rows inside the current chunk, staged in LDS once per
+//                  chunk as 16-bit offsets; a user with more than XCAP of them has its rows set
+//                  to -inf in every score tile by the whole workgroup instead.
+#pragma once
+
+#include "nr_common.h"
+
+namespace nr {
+namespace tk {
+
+constexpr int64_t D = 1024;
+constexpr int64_t kChunk = 16384;  // news rows per stage-1 partial (< 2^16: exclusions are staged as 16-bit offsets)
+constexpr int kMaxChunks = 256;   // chunk heads the merge keeps per user (N <= 2^22)
+constexpr int kFillWorkgroups = 1024;  // workgroups wanted before chunks are walked in sequence
+constexpr int XCAP = 32;          // excluded rows of one chunk staged in LDS per user (more: the global list is searched)
+constexpr int TS = 128;           // tile side: users and news rows per tile
+constexpr int ROWW = 36;          // LDS words per staged 128-byte row slice (144 B: conflict-free b128 reads)
+constexpr int TILE_WORDS = TS * ROWW;
+constexpr int TLD = 132;          // score tile row stride, floats
+static_assert(kChunk % 256 == 0 && kChunk <= 65536 && TS * TLD <= 4 * TILE_WORDS, "score tile must fit the operand ring");
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// (score descending, row ascending)
+__device__ __forceinline__ bool better(float s, int32_t r, float s2, int32_t r2) {
+  return s > s2 || (s == s2 && r < r2);
+}
+
+// NR_BF16: users f32 -> bf16 rows (round to nearest even), U * D / 8 groups of 8 (topk.hip)
+int bf16_users_launch(int64_t U, const float* users, __bf16* out, hipStream_t st, const char* fn);
+
+// How many chunks one workgroup walks in sequence: chunks only run side by side while the
+// user blocks alone do not fill the device.
+static inline int64_t chunk_span(int64_t U, int64_t nchunks) {
+  const int64_t ublocks = (U + TS - 1) / TS;
+  int64_t span = nchunks;
+  while (span > 1 && ublocks * ((nchunks + span - 1) / span) < kFillWorkgroups) --span;
+  return span;
+}
+
+template <typename TI> struct Acc { typedef f32x16 type[2][2]; };  // [news 32-block][user 32-block]
+template <> struct Acc<__bf16> { typedef f32x4 type[4][4]; };      // [news 16-block][user 16-block]
+
+template <typename TI>
+struct ScoreTile {
+  static constexpr int BK = 128 / (int)sizeof(TI);
+  static constexpr int NKT = (int)D / BK;  // K tiles per product (even: a tile starts on ring stage 0)
+
+  uint32_t* smem;  // ring [2][news | users], 4 * TILE_WORDS words, 16-byte aligned; the score tile aliases it
+  float* cinv_s;   // [TS] cand_inv of the tile's news rows, 16-byte aligned (the caller fills it before scores())
+  int tid, lane, wm, wn;  // wm: news half, wn: user half
+  // global -> register staging map: 4 chunks of 16 B per operand per thread; rows past U
+  // are clamped for the loads (their scores are never selected)
+  int soff[4];
+  const u32x4* gu[4];
+  u32x4 rn[4], ru[4];
+  typename Acc<TI>::type acc;
+
+  __device__ __forceinline__ ScoreTile(uint32_t* smem_, float* cinv_s_, const TI* users, int64_t m0, int64_t U)
+      : smem(smem_), cinv_s(cinv_s_) {
+    tid = threadIdx.x;
+    lane = tid & 63;
+    const int wave = tid >> 6;
+    wm = wave >> 1;
+    wn = wave & 1;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int id = tid + 256 * p;
+      soff[p] = (id >> 3) * ROWW + (id & 7) * 4;
+      gu[p] = reinterpret_cast<const u32x4*>(users + min(m0 + (id >> 3), U - 1) * D) + (id & 7);
+    }
+  }
+
+  __device__ __forceinline__ float* tile() const { return reinterpret_cast<float*>(smem); }
+
+  // rows(r): the table row (int64, inside the table) behind news row r of the tile
+  template <typename Rows>
+  __device__ __forceinline__ void gload(const TI* __restrict__ tab, int64_t ldt, Rows rows, int kt) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int id = tid + 256 * p;
+      rn[p] = (reinterpret_cast<const u32x4*>(tab + rows(id >> 3) * ldt) + (id & 7))[kt * 8];
+      ru[p] = gu[p][kt * 8];
+    }
+  }
+  __device__ __forceinline__ void lstore(int buf) {
+    uint32_t* Ns = smem + buf * 2 * TILE_WORDS;
+    uint32_t* Us = Ns + TILE_WORDS;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      *reinterpret_cast<u32x4*>(Ns + soff[p]) = rn[p];
+      *reinterpret_cast<u32x4*>(Us + soff[p]) = ru[p];
+    }
+  }
+  __device__ __forceinline__ void compute(int buf) {
+    const uint32_t* Ns = smem + buf * 2 * TILE_WORDS;
+    const uint32_t* Us = Ns + TILE_WORDS;
+    if constexpr (sizeof(TI) == 4) {
+      // lane (r, h) covers k = 16h + 4q + t of the 32-deep slice (news and users alike)
+      const int fr = lane & 31, fh = lane >> 5;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        f32x4 nf[2], uf[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          nf[i] = *reinterpret_cast<const f32x4*>(Ns + (wm * 64 + 32 * i + fr) * ROWW + 16 * fh + 4 * q);
+          uf[i] = *reinterpret_cast<const f32x4*>(Us + (wn * 64 + 32 * i + fr) * ROWW + 16 * fh + 4 * q);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(nf[i][t], uf[j][t], acc[i][j], 0, 0, 0);
+      }
+    } else {
+      // lane (r, g) holds k = 32 ks + 8 g + j, j < 8, of row r (16x16x32 operand map)
+      const int fr = lane & 15, fg = lane >> 4;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        bf16x8 nf[4], uf[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          nf[i] = *reinterpret_cast<const bf16x8*>(Ns + (wm * 64 + 16 * i + fr) * ROWW + 16 * ks + 4 * fg);
+          uf[i] = *reinterpret_cast<const bf16x8*>(Us + (wn * 64 + 16 * i + fr) * ROWW + 16 * ks + 4 * fg);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nf[i], uf[j], acc[i][j], 0, 0, 0);
+      }
+    }
+  }
+  // one group of 4 consecutive news of one user: scaled, -inf past the valid rows, into the score tile
+  __device__ __forceinline__ void put4(int ul, int nl, float a0, float a1, float a2, float a3, int nvalid) {
+    const float NINF = -__builtin_inff();
+    const float4 ci = *reinterpret_cast<const float4*>(cinv_s + nl);
+    float4 v;
+    v.x = nl + 0 < nvalid ? a0 * ci.x : NINF;
+    v.y = nl + 1 < nvalid ? a1 * ci.y : NINF;
+    v.z = nl + 2 < nvalid ? a2 * ci.z : NINF;
+    v.w = nl + 3 < nvalid ? a3 * ci.w : NINF;
+    *reinterpret_cast<float4*>(tile() + ul * TLD + nl) = v;
+  }
+
+  // One score tile.  On entry the tile's first K slice is in rn / ru (a gload(.., rows, 0))
+  // and cinv_s is written; on return the score tile tile()[user * TLD + news] is complete and
+  // visible to the workgroup, and, if `more`, the first slice of the tile behind `next` is
+  // in flight (it lands over the caller's epilogue).  The caller ends its epilogue with a
+  // barrier before the next call: the operands overwrite the score tile.
+  template <typename Rows, typename Next>
+  __device__ __forceinline__ void scores(const TI* __restrict__ tab, int64_t ldt, Rows rows, bool more, Next next,
+                                         int nvalid) {
+    lstore(0);
+    __syncthreads();
+    if constexpr (sizeof(TI) == 4) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+    }
+    for (int kt = 0; kt < NKT; ++kt) {
+      const int cur = kt & 1;
+      if (kt + 1 < NKT) gload(tab, ldt, rows, kt + 1);
+      else if (more) gload(tab, ldt, next, 0);  // lands over the epilogue
+      compute(cur);
+      if (kt + 1 < NKT) lstore(cur ^ 1);
+      __syncthreads();
+    }
+    // ---- score tile (aliases the ring: every wave is past its last fragment read)
+    if constexpr (sizeof(TI) == 4) {
+      // C/D map: col (user) = lane & 31, row (news) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            put4(wn * 64 + 32 * j + (lane & 31), wm * 64 + 32 * i + 8 * g + 4 * (lane >> 5), acc[i][j][4 * g],
+                 acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], nvalid);
+    } else {
+      // C/D map: col (user) = lane & 15, row (news) = 4 (lane >> 4) + reg
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          put4(wn * 64 + 16 * j + (lane & 15), wm * 64 + 16 * i + 4 * (lane >> 4), acc[i][j][0], acc[i][j][1],
+               acc[i][j][2], acc[i][j][3], nvalid);
+    }
+    __syncthreads();
+  }
+};
+
+// Threads 2u and 2u + 1 serve user u of the block; 2u (sh == 0) owns its staged list.
+struct Excluded {
+  uint16_t* ex_s;     // [XCAP * TS] the users' excluded rows inside the current chunk, [slot][user], minus its first row
+  uint32_t* ov_mask;  // [TS / 32] users with more than XCAP of them: knocked out of every score tile instead
+  const int32_t* excl_idx;
+  const int64_t* excl_off;
+  int su;
+  int64_t e0, e1;
+  int xn;      // the owner's excluded rows inside the current chunk (all of them; XCAP are staged)
+  int64_t cb;  // the current chunk's first row
+
+  __device__ __forceinline__ Excluded(uint16_t* ex_s_, uint32_t* ov_mask_, const int32_t* excl_idx_,
+                                      const int64_t* excl_off_, int64_t m0, bool live, int64_t c0)
+      : ex_s(ex_s_), ov_mask(ov_mask_), excl_idx(excl_idx_), excl_off(excl_off_), su(threadIdx.x >> 1), e0(0), e1(0),
+        xn(0), cb(c0) {
+    if (excl_off && live) {
+      e0 = excl_off[m0 + su];
+      e1 = excl_off[m0 + su + 1];
+    }
+  }
+  // A chunk starts at row n0: clear the overflow mask, barrier, the owners stage their rows
+  // (read after the tile's first barrier).  Called by every thread.
+  __device__ __forceinline__ void chunk_start(int64_t n0) {
+    cb = n0;
+    if (threadIdx.x < TS / 32) ov_mask[threadIdx.x] = 0;
+    __syncthreads();
+    if ((threadIdx.x & 1) == 0) {
+      xn = 0;
+#pragma unroll 4
+      for (int64_t e = e0; e < e1; ++e) {
+        const int64_t d = (int64_t)excl_idx[e] - cb;
+        if (d >= 0 && d < kChunk) {
+          if (xn < XCAP) ex_s[xn * TS + su] = (uint16_t)d;
+          ++xn;
+        }
+      }
+      if (xn > XCAP) atomicOr(&ov_mask[su >> 5], 1u << (su & 31));
+    }
+  }
+  // owner only: is `row` (of the current chunk) on the staged list?
+  __device__ __forceinline__ bool staged(int32_t row) const {
+    if (xn > XCAP) return false;  // such a user's excluded rows are -inf in the score tile already
+    const int d = (int)(row - cb);
+    bool hit = false;
+    for (int i = 0; i < xn; ++i) hit |= ex_s[i * TS + su] == d;
+    return hit;
+  }
+  // users with too many excluded rows for the staged list: every thread walks their lists and
+  // writes -inf into the score tile T of news rows [n0, n0 + TS).  Called by every thread.
+  __device__ __forceinline__ void knock_out_overflow(float* T, int64_t m0, int64_t n0) {
+    const float NINF = -__builtin_inff();
+    bool any = false;
+#pragma unroll
+    for (int w = 0; w < TS / 32; ++w) {
+      uint32_t bits = ov_mask[w];  // block-uniform
+      while (bits) {
+        const int u = 32 * w + __builtin_ctz(bits);
+        bits &= bits - 1;
+        any = true;
+        const int64_t b = excl_off[m0 + u + 1];
+        for (int64_t e = excl_off[m0 + u] + threadIdx.x; e < b; e += 256) {
+          const int64_t d = (int64_t)excl_idx[e] - n0;
+          if (d >= 0 && d < TS) T[u * TLD + (int)d] = NINF;
+        }
+      }
+    }
+    if (any) __syncthreads();
+  }
+};
+
+}  // namespace tk
+}  // namespace nr

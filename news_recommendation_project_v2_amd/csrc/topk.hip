@@ -3,7 +3,8 @@
 //
 //   prep     NR_BF16 only: users f32 -> bf16 rows in the workspace (round to nearest even)
 //   stage 1  grid (user blocks of 128, runs of chunks of kChunk news rows).  A workgroup walks its
-//            chunks in 128-row tiles: gemm_kernel's main loop (gemm.hip: 128 x 128 tile, K in
+//            chunks in 128-row tiles (nr_score_tile.h, shared with fullrank.hip: the tile main
+//            loop and the exclusion staging exist once): gemm_kernel's main loop (128 x 128 tile, K in
 //            128-byte row slices through a two-stage LDS ring, the next slice's global loads
 //            in flight over the MFMAs; f32 on v_mfma_f32_32x32x2_f32, bf16 on
 //            v_mfma_f32_16x16x32_bf16) with the NEWS rows as the A operand, so a lane's
@@ -24,36 +25,19 @@
 //
 // Every comparison is on the strict total order (score descending, row ascending), so no
 // result depends on the order in which lanes or workgroups ran.
-#include "nr_common.h"
+#include "nr_score_tile.h"
 
 #include "../../include/newsrec_topk.h"
 
 namespace nr {
 namespace tk {
 
-constexpr int64_t D = 1024;
-constexpr int64_t kChunk = 16384;  // news rows per stage-1 partial (< 2^16: exclusions are staged as 16-bit offsets)
-constexpr int kMaxChunks = 256;   // chunk heads the merge keeps per user (N <= 2^22)
-constexpr int kFillWorkgroups = 1024;  // stage-1 workgroups wanted before chunks are walked in sequence
-constexpr int XCAP = 32;          // excluded rows of one chunk staged in LDS per user (more: the global list is searched)
-constexpr int TS = 128;           // tile side: users and news rows per tile
-constexpr int ROWW = 36;          // LDS words per staged 128-byte row slice (144 B: conflict-free b128 reads)
-constexpr int TILE_WORDS = TS * ROWW;
-constexpr int TLD = 132;          // score tile row stride, floats
 constexpr int KMAX = NR_TOPK_MAX;
-static_assert(kChunk % 256 == 0 && kChunk <= 65536 && TS * TLD <= 4 * TILE_WORDS, "score tile must fit the operand ring");
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct alignas(8) Pair {
   float s;
   int32_t r;
 };
-
-// (score descending, row ascending)
-__device__ __forceinline__ bool better(float s, int32_t r, float s2, int32_t r2) {
-  return s > s2 || (s == s2 && r < r2);
-}
 
 __global__ __launch_bounds__(256) void topk_bf16_users_kernel(int64_t n8, const float* __restrict__ x,
                                                               __bf16* __restrict__ y) {
@@ -66,8 +50,12 @@ __global__ __launch_bounds__(256) void topk_bf16_users_kernel(int64_t n8, const 
   reinterpret_cast<bf16x8*>(y)[i] = o;
 }
 
-template <typename TI> struct Acc { typedef f32x16 type[2][2]; };  // [news 32-block][user 32-block]
-template <> struct Acc<__bf16> { typedef f32x4 type[4][4]; };      // [news 16-block][user 16-block]
+int bf16_users_launch(int64_t U, const float* users, __bf16* out, hipStream_t st, const char* fn) {
+  const int64_t n8 = U * D / 8;
+  hipLaunchKernelGGL(topk_bf16_users_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, n8, users, out);
+  NR_CHECK_LAUNCH(fn);
+  return NR_OK;
+}
 
 template <typename TI>
 __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, const TI* __restrict__ users,
@@ -76,19 +64,16 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
                                                           const int32_t* __restrict__ excl_idx,
                                                           const int64_t* __restrict__ excl_off, int K,
                                                           int64_t span_rows, Pair* __restrict__ part) {
-  constexpr int BK = 128 / (int)sizeof(TI);
-  constexpr int NKT = (int)D / BK;  // K tiles per product (even: a tile starts on ring stage 0)
   __shared__ __attribute__((aligned(16))) uint32_t smem[4 * TILE_WORDS];  // ring [2][news | users]; score tile
   __shared__ float ls[KMAX * TS];  // the users' sorted lists, [rank][user]
   __shared__ int32_t li[KMAX * TS];
   __shared__ __attribute__((aligned(16))) float cinv_s[TS];
   __shared__ int cnt_s[TS];
-  __shared__ uint16_t ex_s[XCAP * TS];  // the users' excluded rows inside the current chunk, [slot][user], minus its first row
-  __shared__ uint32_t ov_mask[TS / 32];  // users with more than XCAP of them: knocked out of every score tile instead
+  __shared__ uint16_t ex_s[XCAP * TS];
+  __shared__ uint32_t ov_mask[TS / 32];
   float* T = reinterpret_cast<float*>(smem);
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;  // news half, user half
+  const int tid = threadIdx.x, lane = tid & 63;
   const int64_t m0 = (int64_t)blockIdx.x * TS;
   // this workgroup's news rows: span_rows = a whole number of chunks, one running list over them
   const int64_t c0 = (int64_t)blockIdx.y * span_rows;
@@ -96,196 +81,27 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
   const int ntiles = (int)((c1 - c0 + TS - 1) / TS);
   const float NINF = -__builtin_inff();
 
-  // global -> register staging map: 4 chunks of 16 B per operand per thread; rows past U / N
-  // are clamped for the loads (their scores are never selected)
-  int soff[4];
-  const u32x4* gu[4];
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int id = tid + 256 * p;
-    soff[p] = (id >> 3) * ROWW + (id & 7) * 4;
-    gu[p] = reinterpret_cast<const u32x4*>(users + min(m0 + (id >> 3), U - 1) * D) + (id & 7);
-  }
-  u32x4 rn[4], ru[4];
-  auto gload = [&](int64_t n0, int kt) __attribute__((always_inline)) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int id = tid + 256 * p;
-      rn[p] = (reinterpret_cast<const u32x4*>(tab + min(n0 + (id >> 3), N - 1) * ldt) + (id & 7))[kt * 8];
-      ru[p] = gu[p][kt * 8];
-    }
-  };
-  auto lstore = [&](int buf) __attribute__((always_inline)) {
-    uint32_t* Ns = smem + buf * 2 * TILE_WORDS;
-    uint32_t* Us = Ns + TILE_WORDS;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      *reinterpret_cast<u32x4*>(Ns + soff[p]) = rn[p];
-      *reinterpret_cast<u32x4*>(Us + soff[p]) = ru[p];
-    }
-  };
-
-  typename Acc<TI>::type acc;
-  auto compute = [&](int buf) __attribute__((always_inline)) {
-    const uint32_t* Ns = smem + buf * 2 * TILE_WORDS;
-    const uint32_t* Us = Ns + TILE_WORDS;
-    if constexpr (sizeof(TI) == 4) {
-      // lane (r, h) covers k = 16h + 4q + t of the 32-deep slice (news and users alike)
-      const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        f32x4 nf[2], uf[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          nf[i] = *reinterpret_cast<const f32x4*>(Ns + (wm * 64 + 32 * i + fr) * ROWW + 16 * fh + 4 * q);
-          uf[i] = *reinterpret_cast<const f32x4*>(Us + (wn * 64 + 32 * i + fr) * ROWW + 16 * fh + 4 * q);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(nf[i][t], uf[j][t], acc[i][j], 0, 0, 0);
-      }
-    } else {
-      // lane (r, g) holds k = 32 ks + 8 g + j, j < 8, of row r (16x16x32 operand map)
-      const int fr = lane & 15, fg = lane >> 4;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 nf[4], uf[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          nf[i] = *reinterpret_cast<const bf16x8*>(Ns + (wm * 64 + 16 * i + fr) * ROWW + 16 * ks + 4 * fg);
-          uf[i] = *reinterpret_cast<const bf16x8*>(Us + (wn * 64 + 16 * i + fr) * ROWW + 16 * ks + 4 * fg);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nf[i], uf[j], acc[i][j], 0, 0, 0);
-      }
-    }
-  };
-  // one group of 4 consecutive news of one user: scaled, -inf past the table, into the score tile
-  auto put4 = [&](int ul, int nl, float a0, float a1, float a2, float a3, int nvalid) __attribute__((always_inline)) {
-    const float4 ci = *reinterpret_cast<const float4*>(cinv_s + nl);
-    float4 v;
-    v.x = nl + 0 < nvalid ? a0 * ci.x : NINF;
-    v.y = nl + 1 < nvalid ? a1 * ci.y : NINF;
-    v.z = nl + 2 < nvalid ? a2 * ci.z : NINF;
-    v.w = nl + 3 < nvalid ? a3 * ci.w : NINF;
-    *reinterpret_cast<float4*>(T + ul * TLD + nl) = v;
-  };
+  ScoreTile<TI> st(smem, cinv_s, users, m0, U);
 
   // selection state: threads 2u and 2u + 1 serve user u of the block; 2u owns its list
   const int su = tid >> 1, sh = tid & 1;
   const bool live = m0 + su < U;
-  int64_t e0 = 0, e1 = 0;
-  if (excl_off && live) {
-    e0 = excl_off[m0 + su];
-    e1 = excl_off[m0 + su + 1];
-  }
+  Excluded ex(ex_s, ov_mask, excl_idx, excl_off, m0, live, c0);
   int cnt = 0;            // rows kept so far (a heap in LDS, the worst at slot 0)
   float thr = NINF;       // the worst's score once K are kept; -inf until then (every finite score passes)
-  int xn = 0;             // the owner's excluded rows inside the current chunk (all of them; XCAP are staged)
-  int64_t cb = c0;        // the current chunk's first row
-  auto stage_excluded = [&]() __attribute__((always_inline)) {  // (between the two barriers of a chunk start)
-    xn = 0;
-#pragma unroll 4
-    for (int64_t e = e0; e < e1; ++e) {
-      const int64_t d = (int64_t)excl_idx[e] - cb;
-      if (d >= 0 && d < kChunk) {
-        if (xn < XCAP) ex_s[xn * TS + su] = (uint16_t)d;
-        ++xn;
-      }
-    }
-    if (xn > XCAP) atomicOr(&ov_mask[su >> 5], 1u << (su & 31));
-  };
-  auto excluded = [&](int32_t row) __attribute__((always_inline)) -> bool {
-    if (xn > XCAP) return false;  // such a user's excluded rows are -inf in the score tile already
-    const int d = (int)(row - cb);
-    bool hit = false;
-    for (int i = 0; i < xn; ++i) hit |= ex_s[i * TS + su] == d;
-    return hit;
-  };
 
-  gload(c0, 0);
+  // a run of consecutive table rows from n0, clamped past the table (their scores are -inf)
+  auto rows_from = [&](int64_t n0) __attribute__((always_inline)) {
+    return [=](int r) __attribute__((always_inline)) { return min(n0 + r, N - 1); };
+  };
+  st.gload(tab, ldt, rows_from(c0), 0);
   for (int tile = 0; tile < ntiles; ++tile) {
     const int64_t n0 = c0 + (int64_t)tile * TS;
-    if (tile == 0 || n0 == cb + kChunk) {  // a chunk starts: its excluded rows (read after this tile's first barrier)
-      cb = n0;
-      if (tid < TS / 32) ov_mask[tid] = 0;
-      __syncthreads();
-      if (sh == 0) stage_excluded();
-    }
+    if (tile == 0 || n0 == ex.cb + kChunk) ex.chunk_start(n0);
     const int nvalid = (int)min((int64_t)TS, N - n0);
     if (tid < TS) cinv_s[tid] = tid < nvalid ? cinv[n0 + tid] : 0.f;
-    lstore(0);
-    __syncthreads();
-    if constexpr (sizeof(TI) == 4) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
-    }
-    for (int kt = 0; kt < NKT; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < NKT) gload(n0, kt + 1);
-      else if (tile + 1 < ntiles) gload(n0 + TS, 0);  // lands over the epilogue
-      compute(cur);
-      if (kt + 1 < NKT) lstore(cur ^ 1);
-      __syncthreads();
-    }
-    // ---- score tile (aliases the ring: every wave is past its last fragment read)
-    if constexpr (sizeof(TI) == 4) {
-      // C/D map: col (user) = lane & 31, row (news) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            put4(wn * 64 + 32 * j + (lane & 31), wm * 64 + 32 * i + 8 * g + 4 * (lane >> 5), acc[i][j][4 * g],
-                 acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], nvalid);
-    } else {
-      // C/D map: col (user) = lane & 15, row (news) = 4 (lane >> 4) + reg
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          put4(wn * 64 + 16 * j + (lane & 15), wm * 64 + 16 * i + 4 * (lane >> 4), acc[i][j][0], acc[i][j][1],
-               acc[i][j][2], acc[i][j][3], nvalid);
-    }
-    __syncthreads();
-    // ---- users with too many excluded rows for the staged list: every thread walks their lists
-    {
-      bool any = false;
-#pragma unroll
-      for (int w = 0; w < TS / 32; ++w) {
-        uint32_t bits = ov_mask[w];  // block-uniform
-        while (bits) {
-          const int u = 32 * w + __builtin_ctz(bits);
-          bits &= bits - 1;
-          any = true;
-          const int64_t b = excl_off[m0 + u + 1];
-          for (int64_t e = excl_off[m0 + u] + tid; e < b; e += 256) {
-            const int64_t d = (int64_t)excl_idx[e] - n0;
-            if (d >= 0 && d < TS) T[u * TLD + (int)d] = NINF;
-          }
-        }
-      }
-      if (any) __syncthreads();
-    }
+    st.scores(tab, ldt, rows_from(n0), tile + 1 < ntiles, rows_from(n0 + TS), nvalid);
+    ex.knock_out_overflow(T, m0, n0);
     // ---- scan against the running K-th best; what passes and is not excluded is kept (ascending row)
     uint32_t mlo = 0, mhi = 0;
     {
@@ -308,7 +124,7 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
           const float s = T[su * TLD + col];
           const int32_t row = (int32_t)(n0 + col);
           // a later row never beats an equal score already kept, so the compare is strict
-          if (!(s > thr) || excluded(row)) continue;  // (the threshold may have risen since the scan)
+          if (!(s > thr) || ex.staged(row)) continue;  // (the threshold may have risen since the scan)
           // the list is a binary heap with the WORST kept entry (lowest score, then highest
           // row) at slot 0: log2 K steps per kept row
           int i;
@@ -542,16 +358,13 @@ extern "C" int nr_topk_users(int dtype, int64_t dim, int64_t U, const float* use
   // A workgroup keeps one running list over `span` consecutive chunks: the longer its walk, the
   // fewer rows ever pass its threshold (K (1 + ln(rows / K)) of them), so chunks only run side
   // by side while the user blocks alone do not fill the device.  The survivors do not depend on it.
-  const int64_t ublocks = (U + TS - 1) / TS;
-  int64_t span = L.nchunks;
-  while (span > 1 && ublocks * ((L.nchunks + span - 1) / span) < kFillWorkgroups) --span;
+  const int64_t span = chunk_span(U, L.nchunks);
   const int64_t nparts = (L.nchunks + span - 1) / span;
-  const dim3 g1((unsigned)ublocks, (unsigned)nparts);
+  const dim3 g1((unsigned)((U + TS - 1) / TS), (unsigned)nparts);
   if (dtype == NR_BF16) {
     __bf16* ub = (__bf16*)(w + L.ub);
-    const int64_t n8 = U * D / 8;
-    hipLaunchKernelGGL(topk_bf16_users_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, n8, users, ub);
-    NR_CHECK_LAUNCH(fn);
+    const int rcb = bf16_users_launch(U, users, ub, st, fn);
+    if (rcb) return rcb;
     hipLaunchKernelGGL(topk_stage1_kernel<__bf16>, g1, dim3(256), 0, st, U, N, (const __bf16*)ub,
                        (const __bf16*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, (int)K, span * kChunk, part);
   } else {

@@ -161,6 +161,33 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     return {"news_index": _host(idx), "scores": _host(scores)}
 
 
+def get_full_table_ranks(history_rev_index: np.ndarray, history_len_list: np.ndarray, target_index: np.ndarray,
+                         target_len_list: np.ndarray, news_embeddings: torch.Tensor, attention_model: torch.nn.Module,
+                         exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
+                         dtype=None) -> dict:
+    """Where the given news stand among ALL news of the table for each impression's
+    user: ``{"ranks": int32 [T]}`` on the host, in the order of ``target_index``
+    (``target_len_list[i]`` rows of ``news_embeddings`` for impression i, e.g. its
+    clicked candidates).  A rank is the number of eligible news the model puts before
+    the target (score descending, ties by ascending news row): 0 is the top
+    recommendation, and the targets with rank < k are exactly the rows
+    get_top_k_recommendations returns for that k.  -1 marks a target that is in the
+    impression's own history (with ``exclude_history``) or outside the table.
+    evaluation.retrieval_metrics turns the ranks into hit / recall / nDCG@K, MRR and
+    the mean and median rank against the whole catalogue.
+
+    The reference has no counterpart: its AUC / MRR / nDCG are taken over the handful
+    of candidates an impression lists.  This is PoolScoreEngine.rank_targets (the
+    users x table MFMA product of the top-K path with a counting epilogue,
+    include/newsrec_fullrank.h)."""
+    eng = _engine(attention_model, news_embeddings, query_news_embeddings if isinstance(query_news_embeddings,
+                                                                                        torch.Tensor) else None,
+                  dtype=dtype)
+    n = len(history_len_list)
+    eng.load_impressions(history_rev_index, history_len_list, np.zeros(0, np.int32), np.zeros(n, np.int32))
+    return {"ranks": _host(eng.rank_targets(target_index, target_len_list, exclude_history=exclude_history))}
+
+
 def get_embeddings(model_path: str, news_list: Iterable[str], news_text_dict: dict[str, str]):
     """Title encoder entry (data_model_helper.py:45-84): see encoder.py."""
     from .encoder import get_embeddings as _ge

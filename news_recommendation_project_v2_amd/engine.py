@@ -244,6 +244,67 @@ class PoolScoreEngine:
             return idx[sel], scores[sel]
         return idx, scores
 
+    def rank_targets(self, tgt_idx, tgt_len, exclude_history: bool = True, user_block: Optional[int] = None):
+        """Full-table ranks of given news per impression (ops.rank_targets over the pooled
+        users): int32 [T] in the caller's target order, ``tgt_len[i]`` targets (rows of the
+        news table, e.g. the clicked candidates) for impression i.  A rank is the number
+        of eligible news that beat the target in recommend's order, 0 for the best; -1 for
+        a target that is in the impression's own history (with ``exclude_history``) or
+        outside the table.  The targets with rank < k are exactly recommend(k)'s rows.
+        Distinct histories are pooled once: with the deduplicated CSR the impressions'
+        targets are grouped under their distinct user (a stable sort) and the ranks
+        scattered back.  ``user_block`` bounds the workspace; the results depend on neither."""
+        tgt_idx = np.ascontiguousarray(tgt_idx, dtype=np.int32)
+        tgt_len = np.asarray(tgt_len, dtype=np.int64)
+        if len(tgt_len) != self.n_imp:
+            raise ValueError("Number of rows should be consistent")
+        _check_segments(tgt_idx, tgt_len, "target")
+        self.hist_table = self.transform(out=self.hist_table)
+        self.inv_norms()
+        if self.user_idx is not None:
+            hidx, hoff = self.uhist_idx, self.uhist_off
+        else:
+            hidx, hoff = self.hist_idx, self.hist_off
+        n_u = hoff.numel() - 1
+        n_t = len(tgt_idx)
+        ranks = torch.empty(n_t, dtype=torch.int32, device=self.device)
+        if n_t == 0 or n_u == 0:
+            return ranks
+        order = None
+        if self.user_idx is not None:  # the impressions' targets under their distinct user, in impression order
+            owner = np.repeat(self.user_idx.cpu().numpy().astype(np.int64), tgt_len)
+            order = np.argsort(owner, kind="stable")
+            tgt_idx = tgt_idx[order]
+            toff = lengths_to_offsets(np.bincount(owner, minlength=n_u))
+        else:
+            toff = lengths_to_offsets(tgt_len)
+        if self._users is None or self._users.shape[0] != n_u:
+            self._users = torch.empty((n_u, 1024), dtype=torch.float32, device=self.device)
+        users = ops.pool_users(self.pooler, self.hist_table, hidx, hoff, out=self._users)
+        tidx_d = _upload(tgt_idx, self.device)
+        blk = n_u if not user_block else max(1, min(int(user_block), n_u))
+        n_news = self.cand_table.shape[0]
+        most = max(int(toff[min(u0 + blk, n_u)] - toff[u0]) for u0 in range(0, n_u, blk))
+        need = ops.rank_targets_workspace_bytes(self.dtype, blk, n_news, most)
+        self._rank_ws = ops.grow_workspace(getattr(self, "_rank_ws", None), max(need, 256), self.device)
+        sorted_ranks = ranks if order is None else torch.empty_like(ranks)
+        for u0 in range(0, n_u, blk):
+            u1 = min(u0 + blk, n_u)
+            a, b = int(toff[u0]), int(toff[u1])
+            if a == b:
+                continue
+            eidx = eoff = None
+            if exclude_history:
+                # the block's own CSR: offsets rebased on the device, indices shared
+                eoff = hoff[u0:u1 + 1] - hoff[u0:u0 + 1] if u0 else hoff[:u1 + 1]
+                eidx = hidx[int(self._hoff_host(hoff)[u0]):] if u0 else hidx
+            ops.rank_targets(users[u0:u1], self.cand_table, self.cand_inv, tidx_d[a:b],
+                             _upload(toff[u0:u1 + 1] - a, self.device), excl_idx=eidx, excl_off=eoff,
+                             out=sorted_ranks[a:b], workspace=self._rank_ws)
+        if order is not None:
+            ranks[_upload(order, self.device)] = sorted_ranks
+        return ranks
+
     def _hoff_host(self, hoff: torch.Tensor) -> np.ndarray:
         """Host copy of a history offset array (one read-back per loaded impression set)."""
         cache = getattr(self, "_hoff_cache", None)

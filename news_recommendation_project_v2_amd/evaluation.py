@@ -201,3 +201,53 @@ def score_device(ranks, labels, offsets) -> dict:
                 m[i, 3] = ndcg_score(y_true, y_score, 10)
     return {"auc": np.mean(m[:, 0]).item(), "mrr": np.mean(m[:, 1]).item(), "ndcg5": np.mean(m[:, 2]).item(),
             "ndcg10": np.mean(m[:, 3]).item(), "num_samples": int(len(m))}
+
+
+def retrieval_metrics(ranks, target_len, ks: Sequence[int] = (1, 5, 10, 64, 100, 1000)) -> dict:
+    """Retrieval metrics against the WHOLE news table from full-table ranks
+    (data_model_helper.get_full_table_ranks; the reference has no counterpart, its
+    metrics above are taken over an impression's listed candidates only).
+
+    ``ranks`` int [T]: per target, the number of eligible news ranked before it (0 = the
+    top recommendation), -1 for a target that is not eligible; ``target_len`` [I]: targets
+    per impression.  Host numpy in float64.  An impression with no target of rank >= 0 is
+    left out and counted in ``impressions_skipped``.  Per impression with n eligible targets,
+    then averaged over the impressions:
+      hit@K     1 if any target has rank < K
+      recall@K  targets with rank < K / n
+      ndcg@K    sum over targets with rank < K of 1 / log2(rank + 2), over the ideal DCG
+                sum_{i < min(n, K)} 1 / log2(i + 2)
+      mrr       1 / (1 + best rank)
+    ``mean_rank`` and ``median_rank`` are taken over the eligible targets."""
+    r = np.asarray(ranks, dtype=np.int64)
+    lens = np.asarray(target_len, dtype=np.int64)
+    if len(lens) and lens.min() < 0 or int(lens.sum()) != len(r):
+        raise ValueError("target_len must be >= 0 and sum to the number of ranks")
+    n_imp = len(lens)
+    imp = np.repeat(np.arange(n_imp), lens)
+    ok = r >= 0
+    n = np.bincount(imp[ok], minlength=n_imp).astype(np.float64)
+    keep = n > 0
+    out = {"impressions": int(keep.sum()), "impressions_skipped": int(n_imp - keep.sum()), "targets": int(ok.sum())}
+    ri, ii = r[ok].astype(np.float64), imp[ok]
+    nk = n[keep]
+    mean = lambda per_imp: float(per_imp[keep].mean()) if keep.any() else float("nan")
+    for k in ks:
+        k = int(k)
+        inside = ri < k
+        hits = np.bincount(ii[inside], minlength=n_imp).astype(np.float64)
+        dcg = np.bincount(ii[inside], weights=1.0 / np.log2(ri[inside] + 2.0), minlength=n_imp)
+        # ideal DCG of min(n, K) targets at ranks 0, 1, ...: a prefix sum of the discounts
+        top = int(min(nk.max(), k)) if keep.any() else 0
+        ideal = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(top) + 2.0))])
+        idcg = np.ones(n_imp)
+        idcg[keep] = ideal[np.minimum(nk, k).astype(np.int64)]
+        out[f"hit@{k}"] = mean((hits > 0).astype(np.float64))
+        out[f"recall@{k}"] = mean(hits / np.maximum(n, 1.0))
+        out[f"ndcg@{k}"] = mean(dcg / idcg)
+    best = np.full(n_imp, np.inf)
+    np.minimum.at(best, ii, ri)
+    out["mrr"] = mean(1.0 / (1.0 + best))
+    out["mean_rank"] = float(ri.mean()) if len(ri) else float("nan")
+    out["median_rank"] = float(np.median(ri)) if len(ri) else float("nan")
+    return out

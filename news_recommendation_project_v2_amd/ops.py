@@ -357,6 +357,71 @@ def topk_users(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: tor
     return idx, scores
 
 
+def rank_targets_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, n_targets: int) -> int:
+    """nr_rank_targets_workspace_bytes (include/newsrec_fullrank.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_rank_targets_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, n_targets))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"rank_targets: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, T = {n_targets}; "
+            "U >= 1, 1 <= N <= 2^22, T < 2^31)")
+    return need
+
+
+def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, tgt_idx: torch.Tensor,
+                 tgt_off: torch.Tensor, excl_idx: Optional[torch.Tensor] = None,
+                 excl_off: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Full-table ranks of target rows (nr_rank_targets): for the targets
+    tgt_idx[tgt_off[u]:tgt_off[u + 1]] (int32, int64 [U + 1]) of user row u, int32 [T]
+    with the number of eligible rows of ``cand_table`` that beat the target in top-K's
+    order (score descending, ties by ascending row); 0 is the best row, -1 a target
+    that is excluded itself or outside the table.  For k <= 64 the targets with
+    rank < k are exactly the rows topk_users returns.  The exclusion CSR is as
+    topk_users takes it; its entries and the target offsets are checked here (one
+    small sync).  ``out`` = int32 [T] to write into."""
+    dev = _dev(users, cand_table, cand_inv_norm, tgt_idx, tgt_off, excl_idx, excl_off, workspace, out)
+    if users.dtype != torch.float32 or users.dim() != 2 or not users.is_contiguous():
+        raise _lib.NewsRecHIPError("rank_targets: users must be contiguous f32 [U, D]")
+    n_users, dim = users.shape
+    n_news = cand_table.shape[0]
+    ld = _rowmajor(cand_table, "cand_table")
+    if cand_table.shape[1] != dim:
+        raise _lib.NewsRecHIPError("rank_targets: users and cand_table must share their width")
+    if cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < n_news or not cand_inv_norm.is_contiguous():
+        raise _lib.NewsRecHIPError("cand_inv_norm must be contiguous f32 with one entry per candidate-table row")
+    _check_csr(tgt_idx, tgt_off, "tgt")
+    n_tgt = tgt_idx.numel()
+    if tgt_off.numel() != n_users + 1:
+        raise _lib.NewsRecHIPError("rank_targets: tgt_off must have U + 1 entries")
+    if (int(tgt_off[0]) != 0 or int(tgt_off[-1]) != n_tgt
+            or (n_users > 1 and not bool((tgt_off[1:] >= tgt_off[:-1]).all()))):
+        raise _lib.NewsRecHIPError(f"rank_targets: tgt_off must ascend from 0 to the {n_tgt} targets")
+    if (excl_idx is None) != (excl_off is None):
+        raise _lib.NewsRecHIPError("rank_targets: excl_idx and excl_off go together")
+    if excl_idx is not None:
+        _check_csr(excl_idx, excl_off, "excl")
+        if excl_off.numel() != n_users + 1:
+            raise _lib.NewsRecHIPError("rank_targets: excl_off must have U + 1 entries")
+        if excl_idx.numel():
+            lo, hi = (int(v) for v in torch.aminmax(excl_idx))
+            if lo < 0 or hi >= n_news:
+                raise IndexError(f"rank_targets: excluded row {lo if lo < 0 else hi} is outside the {n_news} table rows")
+        else:  # no storage behind an empty tensor; the kernel never reads it
+            excl_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+    if out is None:
+        out = torch.empty(n_tgt, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.shape != (n_tgt,) or not out.is_contiguous():
+        raise _lib.NewsRecHIPError(f"rank_targets: out must be contiguous int32 of shape {(n_tgt,)}")
+    dt = _dtype(cand_table, "cand_table")
+    ws = grow_workspace(workspace, max(rank_targets_workspace_bytes(cand_table.dtype, n_users, n_news, n_tgt), 256), dev)
+    if n_tgt == 0:
+        return out
+    _lib.call("nr_rank_targets", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm),
+              _ptr(excl_idx), _ptr(excl_off), n_tgt, _ptr(tgt_idx), _ptr(tgt_off), _ptr(out), _ptr(ws), ws.numel(),
+              _stream(dev))
+    return out
+
+
 def dense_rank(scores: torch.Tensor, cand_off: torch.Tensor, check: bool = True) -> torch.Tensor:
     """Per-impression dense descending ranks (int32), scipy rankdata(-x, 'dense')."""
     dev = _dev(scores, cand_off)

@@ -5,10 +5,15 @@ has no counterpart -- it only scores the candidates an impression lists).
 
     python scripts/recommend.py --pooler {final,latent} --dtype {f32,bf16} -k K [--keep-history] --synthetic
     python scripts/recommend.py --data-dir data --emb-dir new_embeddings --split MINDsmall_dev -k 10
+    python scripts/recommend.py --synthetic --evaluate [--ks 10,64,100]
 
 Prints one JSON line per run and writes {out-dir}/recommendations.npy: an int32
 [I, K] array of rows of the split's news list (-1 where fewer than K are eligible).
 --keep-history lets an impression's own history appear in its list.
+--evaluate adds retrieval metrics against the WHOLE news list to the JSON line: the
+full-table ranks of each impression's clicked candidates (label 1)
+(data_model_helper.get_full_table_ranks) as hit / recall / nDCG at each K of --ks, MRR
+and the mean and median rank (evaluation.retrieval_metrics).
 """
 from __future__ import annotations
 
@@ -45,6 +50,9 @@ def main():
     ap.add_argument("--split", default="MINDsmall_dev")
     ap.add_argument("--num-impressions", type=int, default=None)
     ap.add_argument("--out-dir", type=Path, default=Path("logs"))
+    ap.add_argument("--evaluate", action="store_true",
+                    help="rank each impression's clicked candidates against the whole news list and report metrics")
+    ap.add_argument("--ks", default="1,5,10,64,100,1000", help="the K of hit@K / recall@K / ndcg@K with --evaluate")
     args = ap.parse_args()
 
     model = FinalAttention(1024, 4096) if args.pooler == "final" else LatentAttentionModel()
@@ -81,11 +89,26 @@ def main():
     path = args.out_dir / "recommendations.npy"
     np.save(path, idx)
     have = idx >= 0
-    print(json.dumps({"split": args.split, "pooler": args.pooler, "dtype": args.dtype, "k": args.k,
-                      "exclude_history": not args.keep_history, "impressions": int(idx.shape[0]),
-                      "news": int(out["news_embeddings"].shape[0]), "filled": float(have.mean()) if idx.size else 1.0,
-                      "mean_top1_score": float(scores[:, 0][have[:, 0]].mean()) if have[:, :1].any() else None,
-                      "ms": round(ms, 1), "out": str(path)}), flush=True)
+    line = {"split": args.split, "pooler": args.pooler, "dtype": args.dtype, "k": args.k,
+            "exclude_history": not args.keep_history, "impressions": int(idx.shape[0]),
+            "news": int(out["news_embeddings"].shape[0]), "filled": float(have.mean()) if idx.size else 1.0,
+            "mean_top1_score": float(scores[:, 0][have[:, 0]].mean()) if have[:, :1].any() else None,
+            "ms": round(ms, 1), "out": str(path)}
+    if args.evaluate:
+        from news_recommendation_project_v2_amd.evaluation import retrieval_metrics
+        labels = out["labels"]
+        clicked = np.concatenate([np.asarray(l) for l in labels]) > 0 if len(labels) else np.zeros(0, bool)
+        tgt_len = np.array([int((np.asarray(l) > 0).sum()) for l in labels], dtype=np.int64)
+        t0 = time.perf_counter()
+        ranks = dmh.get_full_table_ranks(out["history_rev_ind_array"][0], out["history_len_list"],
+                                         np.asarray(out["impression_rev_ind_array"][0])[clicked], tgt_len,
+                                         out["news_embeddings"], model, exclude_history=not args.keep_history,
+                                         dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)["ranks"]
+        line["evaluate_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+        metrics = retrieval_metrics(ranks, tgt_len, ks=[int(k) for k in args.ks.split(",")])
+        line["impressions_evaluated"] = metrics.pop("impressions")  # ("impressions" stays the number recommended for)
+        line.update(metrics)
+    print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,408 @@
+"""Full-table ranks (csrc/fullrank.hip, include/newsrec_fullrank.h) on the GPU against the
+float64 reference of tests/fullrank_ref.py and against top-K retrieval itself.
+
+Bounds.  eps = 1e-4 on the cosine scale is the worst-case f32 accumulation bound of a
+1024-term dot product (1024 * 2^-24 = 6.1e-5 by Cauchy-Schwarz, plus the scale roundings),
+the bound tests/test_topk_gpu.py derives; it is not fitted to a run.  In bf16 mode the
+reference is the float64 score of the SAME operands (users and table rounded to bf16,
+cand_inv as the evaluation path computes it), so the same bound holds.  A rank is then
+known up to the rows whose reference score lies within eps of the target's:
+#{ref > s_t + eps} <= rank <= #{ref >= s_t - eps} over the eligible rows other than t.
+
+Everything else is exact: planted rows >= 1e-2 apart (the construction of
+tests/test_topk_gpu.py, restated here), bit-identical duplicate rows, and the agreement
+with ops.topk_users, which rests on both features running one copy of the tile main loop.
+"""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+import torch
+
+import fullrank_ref
+import topk_ref
+from news_recommendation_project_v2_amd import weights as W
+
+D = 1024
+EPS = 1e-4
+DTYPES = [torch.float32, torch.bfloat16]
+IDS = ["f32", "bf16"]
+
+
+def _chunk():
+    from news_recommendation_project_v2_amd import _lib
+    return int(_lib.load().nr_topk_chunk_rows())
+
+
+def _rounded(x: np.ndarray, dtype) -> np.ndarray:
+    """float64 values of x after rounding to the compute dtype."""
+    return torch.from_numpy(np.asarray(x, dtype=np.float32)).to(dtype).double().numpy()
+
+
+def _csr(lists, dev):
+    off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int64)
+    idx = (np.concatenate([np.asarray(l, dtype=np.int32) for l in lists]) if len(lists) and off[-1]
+           else np.zeros(0, np.int32)).astype(np.int32)
+    return idx, off, torch.from_numpy(idx).to(dev), torch.from_numpy(off).to(dev)
+
+
+class Case:
+    """Operands on the device, the float64 reference scores of the same operands."""
+
+    def __init__(self, users, table, dtype, dev, want_ref=True):
+        from news_recommendation_project_v2_amd import ops
+        self.dtype, self.dev = dtype, dev
+        self.users = torch.from_numpy(np.ascontiguousarray(users, dtype=np.float32)).to(dev)
+        self.table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float32)).to(dev).to(dtype).contiguous()
+        self.inv = ops.row_inv_norm(self.table, 1e-8)
+        self.U, self.N = self.users.shape[0], self.table.shape[0]
+        if want_ref:
+            u64 = (_rounded(users, dtype) if dtype == torch.bfloat16
+                   else np.asarray(users, dtype=np.float32).astype(np.float64))
+            self.ref = topk_ref.cosine_scores(u64, self.table.double().cpu().numpy(), self.inv.double().cpu().numpy())
+
+    def rank(self, targets, excl=None):
+        """int32 ranks of the per-user target lists, as one flat array and its offsets."""
+        from news_recommendation_project_v2_amd import ops
+        tidx, toff, ti, to = _csr(targets, self.dev)
+        ei = eo = None
+        if excl is not None:
+            _, _, ei, eo = _csr(excl, self.dev)
+        r = ops.rank_targets(self.users, self.table, self.inv, ti, to, excl_idx=ei, excl_off=eo)
+        torch.cuda.synchronize()
+        assert r.dtype == torch.int32 and r.shape == (len(tidx),)
+        return r.cpu().numpy(), toff
+
+    def topk_rows(self, k, excl=None):
+        from news_recommendation_project_v2_amd import ops
+        ei = eo = None
+        if excl is not None:
+            _, _, ei, eo = _csr(excl, self.dev)
+        idx, _ = ops.topk_users(self.users, self.table, self.inv, k, excl_idx=ei, excl_off=eo)
+        return idx.cpu().numpy()
+
+
+# ------------------------------------------------------------------ 1. planted, exact
+def _planted(k, n_news, dtype, dev, seed, n_users=3, spread=None):
+    """Orthonormal users (scaled), K + 8 planted rows per user with cosines 0.9, 0.88, ...,
+    a background at cosine -0.56 with every user; rows planted for a user are excluded for
+    the others.  Returns (case, planted rows [U][K + 8] best first, exclusion lists)."""
+    rng = np.random.default_rng(seed)
+    P = k + 8
+    q, _ = np.linalg.qr(rng.standard_normal((D, n_users)))
+    e = q.T                                  # users' directions, orthonormal
+    noise = rng.standard_normal((n_news, D))  # a random unit direction per row, orthogonal to the users
+    noise -= (noise @ e.T) @ e
+    noise /= np.sqrt((noise * noise).sum(1, keepdims=True))
+    bg = -0.56 * e.sum(0)
+    table = bg[None, :] + np.sqrt(1.0 - n_users * 0.56 ** 2) * noise[:n_news]
+    where = rng.permutation(n_news if spread is None else spread)[:n_users * P].reshape(n_users, P)
+    if spread is not None:                   # planted rows alternate between the first rows and the last ones
+        where[:, 1::2] = n_news - 1 - where[:, 1::2]
+    for u in range(n_users):
+        for j in range(P):
+            c = 0.9 - 0.02 * j
+            table[where[u, j]] = c * e[u] + np.sqrt(1.0 - c * c) * noise[where[u, j]]
+    table *= rng.uniform(0.5, 2.0, (n_news, 1))
+    users = e * np.array([1.0, 0.37, 12.5, 3.0, 0.01][:n_users])[:, None]
+    case = Case(users, table, dtype, dev)
+    excl = [np.concatenate([where[v] for v in range(n_users) if v != u]) for u in range(n_users)]
+    # before any call: the planted scores are >= 1e-2 apart and >= 1e-2 above the rest
+    for u in range(n_users):
+        ref = case.ref[u].copy()
+        ref[excl[u]] = -np.inf
+        top = ref[where[u]]
+        assert (top[:-1] - top[1:] >= 1e-2).all(), "planted scores closer than 1e-2"
+        rest = np.delete(ref, where[u])
+        assert top[-1] - rest.max() >= 1e-2, "last planted score within 1e-2 of the rest"
+    return case, where, excl
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("shape", ["1000", "2c+77"])
+def test_gpu_fullrank_planted_exact(gpu_device, shape, dtype):
+    """The j-th planted row of a user has rank exactly j; a row planted for another user
+    (excluded) has rank -1.  In the long table the planted rows lie at both ends."""
+    c = _chunk()
+    N, spread = (1000, None) if shape == "1000" else (2 * c + 77, 190)
+    case, where, excl = _planted(10, N, dtype, gpu_device, seed=21, spread=spread)
+    if spread is not None:
+        assert (where < c).any() and (where >= 2 * c).any()
+    P = where.shape[1]
+    targets = [np.concatenate([where[u], where[(u + 1) % 3][:4], where[u][:2]]) for u in range(3)]
+    r, toff = case.rank(targets, excl)
+    for u in range(3):
+        got = r[toff[u]:toff[u + 1]]
+        assert got[:P].tolist() == list(range(P)), (u, got[:P])
+        assert got[P:P + 4].tolist() == [-1] * 4      # excluded targets
+        assert got[P + 4:].tolist() == [0, 1]         # duplicate targets get their own answer
+    assert np.array_equal(r, fullrank_ref.rank_targets(case.ref, np.concatenate(targets), toff, *_csr(excl, "cpu")[:2]))
+
+
+# ------------------------------------------------------------------ 2. permutation, top-K agreement
+def _random_users_table(U, N, seed, zero_user=None):
+    rng = np.random.default_rng(seed)
+    table = rng.standard_normal((N, D)).astype(np.float32) * rng.uniform(0.5, 2.0, (N, 1)).astype(np.float32) + 0.05
+    users = rng.standard_normal((U, D)).astype(np.float32) * 0.7 + 0.05
+    if zero_user is not None:
+        users[zero_user] = 0.0
+    return rng, users, table
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_gpu_fullrank_permutation_and_topk_sets(gpu_device, dtype):
+    """Every row a target of every user (1,000 targets per user: far past anything staged):
+    the ranks of the eligible rows are a permutation of 0 .. E - 1, the excluded rows get
+    -1, and for K in {1, 10, 64} the targets with rank < K are exactly top-K's rows."""
+    N = 1000
+    rng, users, table = _random_users_table(3, N, 31, zero_user=1)
+    case = Case(users, table, dtype, gpu_device, want_ref=False)
+    excl = [rng.integers(0, N, 40), np.array([0, 3, 3, 999, 10]), np.zeros(0, np.int64)]
+    r, toff = case.rank([np.arange(N)] * 3, excl)
+    r = r.reshape(3, N)
+    for u in range(3):
+        banned = np.zeros(N, dtype=bool)
+        banned[excl[u]] = True
+        assert (r[u][banned] == -1).all()
+        assert np.array_equal(np.sort(r[u][~banned]), np.arange(N - banned.sum())), u
+    # the zero user scores 0 everywhere: the number of eligible rows below the target
+    banned = np.zeros(N, dtype=bool)
+    banned[excl[1]] = True
+    assert np.array_equal(r[1][~banned], np.arange(N - banned.sum()))
+    for k in (1, 10, 64):
+        top = case.topk_rows(k, excl)
+        for u in range(3):
+            assert set(np.nonzero((r[u] >= 0) & (r[u] < k))[0].tolist()) == set(top[u].tolist()), (k, u)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_gpu_fullrank_topk_sets_across_chunks(gpu_device, dtype):
+    """N = 2 chunks + 77: 2,000 sampled targets plus top-64's rows per user."""
+    N = 2 * _chunk() + 77
+    rng, users, table = _random_users_table(3, N, 32, zero_user=2)
+    case = Case(users, table, dtype, gpu_device, want_ref=False)
+    excl = [rng.integers(0, N, 50), np.zeros(0, np.int64), np.array([0, 1, 1, N - 1, 5])]
+    tops = {k: case.topk_rows(k, excl) for k in (1, 10, 64)}
+    targets = [np.concatenate([rng.choice(N, 2000, replace=False), tops[64][u]]) for u in range(3)]
+    r, toff = case.rank(targets, excl)
+    for u in range(3):
+        t, ru = targets[u], r[toff[u]:toff[u + 1]]
+        banned = np.zeros(N, dtype=bool)
+        banned[excl[u]] = True
+        assert ((ru == -1) == banned[t]).all()
+        # distinct eligible targets have distinct ranks below the eligible count; a repeated target repeats its rank
+        by_row = {}
+        for row, rank in zip(t.tolist(), ru.tolist()):
+            assert by_row.setdefault(row, rank) == rank
+        good = [v for v in by_row.values() if v >= 0]
+        assert len(set(good)) == len(good) and max(good) < N - banned.sum()
+        for k in (1, 10, 64):
+            assert {row for row, rank in by_row.items() if 0 <= rank < k} == set(tops[k][u].tolist()), (k, u)
+
+
+# ------------------------------------------------------------------ 3. band
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("shape", ["1x1000", "257x1000", "5x2c+77"])
+def test_gpu_fullrank_random_banded(gpu_device, shape, dtype):
+    U, N = {"1x1000": (1, 1000), "257x1000": (257, 1000), "5x2c+77": (5, 2 * _chunk() + 77)}[shape]
+    rng, users, table = _random_users_table(U, N, U * 7 + 3)
+    case = Case(users, table, dtype, gpu_device)
+    targets = [rng.integers(0, N, rng.integers(2, 5)) for _ in range(U)]
+    excl = [rng.integers(0, N, rng.integers(0, 40)) if u % 3 == 0 else np.zeros(0, np.int64) for u in range(U)]
+    r, toff = case.rank(targets, excl)
+    worst, widest = 0, 0
+    for u in range(U):
+        ok = np.ones(N, dtype=bool)
+        ok[excl[u]] = False
+        for t, got in zip(targets[u], r[toff[u]:toff[u + 1]]):
+            if not ok[t]:
+                assert got == -1
+                continue
+            others = ok.copy()
+            others[t] = False
+            s = case.ref[u][others]
+            lo, hi = int((s > case.ref[u, t] + EPS).sum()), int((s >= case.ref[u, t] - EPS).sum())
+            worst = max(worst, lo - got, got - hi)
+            widest = max(widest, hi - lo)
+            assert lo <= got <= hi, (u, t, lo, got, hi)
+    print(f"band: every rank inside its reference band (widest band {widest} rows, worst excess {worst}; eps {EPS:.0e})")
+
+
+# ------------------------------------------------------------------ 4. exact ties across tiles and chunks
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_gpu_fullrank_ties_across_tiles_and_chunks(gpu_device, dtype):
+    """Bit-identical rows a < chunk <= b, and p < q inside one tile: the row rule decides,
+    so rank(b) = rank(a) + 1; with a excluded, b takes a's place."""
+    c = _chunk()
+    N = 2 * c + 77
+    rng, users, table = _random_users_table(3, N, 41)
+    a, b, p, q = 70, c + 5, 130, 141
+    assert a // 128 != b // 128 and a < c <= b and p // 128 == q // 128
+    table[b] = table[a]
+    table[q] = table[p]
+    case = Case(users, table, dtype, gpu_device, want_ref=False)
+    tg = [np.array([a, b, p, q])] * 3
+    r, _ = case.rank(tg)
+    r = r.reshape(3, 4)
+    assert (r[:, 1] == r[:, 0] + 1).all() and (r[:, 3] == r[:, 2] + 1).all(), r
+    r2, _ = case.rank(tg, [np.array([a]), np.array([p, p]), np.array([a, p])])
+    r2 = r2.reshape(3, 4)
+    assert r2[0].tolist() == [-1, r[0, 0], r[0, 2] - (r[0, 0] < r[0, 2]), r[0, 3] - (r[0, 0] < r[0, 3])]
+    assert r2[1].tolist() == [r[1, 0] - (r[1, 2] < r[1, 0]), r[1, 1] - (r[1, 2] < r[1, 1]), -1, r[1, 2]]
+    assert r2[2, 0] == r2[2, 2] == -1
+    assert r2[2, 1] == r[2, 0] - (r[2, 2] < r[2, 0]) and r2[2, 3] == r[2, 2] - (r[2, 0] < r[2, 2])
+
+
+# ------------------------------------------------------------------ 5. launch forms, determinism, long exclusion lists
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_gpu_fullrank_many_users_walk_chunks_in_sequence(gpu_device, dtype):
+    """With enough user blocks to fill the device a workgroup walks several chunks with
+    one set of counters (and re-stages the exclusions at each chunk boundary); the ranks are
+    those of the same users run alone, chunk by chunk side by side with atomics.  Two runs
+    give the same bits."""
+    from news_recommendation_project_v2_amd import ops
+    c, U = _chunk(), 65536
+    N = 2 * c + 77
+    gen = torch.Generator(device=gpu_device).manual_seed(9)
+    table = torch.randn((N, D), generator=gen, device=gpu_device).to(dtype)
+    users = torch.randn((U, D), generator=gen, device=gpu_device)
+    inv = ops.row_inv_norm(table, 1e-8)
+    sel = [0, 127, 128, 40000, U - 1]
+    small = users[sel].contiguous()
+    top, _ = ops.topk_users(small, table, inv, 3)
+    edge = [c - 1, c, c + 5, 2 * c, 2 * c + 76, c - 1]
+    lists = {u: np.concatenate([top[i].cpu().numpy(), edge]) for i, u in enumerate(sel)}
+    rng = np.random.default_rng(5)
+    tgts = {u: np.concatenate([rng.integers(0, N, 3 + 10 * i), [0, c - 2, c + 1, N - 1, lists[u][0]]])
+            for i, u in enumerate(sel)}  # 8 .. 48 targets: within and past those staged per user; one excluded
+    _, _, ei_s, eo_s = _csr([lists[u] for u in sel], gpu_device)
+    _, _, ei_b, eo_b = _csr([lists.get(u, ()) for u in range(U)], gpu_device)
+    _, to_s, ti_s, tof_s = _csr([tgts[u] for u in sel], gpu_device)
+    _, to_b, ti_b, tof_b = _csr([tgts.get(u, ()) for u in range(U)], gpu_device)
+    r_s = ops.rank_targets(small, table, inv, ti_s, tof_s, excl_idx=ei_s, excl_off=eo_s)
+    r_b = ops.rank_targets(users, table, inv, ti_b, tof_b, excl_idx=ei_b, excl_off=eo_b)
+    r_b2 = ops.rank_targets(users, table, inv, ti_b, tof_b, excl_idx=ei_b, excl_off=eo_b)
+    r_s2 = ops.rank_targets(small, table, inv, ti_s, tof_s, excl_idx=ei_s, excl_off=eo_s)
+    torch.cuda.synchronize()
+    assert torch.equal(r_b, r_s) and torch.equal(r_b2, r_b) and torch.equal(r_s2, r_s)
+    r = r_s.cpu().numpy()
+    for i, u in enumerate(sel):
+        got = r[to_s[i]:to_s[i + 1]]
+        assert got[-1] == -1 and ((got == -1) == np.isin(tgts[u], lists[u])).all()
+        # the excluded top 3 are gone: nothing else can have moved past rank N - 1 - 8
+        assert got.max() < N - len(set(lists[u].tolist()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_gpu_fullrank_long_exclusion_list(gpu_device, dtype):
+    """More excluded rows in one chunk than are staged per user: the whole-workgroup path.
+    Planted case: the two other users' planted rows, 60 background rows and the user's own
+    three best are excluded, so its j-th planted row has rank j - 3."""
+    case, where, excl = _planted(10, 1000, dtype, gpu_device, seed=22)
+    P = where.shape[1]
+    rng = np.random.default_rng(2)
+    bg = np.setdiff1d(np.arange(1000), where.reshape(-1))
+    ex = [np.concatenate([excl[u], rng.choice(bg, 60, replace=False), where[u, :3], where[u, :3]]) for u in range(3)]
+    ex[2] = excl[2][:5]  # one user stays on the staged path: the other users' rows count again
+    assert min(len(set(e.tolist())) for e in ex[:2]) > 32
+    targets = [np.concatenate([where[u], bg[:5]]) for u in range(3)]
+    r, toff = case.rank(targets, ex)
+    for u in range(3):
+        got = r[toff[u]:toff[u + 1]]
+        # (a row planted for another user has cosine 0 with this one: below its planted rows, above the background)
+        assert got[:P].tolist() == ([-1] * 3 + list(range(P - 3)) if u < 2 else list(range(P))), (u, got)
+        gone = np.isin(bg[:5], ex[u])
+        assert (got[P:][gone] == -1).all() and (got[P:][~gone] >= (P - 3 if u < 2 else 3 * P - 5)).all()
+    want = fullrank_ref.rank_targets(case.ref, np.concatenate(targets), toff, *_csr(ex, "cpu")[:2])
+    for u in range(3):  # the planted rows are exact in the reference too (the background rows: a band, not exact)
+        assert np.array_equal(r[toff[u]:toff[u] + P], want[toff[u]:toff[u] + P])
+
+
+# ------------------------------------------------------------------ 6. engine and API
+def _model(pooler, dev):
+    from news_recommendation_project_v2_amd.latent_attention import LatentAttentionModel
+    from news_recommendation_project_v2_amd.modeling_utils import FinalAttention
+    if pooler == "final":
+        sd, m = W.final_attention_state_dict(5), FinalAttention(1024, 4096)
+    else:
+        sd, m = W.latent_attention_state_dict(5, ln_random=True), LatentAttentionModel()
+    m.load_state_dict(sd)
+    return m.to(dev).eval()
+
+
+def _impressions(pooler, n_news, n_imp, seed):
+    """About 40 impressions over 12 distinct histories (repeated: the deduplicated path)."""
+    rng = np.random.default_rng(seed)
+    distinct = [rng.integers(0, n_news, n).astype(np.int32) for n in rng.integers(1, 12, 12)]
+    if pooler == "final":  # an empty history (a zero user) among them; the latent pooler's 0 / 0 is not finite
+        distinct[3] = np.zeros(0, np.int32)
+    pick = rng.integers(0, 12, n_imp)
+    hl = np.array([len(distinct[p]) for p in pick], dtype=np.int32)
+    hi = np.concatenate([distinct[p] for p in pick]).astype(np.int32)
+    return rng, hi, hl
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pooler,dtype", [("final", torch.float32), ("latent", torch.bfloat16)])
+def test_gpu_engine_rank_targets_dedupe_and_user_block(gpu_device, pooler, dtype):
+    from news_recommendation_project_v2_amd.engine import PoolScoreEngine
+    n_news, n_imp = 300, 41
+    rng, hi, hl = _impressions(pooler, n_news, n_imp, 8)
+    tl = rng.integers(0, 6, n_imp).astype(np.int64)   # some impressions without a target
+    ti = rng.integers(0, n_news, int(tl.sum())).astype(np.int32)
+    off = np.concatenate([[0], np.cumsum(hl)])
+    first = int(np.nonzero((hl > 0) & (tl > 0))[0][0])
+    ti[int(tl[:first].sum())] = hi[off[first]]        # a target in its impression's own history
+    out = {}
+    for dedupe in (True, False):
+        eng = PoolScoreEngine(_model(pooler, gpu_device), dtype=dtype, device=gpu_device)
+        eng.load_news(W.news_table(5, n_news, 1024, name="fullrank"))
+        eng.load_impressions(hi, hl, np.zeros(0, np.int32), np.zeros(n_imp, np.int32), dedupe=dedupe)
+        assert (eng.user_idx is not None) == dedupe
+        for blk in (None, 2):
+            r = eng.rank_targets(ti, tl, user_block=blk)
+            torch.cuda.synchronize()
+            assert r.dtype == torch.int32 and r.shape == (len(ti),)
+            out[dedupe, blk] = r.cpu().numpy()
+        out[dedupe, "keep"] = eng.rank_targets(ti, tl, exclude_history=False).cpu().numpy()
+    for key in ((True, 2), (False, None), (False, 2)):
+        assert np.array_equal(out[key], out[True, None]), key
+    assert np.array_equal(out[True, "keep"], out[False, "keep"])
+    toff = np.concatenate([[0], np.cumsum(tl)])
+    in_hist = np.concatenate([np.isin(ti[toff[i]:toff[i + 1]], hi[off[i]:off[i + 1]]) for i in range(n_imp)])
+    assert in_hist.any() and ((out[True, None] == -1) == in_hist).all()
+    assert (out[True, "keep"] >= 0).all() and (out[True, "keep"][~in_hist] >= out[True, None][~in_hist]).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pooler", ["final", "latent"])
+def test_gpu_get_full_table_ranks(gpu_device, pooler):
+    """The API: every news a target of every impression; the rank < 10 sets are
+    get_top_k_recommendations' rows, with and without the history excluded."""
+    from news_recommendation_project_v2_amd import data_model_helper as dmh
+    n_news, n_imp, k = 300, 40, 10
+    _, hi, hl = _impressions(pooler, n_news, n_imp, 18)
+    table = W.news_table(5, n_news, 1024, name="fullrank-api")
+    m = _model(pooler, gpu_device)
+    every = np.tile(np.arange(n_news, dtype=np.int32), n_imp)
+    tl = np.full(n_imp, n_news, np.int64)
+    off = np.concatenate([[0], np.cumsum(hl)]).astype(np.int64)
+    for exclude in (True, False):
+        got = dmh.get_full_table_ranks(hi, hl, every, tl, table, m, exclude_history=exclude)
+        assert set(got) == {"ranks"}
+        r = got["ranks"]
+        assert isinstance(r, np.ndarray) and r.dtype == np.int32 and r.shape == (n_imp * n_news,)
+        r = r.reshape(n_imp, n_news)
+        top = dmh.get_top_k_recommendations(hi, hl, table, m, k, exclude_history=exclude)["news_index"]
+        for i in range(n_imp):
+            hist = np.unique(hi[off[i]:off[i + 1]]) if exclude else np.zeros(0, np.int64)
+            assert (r[i][hist] == -1).all() and (r[i] == -1).sum() == len(hist)
+            assert np.array_equal(np.sort(r[i][r[i] >= 0]), np.arange(n_news - len(hist)))
+            assert set(np.nonzero((r[i] >= 0) & (r[i] < k))[0].tolist()) == set(top[i].tolist()), i
