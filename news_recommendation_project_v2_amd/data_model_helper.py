@@ -141,7 +141,7 @@ def get_final_second_attention_score(history_rev_index: np.ndarray, history_len_
 def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: np.ndarray,
                               news_embeddings: torch.Tensor, attention_model: torch.nn.Module, k: int,
                               exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
-                              dtype=None) -> dict:
+                              dtype=None, diversify: Optional[float] = None, pool: Optional[int] = None) -> dict:
     """The k news of the WHOLE table that the model recommends per impression:
     ``{"news_index": int32 [I, k], "scores": float32 [I, k]}`` on the host, score
     descending, ties by ascending news row, ``(-1, -inf)`` where fewer than k news are
@@ -151,12 +151,28 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
 
     The reference has no counterpart: it only scores the candidates an impression
     lists.  This is PoolScoreEngine.recommend (users x table as one MFMA GEMM with
-    the K best kept per user as the tiles are produced, include/newsrec_topk.h)."""
+    the K best kept per user as the tiles are produced, include/newsrec_topk.h).
+
+    ``diversify`` = lambda in [0, 1] re-ranks for diversity (PoolScoreEngine.recommend_diverse,
+    greedy MMR, include/newsrec_rerank.h): the ``pool`` (default 64, at least k) best news
+    are retrieved and k of them picked one at a time, each maximising lambda * score -
+    (1 - lambda) * (largest cosine to a news already picked).  The lists are then in
+    pick order, the scores still the news' own, and the result gains ``"ild"`` float32
+    [I, 2], the intra-list diversity of the plain top-k list and of the returned one, and
+    ``"plain_scores"`` float32 [I, k], the plain top-k list's scores
+    (evaluation.diversity_metrics summarises them).  ``pool`` without ``diversify`` is refused."""
+    if diversify is None and pool is not None:
+        raise ValueError("get_top_k_recommendations: pool needs diversify")
     eng = _engine(attention_model, news_embeddings, query_news_embeddings if isinstance(query_news_embeddings,
                                                                                         torch.Tensor) else None,
                   dtype=dtype)
     n = len(history_len_list)
     eng.load_impressions(history_rev_index, history_len_list, np.zeros(0, np.int32), np.zeros(n, np.int32))
+    if diversify is not None:
+        idx, scores, ild, plain = eng.recommend_diverse(k, diversify, pool=64 if pool is None else pool,
+                                                        exclude_history=exclude_history, want_ild=True,
+                                                        want_plain=True)
+        return {"news_index": _host(idx), "scores": _host(scores), "ild": _host(ild), "plain_scores": _host(plain)}
     idx, scores = eng.recommend(k, exclude_history=exclude_history)
     return {"news_index": _host(idx), "scores": _host(scores)}
 

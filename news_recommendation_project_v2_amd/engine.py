@@ -203,15 +203,9 @@ class PoolScoreEngine:
         self.inv_norms()
         return self.pool_score(want_users=want_users, scores=scores)
 
-    def recommend(self, k: int, exclude_history: bool = True, user_block: Optional[int] = None):
-        """The k best news of the WHOLE table per impression (ops.topk_users over the
-        pooled users): (idx int32 [I, k], scores f32 [I, k]), score descending, ties by
-        ascending row, (-1, -inf) where fewer than k rows are eligible; the scores are
-        pool_score's for that (impression, news) pair bit for bit.  ``exclude_history``
-        leaves an impression's own history out of its list.  Distinct histories are
-        pooled and searched once (the deduplicated CSR when load_impressions built it).
-        ``user_block`` bounds the workspace by running the users in blocks of that many
-        rows; the results do not depend on it."""
+    def _recommend_distinct(self, k: int, exclude_history: bool, user_block: Optional[int]):
+        """recommend's lists per DISTINCT history (the deduplicated CSR when
+        load_impressions built it, else one per impression): (idx [n_u, k], scores [n_u, k])."""
         self.hist_table = self.transform(out=self.hist_table)
         self.inv_norms()
         if self.user_idx is not None:
@@ -239,10 +233,53 @@ class PoolScoreEngine:
             ops.topk_users(users[u0:u1], self.cand_table, self.cand_inv, k,
                            excl_idx=eidx if exclude_history else None, excl_off=eoff,
                            out=(idx[u0:u1], scores[u0:u1]), workspace=self._topk_ws)
-        if self.user_idx is not None:
+        return idx, scores
+
+    def recommend(self, k: int, exclude_history: bool = True, user_block: Optional[int] = None):
+        """The k best news of the WHOLE table per impression (ops.topk_users over the
+        pooled users): (idx int32 [I, k], scores f32 [I, k]), score descending, ties by
+        ascending row, (-1, -inf) where fewer than k rows are eligible; the scores are
+        pool_score's for that (impression, news) pair bit for bit.  ``exclude_history``
+        leaves an impression's own history out of its list.  Distinct histories are
+        pooled and searched once (the deduplicated CSR when load_impressions built it).
+        ``user_block`` bounds the workspace by running the users in blocks of that many
+        rows; the results do not depend on it."""
+        idx, scores = self._recommend_distinct(k, exclude_history, user_block)
+        if self.user_idx is not None and idx.shape[0]:
             sel = self.user_idx.long()
             return idx[sel], scores[sel]
         return idx, scores
+
+    def recommend_diverse(self, k: int, lam: float, pool: int = 64, exclude_history: bool = True,
+                          user_block: Optional[int] = None, want_ild: bool = False, want_plain: bool = False):
+        """recommend's lists re-ranked for diversity (ops.rerank_mmr, greedy MMR): the
+        ``pool`` best news per distinct history are retrieved as recommend(pool) does,
+        k of them are picked one at a time, each maximising lam * score - (1 - lam) *
+        (largest cosine to a news already picked), and only then are the lists expanded
+        to the impressions.  Returns (idx int32 [I, k], scores f32 [I, k]) -- the scores
+        are recommend's for the chosen news, in pick order -- and with ``want_ild`` also
+        f32 [I, 2]: the intra-list diversity (mean 1 - cosine over the pairs) of
+        recommend(k)'s list and of the returned one; with ``want_plain`` also recommend(k)'s
+        scores f32 [I, k] (the pool's first k), for comparing the relevance given up.
+        lam = 1 returns recommend(k)."""
+        k, pool = int(k), int(pool)
+        if pool < k:
+            raise ValueError(f"recommend_diverse: pool = {pool} < k = {k}")
+        # lam = 1 keeps recommend's order: its list is the first k of any pool, so only k are retrieved
+        pidx, pscores = self._recommend_distinct(k if float(lam) == 1.0 else pool, exclude_history, user_block)
+        n_u = pidx.shape[0]
+        idx = torch.empty((n_u, k), dtype=torch.int32, device=self.device)
+        scores = torch.empty((n_u, k), dtype=torch.float32, device=self.device)
+        ild = torch.empty((n_u, 2), dtype=torch.float32, device=self.device) if want_ild else None
+        if n_u:
+            ops.rerank_mmr(self.cand_table, self.cand_inv, pidx, pscores, k, lam, want_ild=want_ild,
+                           out=(idx, scores, None, ild, None))
+            if self.user_idx is not None:
+                sel = self.user_idx.long()
+                idx, scores = idx[sel], scores[sel]
+                ild = ild[sel] if want_ild else None
+                pscores = pscores[sel] if want_plain else pscores
+        return (idx, scores) + ((ild,) if want_ild else ()) + ((pscores[:, :k].contiguous(),) if want_plain else ())
 
     def rank_targets(self, tgt_idx, tgt_len, exclude_history: bool = True, user_block: Optional[int] = None):
         """Full-table ranks of given news per impression (ops.rank_targets over the pooled

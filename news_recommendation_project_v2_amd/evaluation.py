@@ -251,3 +251,41 @@ def retrieval_metrics(ranks, target_len, ks: Sequence[int] = (1, 5, 10, 64, 100,
     out["mean_rank"] = float(ri.mean()) if len(ri) else float("nan")
     out["median_rank"] = float(np.median(ri)) if len(ri) else float("nan")
     return out
+
+
+def diversity_metrics(ild, idx=None, categories=None, rel_before=None, rel_after=None) -> dict:
+    """Summary of a diversity re-ranking (data_model_helper.get_top_k_recommendations with
+    ``diversify``; the reference has no counterpart).  Host numpy in float64.
+
+    ``ild`` [I, 2]: per list the intra-list diversity (mean 1 - cosine over the pairs)
+    before and after the re-ranking; ``rel_before`` / ``rel_after`` [I, k]: the scores of
+    the plain top-k lists and of the re-ranked ones (a short list's -inf tail is left
+    out); ``idx`` int [I, k] with ``categories`` int [N] (one label per news row): the
+    re-ranked lists, for the mean number of distinct categories per list (-1 entries
+    are left out).  Returns the means over the lists; a key whose input is missing is
+    absent."""
+    d = np.asarray(ild, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != 2:
+        raise ValueError("ild must be [I, 2] (before, after)")
+    nan = float("nan")
+    out = {"lists": int(d.shape[0]),
+           "ild_before": float(d[:, 0].mean()) if len(d) else nan,
+           "ild_after": float(d[:, 1].mean()) if len(d) else nan}
+    for name, rel in (("relevance_before", rel_before), ("relevance_after", rel_after)):
+        if rel is None:
+            continue
+        r = np.asarray(rel, dtype=np.float64)
+        ok = np.isfinite(r)
+        out[name] = float(r[ok].mean()) if ok.any() else nan
+    if (idx is None) != (categories is None):
+        raise ValueError("idx and categories go together")
+    if idx is not None:
+        ix = np.asarray(idx, dtype=np.int64)
+        cat = np.asarray(categories)
+        if ix.ndim != 2 or ix.shape[0] != d.shape[0]:
+            raise ValueError("idx must be [I, k] with one row per ild row")
+        if ix.size and ix.max() >= len(cat):
+            raise IndexError(f"news row {int(ix.max())} has no category ({len(cat)} were given)")
+        counts = [len(set(cat[row[row >= 0]].tolist())) for row in ix]
+        out["distinct_categories"] = float(np.mean(counts)) if counts else nan
+    return out

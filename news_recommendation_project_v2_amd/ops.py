@@ -422,6 +422,54 @@ def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: t
     return out
 
 
+def rerank_mmr(cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, list_idx: torch.Tensor, list_rel: torch.Tensor,
+               k: int, lam: float, want_pos: bool = False, want_ild: bool = False, want_sim: bool = False, out=None):
+    """Greedy MMR re-ranking of retrieved lists (nr_rerank_mmr, include/newsrec_rerank.h):
+    ``list_idx`` int32 [U, M] rows of ``cand_table`` with relevance ``list_rel`` f32 [U, M]
+    (e.g. topk_users' result, M <= 64; an index outside the table is a pad).  k of the M are
+    picked one at a time, each maximising lam * rel - (1 - lam) * (largest cosine to an
+    entry already picked); ties go to the lower position.  Returns (idx int32 [U, k],
+    rel f32 [U, k]) in pick order, a short tail as (-1, -inf), followed by those asked
+    for of: pos int32 [U, k] (positions in the input list), ild f32 [U, 2] (intra-list
+    diversity of the input's first k valid entries and of the picks), sim f32 [U, M, M]
+    (the cosine matrix, diagonal and pads 0).  ``out`` = (idx, rel, pos, ild, sim) to
+    write into, None for the ones not wanted."""
+    dev = _dev(cand_table, cand_inv_norm, list_idx, list_rel, *(out or ()))
+    ld = _rowmajor(cand_table, "cand_table")
+    n_news, dim = cand_table.shape
+    dt = _dtype(cand_table, "cand_table")
+    if cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < n_news or not cand_inv_norm.is_contiguous():
+        raise _lib.NewsRecHIPError("cand_inv_norm must be contiguous f32 with one entry per candidate-table row")
+    if list_idx.dtype != torch.int32 or list_idx.dim() != 2 or not list_idx.is_contiguous():
+        raise _lib.NewsRecHIPError("rerank_mmr: list_idx must be contiguous int32 [U, M]")
+    if list_rel.dtype != torch.float32 or list_rel.shape != list_idx.shape or not list_rel.is_contiguous():
+        raise _lib.NewsRecHIPError("rerank_mmr: list_rel must be contiguous f32 of list_idx's shape")
+    n_users, m = list_idx.shape
+    k, lam = int(k), float(lam)
+    if not 1 <= m <= _lib.NR_RERANK_MAX or not 1 <= k <= m:
+        raise _lib.NewsRecHIPError(f"rerank_mmr: need 1 <= k <= M <= {_lib.NR_RERANK_MAX}, got k = {k}, M = {m}")
+    if not 0.0 <= lam <= 1.0:  # NaN fails too
+        raise _lib.NewsRecHIPError(f"rerank_mmr: lam = {lam} outside [0, 1]")
+    spec = (("idx", torch.int32, (n_users, k), True), ("rel", torch.float32, (n_users, k), True),
+            ("pos", torch.int32, (n_users, k), want_pos), ("ild", torch.float32, (n_users, 2), want_ild),
+            ("sim", torch.float32, (n_users, m, m), want_sim))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if want else None for _, dtype, shape, want in spec)
+    elif len(out) != len(spec):
+        raise _lib.NewsRecHIPError("rerank_mmr: out must be (idx, rel, pos, ild, sim), None for the ones not wanted")
+    for t, (name, dtype, shape, want) in zip(out, spec):
+        if want and t is None:
+            raise _lib.NewsRecHIPError(f"rerank_mmr: out has no {name}")
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise _lib.NewsRecHIPError(f"rerank_mmr: out {name} must be contiguous {dtype} of shape {shape}")
+    res = tuple(t for t, (_, _, _, want) in zip(out, spec) if want)
+    if n_users == 0:
+        return res
+    _lib.call("nr_rerank_mmr", dt, dim, n_users, n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm), _ptr(list_idx),
+              _ptr(list_rel), m, k, lam, *(_ptr(t) for t in out), _stream(dev))
+    return res
+
+
 def dense_rank(scores: torch.Tensor, cand_off: torch.Tensor, check: bool = True) -> torch.Tensor:
     """Per-impression dense descending ranks (int32), scipy rankdata(-x, 'dense')."""
     dev = _dev(scores, cand_off)

@@ -6,6 +6,7 @@ has no counterpart -- it only scores the candidates an impression lists).
     python scripts/recommend.py --pooler {final,latent} --dtype {f32,bf16} -k K [--keep-history] --synthetic
     python scripts/recommend.py --data-dir data --emb-dir new_embeddings --split MINDsmall_dev -k 10
     python scripts/recommend.py --synthetic --evaluate [--ks 10,64,100]
+    python scripts/recommend.py --synthetic --diversify 0.7 [--pool 64]
 
 Prints one JSON line per run and writes {out-dir}/recommendations.npy: an int32
 [I, K] array of rows of the split's news list (-1 where fewer than K are eligible).
@@ -14,6 +15,10 @@ Prints one JSON line per run and writes {out-dir}/recommendations.npy: an int32
 full-table ranks of each impression's clicked candidates (label 1)
 (data_model_helper.get_full_table_ranks) as hit / recall / nDCG at each K of --ks, MRR
 and the mean and median rank (evaluation.retrieval_metrics).
+--diversify LAMBDA re-ranks for diversity (greedy MMR over the --pool best news, default
+64): recommendations.npy then holds the re-ranked lists, in pick order, and the JSON
+line gains evaluation.diversity_metrics (mean intra-list diversity and mean score of the
+plain and of the re-ranked lists).
 """
 from __future__ import annotations
 
@@ -53,7 +58,12 @@ def main():
     ap.add_argument("--evaluate", action="store_true",
                     help="rank each impression's clicked candidates against the whole news list and report metrics")
     ap.add_argument("--ks", default="1,5,10,64,100,1000", help="the K of hit@K / recall@K / ndcg@K with --evaluate")
+    ap.add_argument("--diversify", type=float, default=None, metavar="LAMBDA",
+                    help="re-rank for diversity: lambda in [0, 1], 1 keeps the plain order")
+    ap.add_argument("--pool", type=int, default=None, metavar="M", help="news retrieved before --diversify picks K (64)")
     args = ap.parse_args()
+    if args.pool is not None and args.diversify is None:
+        ap.error("--pool needs --diversify")
 
     model = FinalAttention(1024, 4096) if args.pooler == "final" else LatentAttentionModel()
     ckpt = args.ckpt or Path("models") / ("final_attn" if args.pooler == "final" else "latent_attn") / "Epoch_5.pt"
@@ -82,7 +92,9 @@ def main():
     rec = dmh.get_top_k_recommendations(out["history_rev_ind_array"][0], out["history_len_list"],
                                         out["news_embeddings"], model, args.k,
                                         exclude_history=not args.keep_history,
-                                        dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)
+                                        dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
+                                        **({} if args.diversify is None else
+                                           {"diversify": args.diversify, "pool": args.pool}))
     ms = (time.perf_counter() - t0) * 1e3
     idx, scores = rec["news_index"], rec["scores"]
     args.out_dir.mkdir(parents=True, exist_ok=True)
@@ -94,6 +106,12 @@ def main():
             "news": int(out["news_embeddings"].shape[0]), "filled": float(have.mean()) if idx.size else 1.0,
             "mean_top1_score": float(scores[:, 0][have[:, 0]].mean()) if have[:, :1].any() else None,
             "ms": round(ms, 1), "out": str(path)}
+    if args.diversify is not None:
+        from news_recommendation_project_v2_amd.evaluation import diversity_metrics
+        line.update(diversify=args.diversify, pool=args.pool or 64)
+        dm = diversity_metrics(rec["ild"], rel_before=rec["plain_scores"], rel_after=scores)
+        dm.pop("lists")
+        line.update(dm)
     if args.evaluate:
         from news_recommendation_project_v2_amd.evaluation import retrieval_metrics
         labels = out["labels"]
