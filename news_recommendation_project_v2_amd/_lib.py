@@ -19,11 +19,11 @@ INCLUDE = Path(__file__).resolve().parent.parent / "include"
 # translation units of libnewsrec_hip.so, in link order (also the hash order)
 HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip", "encoder.hip", "train.hip",
                "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip", "contrastive.hip", "topk.hip",
-               "fullrank.hip", "rerank.hip")
+               "fullrank.hip", "rerank.hip", "explain.hip")
 # the headers they include (every object is rebuilt when one changes), hashed after the sources
 HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CSRC / "nr_score_tile.h",
                INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
-               INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h")
+               INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h")
 
 
 def hip_source_files() -> list:
@@ -167,6 +167,12 @@ RERANK_SIGNATURES = {
     "nr_rerank_mmr": (_i, [_i, _l, _l, _l, _p, _l, _p, _p, _p, _l, _l, _f, _p, _p, _p, _p, _p, _p]),
 }
 
+# per-click attribution of scores (include/newsrec_explain.h), bound by load() like SIGNATURES
+NR_EXPLAIN_TOP_MAX = 8
+EXPLAIN_SIGNATURES = {
+    "nr_explain_scores": (_i, [_i, _i, _l, _p, _l, _l, _p, _l, _p, _l, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p]),
+}
+
 
 class ContrastiveSpec(ctypes.Structure):
     """struct nr_contrastive_spec (include/newsrec_contrastive.h)."""
@@ -224,7 +230,7 @@ def load() -> ctypes.CDLL:
             "(there is no CPU fallback for the MI355X hot path)")
     lib = ctypes.CDLL(os.fspath(LIB_PATH))
     for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES,
-                              **FULLRANK_SIGNATURES, **RERANK_SIGNATURES}.items():
+                              **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -141,7 +141,8 @@ def get_final_second_attention_score(history_rev_index: np.ndarray, history_len_
 def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: np.ndarray,
                               news_embeddings: torch.Tensor, attention_model: torch.nn.Module, k: int,
                               exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
-                              dtype=None, diversify: Optional[float] = None, pool: Optional[int] = None) -> dict:
+                              dtype=None, diversify: Optional[float] = None, pool: Optional[int] = None,
+                              explain: Optional[int] = None) -> dict:
     """The k news of the WHOLE table that the model recommends per impression:
     ``{"news_index": int32 [I, k], "scores": float32 [I, k]}`` on the host, score
     descending, ties by ascending news row, ``(-1, -inf)`` where fewer than k news are
@@ -160,19 +161,39 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     pick order, the scores still the news' own, and the result gains ``"ild"`` float32
     [I, 2], the intra-list diversity of the plain top-k list and of the returned one, and
     ``"plain_scores"`` float32 [I, k], the plain top-k list's scores
-    (evaluation.diversity_metrics summarises them).  ``pool`` without ``diversify`` is refused."""
+    (evaluation.diversity_metrics summarises them).  ``pool`` without ``diversify`` is refused.
+
+    ``explain`` = T in [1, 8] adds the reasons (PoolScoreEngine.recommend_explained,
+    include/newsrec_explain.h): ``"why_news"`` int32 [I, k, T], for each recommendation the T
+    news of the impression's history (rows of the news table) whose clicks contributed
+    most to its score, and ``"why_share"`` float32 [I, k, T], those clicks' additive shares
+    of the score (all of a history's shares add up to the score), value descending;
+    ``(-1, -inf)`` for a missing recommendation and past the history's length
+    (evaluation.explanation_metrics summarises them).  Without ``explain`` the result is as
+    described above."""
     if diversify is None and pool is not None:
         raise ValueError("get_top_k_recommendations: pool needs diversify")
+    if explain is not None and not 1 <= int(explain) <= 8:
+        raise ValueError(f"get_top_k_recommendations: explain = {explain} outside [1, 8]")
     eng = _engine(attention_model, news_embeddings, query_news_embeddings if isinstance(query_news_embeddings,
                                                                                         torch.Tensor) else None,
                   dtype=dtype)
     n = len(history_len_list)
     eng.load_impressions(history_rev_index, history_len_list, np.zeros(0, np.int32), np.zeros(n, np.int32))
+    why = {}
+    if explain is not None:
+        idx, scores, why_news, why_val = eng.recommend_explained(k, top=int(explain), lam=diversify,
+                                                                 pool=64 if pool is None else pool,
+                                                                 exclude_history=exclude_history)
+        why = {"why_news": _host(why_news), "why_share": _host(why_val)}
+        if diversify is None:
+            return {"news_index": _host(idx), "scores": _host(scores), **why}
     if diversify is not None:
         idx, scores, ild, plain = eng.recommend_diverse(k, diversify, pool=64 if pool is None else pool,
                                                         exclude_history=exclude_history, want_ild=True,
                                                         want_plain=True)
-        return {"news_index": _host(idx), "scores": _host(scores), "ild": _host(ild), "plain_scores": _host(plain)}
+        return {"news_index": _host(idx), "scores": _host(scores), "ild": _host(ild), "plain_scores": _host(plain),
+                **why}
     idx, scores = eng.recommend(k, exclude_history=exclude_history)
     return {"news_index": _host(idx), "scores": _host(scores)}
 

@@ -262,6 +262,19 @@ class PoolScoreEngine:
         recommend(k)'s list and of the returned one; with ``want_plain`` also recommend(k)'s
         scores f32 [I, k] (the pool's first k), for comparing the relevance given up.
         lam = 1 returns recommend(k)."""
+        idx, scores, ild, pscores = self._diverse_distinct(k, lam, pool, exclude_history, user_block, want_ild)
+        k = int(k)
+        if idx.shape[0] and self.user_idx is not None:
+            sel = self.user_idx.long()
+            idx, scores = idx[sel], scores[sel]
+            ild = ild[sel] if want_ild else None
+            pscores = pscores[sel] if want_plain else pscores
+        return (idx, scores) + ((ild,) if want_ild else ()) + ((pscores[:, :k].contiguous(),) if want_plain else ())
+
+    def _diverse_distinct(self, k: int, lam: float, pool: int, exclude_history: bool, user_block: Optional[int],
+                          want_ild: bool = False):
+        """recommend_diverse's lists per DISTINCT history: (idx [n_u, k], scores [n_u, k], ild
+        [n_u, 2] or None, the retrieved pool's scores [n_u, pool])."""
         k, pool = int(k), int(pool)
         if pool < k:
             raise ValueError(f"recommend_diverse: pool = {pool} < k = {k}")
@@ -274,12 +287,68 @@ class PoolScoreEngine:
         if n_u:
             ops.rerank_mmr(self.cand_table, self.cand_inv, pidx, pscores, k, lam, want_ild=want_ild,
                            out=(idx, scores, None, ild, None))
-            if self.user_idx is not None:
-                sel = self.user_idx.long()
-                idx, scores = idx[sel], scores[sel]
-                ild = ild[sel] if want_ild else None
-                pscores = pscores[sel] if want_plain else pscores
-        return (idx, scores) + ((ild,) if want_ild else ()) + ((pscores[:, :k].contiguous(),) if want_plain else ())
+        return idx, scores, ild, pscores
+
+    def explain(self, idx: torch.Tensor, top: int = 3, want_sum: bool = False, want_matrix: bool = False):
+        """Why these news: the exact per-click attribution of the scores of one list per
+        impression (ops.explain_scores over the loaded history CSR).  ``idx`` int32 [I, K]
+        rows of the news table (K <= 64; an entry outside the table is a pad): recommend's
+        or recommend_diverse's lists, or an impression's own candidates padded to a
+        rectangle.  Returns (top_pos int32 [I, K, top], top_val f32 [I, K, top]): the
+        positions within the impression's history of the ``top`` clicks that contributed
+        most to each listed news' score and their contributions (-1, -inf past the
+        history's length or for a pad); with ``want_sum`` also f32 [I, K], every click's
+        contributions added up (pool_score's score of the pair); with ``want_matrix`` also
+        f32 [len(hist_idx), K], all of them.  The pooler table and the inverse norms are
+        computed when a step has not left them."""
+        idx = torch.as_tensor(idx).to(self.device)
+        if idx.dim() != 2 or idx.shape[0] != self.n_imp:
+            raise ValueError("Number of rows should be consistent")
+        self._tables()
+        return ops.explain_scores(self.pooler, self.hist_table, self.cand_table, self.cand_inv, self.hist_idx,
+                                  self.hist_off, idx.to(torch.int32).contiguous(), top=top, want_sum=want_sum,
+                                  want_matrix=want_matrix)
+
+    def _tables(self) -> None:
+        if self.hist_table is None:
+            self.hist_table = self.transform()
+        if self.cand_inv is None:
+            self.inv_norms()
+
+    def recommend_explained(self, k: int, top: int = 3, lam: Optional[float] = None, pool: int = 64,
+                            exclude_history: bool = True, user_block: Optional[int] = None):
+        """recommend's lists (with ``lam``: recommend_diverse's, re-ranked from the ``pool``
+        best) together with their reasons: (idx int32 [I, k], scores f32 [I, k], why_news
+        int32 [I, k, top], why_val f32 [I, k, top]).  why_news[i, j] are the ``top`` news of
+        impression i's history (rows of the news table) whose clicks contributed most to
+        the score of idx[i, j], why_val their contributions (ops.explain_scores: the
+        contributions of all clicks add up to the score), value descending; (-1, -inf) for a
+        pad and past the history's length.  The lists are retrieved and explained once per
+        distinct history (the deduplicated CSR when load_impressions built it) and only
+        then expanded to the impressions; the result does not depend on that."""
+        if lam is None:
+            idx, scores = self._recommend_distinct(int(k), exclude_history, user_block)
+        else:
+            idx, scores, _, _ = self._diverse_distinct(k, lam, pool, exclude_history, user_block)
+        if self.user_idx is not None:
+            hidx, hoff = self.uhist_idx, self.uhist_off
+        else:
+            hidx, hoff = self.hist_idx, self.hist_off
+        n_u, top = idx.shape[0], int(top)
+        if n_u == 0:
+            return (idx, scores, torch.empty((0, int(k), top), dtype=torch.int32, device=self.device),
+                    torch.empty((0, int(k), top), dtype=torch.float32, device=self.device))
+        pos, val = ops.explain_scores(self.pooler, self.hist_table, self.cand_table, self.cand_inv, hidx, hoff, idx,
+                                      top=top)
+        if hidx.numel():
+            row = (hoff[:-1].view(-1, 1, 1) + pos.clamp(min=0)).clamp(max=hidx.numel() - 1)
+            why = torch.where(pos >= 0, hidx[row], torch.full_like(pos, -1))
+        else:
+            why = torch.full_like(pos, -1)
+        if self.user_idx is not None:
+            sel = self.user_idx.long()
+            idx, scores, why, val = idx[sel], scores[sel], why[sel], val[sel]
+        return idx, scores, why, val
 
     def rank_targets(self, tgt_idx, tgt_len, exclude_history: bool = True, user_block: Optional[int] = None):
         """Full-table ranks of given news per impression (ops.rank_targets over the pooled

@@ -289,3 +289,34 @@ def diversity_metrics(ild, idx=None, categories=None, rel_before=None, rel_after
         counts = [len(set(cat[row[row >= 0]].tolist())) for row in ix]
         out["distinct_categories"] = float(np.mean(counts)) if counts else nan
     return out
+
+
+def explanation_metrics(why_share, scores) -> dict:
+    """Summary of per-click explanations (data_model_helper.get_top_k_recommendations with
+    ``explain``; the reference has no counterpart).  Host numpy in float64.
+
+    ``why_share`` [I, k, T]: per recommendation its T largest per-click contributions, value
+    descending, -inf where the history has fewer than T clicks; ``scores`` [I, k]: the
+    recommendations' scores (the sum of ALL of a history's contributions), -inf for a pad.
+    A pad and a recommendation without any click are skipped.  Returns
+    ``recommendations`` (the number summarised), ``negative_top`` (the share of them
+    whose largest contribution is negative: no click speaks for the news on its own), and
+    over those with a positive score ``top1_share`` / ``topT_share``: the mean fraction
+    of the score carried by the largest and by the T largest contributions (a fraction can
+    exceed 1 when other clicks count against the news)."""
+    w = np.asarray(why_share, dtype=np.float64)
+    s = np.asarray(scores, dtype=np.float64)
+    if w.ndim != 3 or s.shape != w.shape[:2]:
+        raise ValueError("why_share must be [I, k, T] and scores [I, k]")
+    nan = float("nan")
+    if w.shape[2] == 0:
+        raise ValueError("why_share holds no contributions (T = 0)")
+    ok = np.isfinite(s) & np.isfinite(w[:, :, 0])
+    out = {"recommendations": int(ok.sum()),
+           "negative_top": float((w[:, :, 0][ok] < 0).mean()) if ok.any() else nan}
+    pos = ok & (s > 0)
+    top1 = w[:, :, 0][pos] / s[pos]
+    topt = np.where(np.isfinite(w), w, 0.0).sum(axis=2)[pos] / s[pos]
+    out["top1_share"] = float(top1.mean()) if pos.any() else nan
+    out["topT_share"] = float(topt.mean()) if pos.any() else nan
+    return out

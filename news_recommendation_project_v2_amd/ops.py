@@ -470,6 +470,73 @@ def rerank_mmr(cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, list_idx: 
     return res
 
 
+def explain_scores(pooler: str, hist_table: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor,
+                   hist_idx: torch.Tensor, hist_off: torch.Tensor, list_idx: torch.Tensor, top: int = 3,
+                   want_sum: bool = False, want_matrix: bool = False, out=None):
+    """Exact per-click attribution of scores (nr_explain_scores, include/newsrec_explain.h):
+    for user u with history hist_idx[hist_off[u]:hist_off[u + 1]] (rows of ``hist_table``,
+    pool_score's layout) and the listed rows ``list_idx`` int32 [U, K] of ``cand_table``
+    (K <= 64; an index outside the table is a pad), the additive contribution of every
+    click to every listed news' score.  Returns (top_pos int32 [U, K, top], top_val f32
+    [U, K, top]) -- the history positions of the ``top`` <= 8 largest contributions, value
+    descending, ties by ascending position, a short tail as (-1, -inf) -- followed by
+    those asked for of: sums f32 [U, K] (the contributions' sums: pool_score's scores),
+    matrix f32 [len(hist_idx), K] (every contribution, row = CSR row of the click).
+    ``top`` = 0 leaves the top lists out.  ``out`` = (top_pos, top_val, sums, matrix) to
+    write into, None for the ones not wanted."""
+    dev = _dev(hist_table, cand_table, cand_inv_norm, hist_idx, hist_off, list_idx, *(out or ()))
+    if pooler not in POOLERS:
+        raise _lib.NewsRecHIPError(f"explain_scores: unknown pooler {pooler!r}")
+    _check_csr(hist_idx, hist_off, "hist")
+    hld, ld = _rowmajor(hist_table, "hist_table"), _rowmajor(cand_table, "cand_table")
+    n_news, dim = cand_table.shape
+    dt = _dtype(cand_table, "cand_table")
+    if hist_table.dtype != cand_table.dtype:
+        raise _lib.NewsRecHIPError("hist_table and cand_table must share a dtype")
+    if hist_table.shape[1] != (2 * dim if pooler == "final" else dim):
+        raise _lib.NewsRecHIPError(f"explain_scores: hist_table rows must be {'2 x ' if pooler == 'final' else ''}"
+                                   f"{dim} wide for the {pooler} pooler")
+    if cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < n_news or not cand_inv_norm.is_contiguous():
+        raise _lib.NewsRecHIPError("cand_inv_norm must be contiguous f32 with one entry per candidate-table row")
+    if list_idx.dtype != torch.int32 or list_idx.dim() != 2 or not list_idx.is_contiguous():
+        raise _lib.NewsRecHIPError("explain_scores: list_idx must be contiguous int32 [U, K]")
+    n_users, k = list_idx.shape
+    if hist_off.numel() != n_users + 1:
+        raise _lib.NewsRecHIPError("explain_scores: hist_off must have U + 1 entries")
+    top = int(top)
+    if not 1 <= k <= _lib.NR_TOPK_MAX:
+        raise _lib.NewsRecHIPError(f"explain_scores: need 1 <= K <= {_lib.NR_TOPK_MAX}, got K = {k}")
+    if not 0 <= top <= _lib.NR_EXPLAIN_TOP_MAX:
+        raise _lib.NewsRecHIPError(f"explain_scores: top = {top} outside [0, {_lib.NR_EXPLAIN_TOP_MAX}]")
+    if not (top or want_sum or want_matrix):
+        raise _lib.NewsRecHIPError("explain_scores: nothing requested (top = 0, no sums, no matrix)")
+    n_hist = hist_idx.numel()
+    spec = (("top_pos", torch.int32, (n_users, k, top), top > 0), ("top_val", torch.float32, (n_users, k, top), top > 0),
+            ("sums", torch.float32, (n_users, k), want_sum), ("matrix", torch.float32, (n_hist, k), want_matrix))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if want else None for _, dtype, shape, want in spec)
+    elif len(out) != len(spec):
+        raise _lib.NewsRecHIPError("explain_scores: out must be (top_pos, top_val, sums, matrix), None for the ones "
+                                   "not wanted")
+    for t, (name, dtype, shape, want) in zip(out, spec):
+        if want and t is None:
+            raise _lib.NewsRecHIPError(f"explain_scores: out has no {name}")
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise _lib.NewsRecHIPError(f"explain_scores: out {name} must be contiguous {dtype} of shape {shape}")
+    res = tuple(t for t, (_, _, _, want) in zip(out, spec) if want)
+    if n_users == 0:
+        return res
+    if want_matrix and int(hist_off[-1]) != n_hist:  # the matrix has one row per CSR row (one small sync)
+        raise _lib.NewsRecHIPError(f"explain_scores: hist_off ends at {int(hist_off[-1])}, hist_idx has {n_hist} rows")
+    hidx = hist_idx if n_hist else torch.zeros(1, dtype=torch.int32, device=dev)
+    # zero-element tensors report data_ptr() == 0: give the kernel a real (unwritten) slot
+    bufs = [t if t is None or t.numel() else torch.empty(1, dtype=t.dtype, device=dev) for t in out]
+    _lib.call("nr_explain_scores", POOLERS[pooler], dt, dim, _ptr(hist_table), hld, n_news, _ptr(cand_table), ld,
+              _ptr(cand_inv_norm), n_users, _ptr(hidx), _ptr(hist_off), _ptr(list_idx), k, max(top, 1),
+              *(_ptr(t) for t in bufs), _stream(dev))
+    return res
+
+
 def dense_rank(scores: torch.Tensor, cand_off: torch.Tensor, check: bool = True) -> torch.Tensor:
     """Per-impression dense descending ranks (int32), scipy rankdata(-x, 'dense')."""
     dev = _dev(scores, cand_off)

@@ -7,6 +7,7 @@ has no counterpart -- it only scores the candidates an impression lists).
     python scripts/recommend.py --data-dir data --emb-dir new_embeddings --split MINDsmall_dev -k 10
     python scripts/recommend.py --synthetic --evaluate [--ks 10,64,100]
     python scripts/recommend.py --synthetic --diversify 0.7 [--pool 64]
+    python scripts/recommend.py --synthetic --explain 3
 
 Prints one JSON line per run and writes {out-dir}/recommendations.npy: an int32
 [I, K] array of rows of the split's news list (-1 where fewer than K are eligible).
@@ -19,6 +20,12 @@ and the mean and median rank (evaluation.retrieval_metrics).
 64): recommendations.npy then holds the re-ranked lists, in pick order, and the JSON
 line gains evaluation.diversity_metrics (mean intra-list diversity and mean score of the
 plain and of the re-ranked lists).
+--explain T adds the reasons: {out-dir}/recommendations_why.npy, an int32 [I, K, T] array
+with, beside each recommendation, the T news of the impression's history (rows of the
+news list, -1 where there are fewer) whose clicks contributed most to its score, and
+{out-dir}/recommendations_why_share.npy with those contributions; the JSON line gains
+evaluation.explanation_metrics (the mean share of a score carried by its largest and by
+its T largest contributions, and how often the largest one is negative).
 """
 from __future__ import annotations
 
@@ -61,6 +68,8 @@ def main():
     ap.add_argument("--diversify", type=float, default=None, metavar="LAMBDA",
                     help="re-rank for diversity: lambda in [0, 1], 1 keeps the plain order")
     ap.add_argument("--pool", type=int, default=None, metavar="M", help="news retrieved before --diversify picks K (64)")
+    ap.add_argument("--explain", type=int, default=None, metavar="T",
+                    help="also write the T history news (1..8) that contributed most to each recommendation")
     args = ap.parse_args()
     if args.pool is not None and args.diversify is None:
         ap.error("--pool needs --diversify")
@@ -94,7 +103,8 @@ def main():
                                         exclude_history=not args.keep_history,
                                         dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
                                         **({} if args.diversify is None else
-                                           {"diversify": args.diversify, "pool": args.pool}))
+                                           {"diversify": args.diversify, "pool": args.pool}),
+                                        **({} if args.explain is None else {"explain": args.explain}))
     ms = (time.perf_counter() - t0) * 1e3
     idx, scores = rec["news_index"], rec["scores"]
     args.out_dir.mkdir(parents=True, exist_ok=True)
@@ -112,6 +122,13 @@ def main():
         dm = diversity_metrics(rec["ild"], rel_before=rec["plain_scores"], rel_after=scores)
         dm.pop("lists")
         line.update(dm)
+    if args.explain is not None:
+        from news_recommendation_project_v2_amd.evaluation import explanation_metrics
+        why_path = args.out_dir / "recommendations_why.npy"
+        np.save(why_path, rec["why_news"])
+        np.save(args.out_dir / "recommendations_why_share.npy", rec["why_share"])
+        em = explanation_metrics(rec["why_share"], scores)
+        line.update(explain=args.explain, why_out=str(why_path), explained=em.pop("recommendations"), **em)
     if args.evaluate:
         from news_recommendation_project_v2_amd.evaluation import retrieval_metrics
         labels = out["labels"]

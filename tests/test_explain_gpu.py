@@ -1,0 +1,507 @@
+"""Per-click attribution of scores (csrc/explain.hip, include/newsrec_explain.h) on the GPU
+against the float64 reference of tests/explain_ref.py.
+
+Bounds.  SIM_EPS = 1e-4 per unit of absolute mass is the project's f32 cosine contract
+(the worst-case f32 accumulation bound of a 1024-term dot product, 1024 * 2^-24 ~ 6.1e-5,
+plus the scalings; tests/test_topk_gpu.py): |contrib_out - a64| <= SIM_EPS * max(1, mass),
+mass = sum_d |term_d| from the reference.  On these inputs mass < 0.7, so the bound is 1e-4.
+In bf16 mode the reference is the float64 evaluation of the SAME stored operands (the bf16
+tables upcast, cand_inv as the evaluation path computes it), so the same bound holds.
+
+Exact lists.  EXPL_ERR_MEASURED is the largest |contrib_out - a64| over this file's inputs,
+the three poolers and both dtypes, measured on an MI355X (printed by
+test_gpu_explain_error_measured); EPS_EXACT = 4 x that (two contributions per comparison
+and a factor 2 of headroom) is the reference gap above which a top-T list must equal the
+reference's.  It must stay below EPS_EXACT_CAP = 2e-5: a larger error means the
+accumulation is wrong.
+
+SUM_DIFF_MEASURED is the largest |sum_out - ops.score_users| over the pairs of
+test_gpu_explain_sum_is_the_score (which prints it), measured on an MI355X: 1.1e-7 against
+the bound of 1e-4.
+"""
+from __future__ import annotations
+
+import json
+
+import numpy as np
+import pytest
+import torch
+
+import explain_ref
+from conftest import REPO
+from news_recommendation_project_v2_amd import weights as W
+
+D = 1024
+N_NEWS = 3000
+SIM_EPS = 1e-4
+EXPL_ERR_MEASURED = 9.3e-8
+SUM_DIFF_MEASURED = 1.1e-7
+EPS_EXACT = 4 * EXPL_ERR_MEASURED
+EPS_EXACT_CAP = 2e-5
+MAX_LEFT_OUT = 0.15
+DTYPES = [torch.float32, torch.bfloat16]
+IDS = ["f32", "bf16"]
+POOLERS = ["final", "latent", "mean"]
+H_SET = [0, 1, 2, 15, 16, 17, 31, 32, 33, 64, 65, 200]
+K_SET = [1, 10, 16, 17, 33, 64]
+INVALID, UNSUPPORTED = -1, -3
+NINF = -np.inf
+
+
+def _bits(x):
+    return np.ascontiguousarray(x).view(np.int32)
+
+
+# ------------------------------------------------------------------ inputs, shared and left unchanged
+_T = {}
+
+
+def _tables(dtype, dev):
+    """N(0, 1) history and candidate tables of 3,000 rows, the FINAL p half exp(N(0, 1));
+    per dtype the device tensors and the float64 upcast of what is stored."""
+    from news_recommendation_project_v2_amd import ops
+    if "host" not in _T:
+        rng = np.random.default_rng(41)
+        _T["host"] = tuple(rng.standard_normal((N_NEWS, D)).astype(np.float32) for _ in range(3))
+    if dtype not in _T:
+        x, w, c = _T["host"]
+        cand = torch.from_numpy(c).to(dev).to(dtype).contiguous()
+        plain = torch.from_numpy(x).to(dev).to(dtype).contiguous()
+        final = torch.from_numpy(np.concatenate([x, np.exp(w)], axis=1)).to(dev).to(dtype).contiguous()
+        inv = ops.row_inv_norm(cand, 1e-8)
+        torch.cuda.synchronize()
+        _T[dtype] = {"cand": cand, "inv": inv, "final": final, "latent": plain, "mean": plain,
+                     "cand64": cand.double().cpu().numpy(), "inv64": inv.double().cpu().numpy(),
+                     "final64": final.double().cpu().numpy(), "latent64": plain.double().cpu().numpy()}
+        _T[dtype]["mean64"] = _T[dtype]["latent64"]
+    return _T[dtype]
+
+
+def _inputs(n_users):
+    """Histories with lengths from H_SET (each of them at least once when there are enough
+    users), rows drawn with replacement; lists of 64 entries, about one in ten a pad."""
+    key = ("in", n_users)
+    if key not in _T:
+        rng = np.random.default_rng(4200 + n_users)
+        lens = rng.choice(H_SET, n_users)
+        if n_users >= len(H_SET):
+            lens[rng.permutation(n_users)[:len(H_SET)]] = H_SET
+        elif n_users == 3:
+            lens[:] = [0, 200, 33]
+        else:
+            lens[:] = 65
+        hist_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        hist_idx = rng.integers(0, N_NEWS, int(hist_off[-1])).astype(np.int32)
+        lst = rng.integers(0, N_NEWS, (n_users, 64)).astype(np.int32)
+        pad = rng.random(lst.shape) < 0.1
+        lst[pad] = rng.choice([-1, N_NEWS, N_NEWS + 7, -5, 2 ** 31 - 1], int(pad.sum()))
+        _T[key] = (hist_idx, hist_off, lst)
+    return _T[key]
+
+
+def _ref(pooler, dtype, dev, n_users):
+    key = ("ref", pooler, dtype, n_users)
+    if key not in _T:
+        t = _tables(dtype, dev)
+        hist_idx, hist_off, lst = _inputs(n_users)
+        _T[key] = explain_ref.explain(pooler, t[pooler + "64"], t["cand64"], t["inv64"], hist_idx, hist_off, lst, top=8)
+    return _T[key]
+
+
+def _run(pooler, dtype, dev, hist_idx, hist_off, lst, top=3, want_sum=True, want_matrix=True, prefill=True):
+    """ops.explain_scores as numpy: dict of pos, val, sums, matrix (those asked for).  The
+    outputs start as a pattern, so anything the kernel leaves unwritten shows."""
+    from news_recommendation_project_v2_amd import ops
+    t = _tables(dtype, dev)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    n_users, k = lst.shape
+    out = None
+    if prefill:
+        out = (torch.full((n_users, k, top), 77, dtype=torch.int32, device=dev) if top else None,
+               torch.full((n_users, k, top), np.nan, dtype=torch.float32, device=dev) if top else None,
+               torch.full((n_users, k), np.nan, dtype=torch.float32, device=dev) if want_sum else None,
+               torch.full((len(hist_idx), k), np.nan, dtype=torch.float32, device=dev) if want_matrix else None)
+    res = ops.explain_scores(pooler, t[pooler], t["cand"], t["inv"], up(hist_idx), up(hist_off), up(lst), top=top,
+                             want_sum=want_sum, want_matrix=want_matrix, out=out)
+    torch.cuda.synchronize()
+    names = (["pos", "val"] if top else []) + (["sums"] if want_sum else []) + (["matrix"] if want_matrix else [])
+    return {n: r.cpu().numpy() for n, r in zip(names, res)}
+
+
+def _values_case(pooler, dtype, dev, n_users, k):
+    """One run checked against the reference; returns (largest error, largest mass)."""
+    hist_idx, hist_off, lst = _inputs(n_users)
+    ref = _ref(pooler, dtype, dev, n_users)
+    got = _run(pooler, dtype, dev, hist_idx, hist_off, lst[:, :k], top=3)
+    a64, mass, valid = ref["a"][:, :k], ref["mass"][:, :k], ref["valid"][:, :k]
+    lens = np.diff(hist_off)
+    m = got["matrix"]
+    assert not np.isnan(m).any(), "a contribution was left unwritten"
+    err = np.abs(m.astype(np.float64) - a64)
+    assert (err <= SIM_EPS * np.maximum(1.0, mass)).all(), (pooler, k, float(err.max()))
+    col_valid = np.repeat(valid, lens, axis=0)
+    assert not m[~col_valid].any(), "a pad's column must be 0"
+    empty = np.broadcast_to((lens == 0)[:, None], valid.shape)
+    dead = ~valid | empty
+    assert (got["pos"][dead] == -1).all() and np.isneginf(got["val"][dead]).all()
+    assert not np.isnan(got["sums"]).any() and not got["sums"][dead].any()
+    assert (got["pos"][~dead][:, 0] >= 0).all()
+    assert (np.abs(got["sums"].astype(np.float64) - ref["sums"][:, :k]) <= SIM_EPS).all()
+    return (float(err.max()) if err.size else 0.0), (float(mass.max()) if mass.size else 0.0)
+
+
+# ------------------------------------------------------------------ 1. values
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("pooler", POOLERS)
+@pytest.mark.parametrize("n_users", [1, 3, 301])
+def test_gpu_explain_values(gpu_device, n_users, pooler, dtype):
+    worst = [_values_case(pooler, dtype, gpu_device, n_users, k) for k in K_SET]
+    print(f"max |contrib_out - a64| = {max(w[0] for w in worst):.3e}, max mass = {max(w[1] for w in worst):.3f}")
+    assert max(w[1] for w in worst) < 1.0
+
+
+@pytest.mark.gpu
+def test_gpu_explain_error_measured(gpu_device):
+    """Prints EXPL_ERR_MEASURED: the largest |contrib_out - a64| over this file's inputs."""
+    assert EPS_EXACT <= EPS_EXACT_CAP
+    worst = max(_values_case(p, dt, gpu_device, 301, 64)[0] for p in POOLERS for dt in DTYPES)
+    print(f"EXPL_ERR_MEASURED: max |contrib_out - a64| = {worst:.3e}")
+    assert worst <= EPS_EXACT / 2, f"|contrib_out - float64| = {worst:.3e}: EPS_EXACT no longer covers two contributions"
+
+
+# ------------------------------------------------------------------ 2. the sum is the score
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("pooler", POOLERS)
+def test_gpu_explain_sum_is_the_score(gpu_device, pooler, dtype):
+    """sum_out against the evaluation path's own score of the same pairs (pool_users +
+    score_users, from the same stored operands in both dtypes)."""
+    from news_recommendation_project_v2_amd import ops
+    dev = gpu_device
+    t = _tables(dtype, dev)
+    hist_idx, hist_off, lst = _inputs(301)
+    lens = np.diff(hist_off)
+    worst = 0.0
+    for k in (10, 64):
+        got = _run(pooler, dtype, dev, hist_idx, hist_off, lst[:, :k], top=0, want_matrix=False)
+        live = explain_ref.valid_entries(lst[:, :k], N_NEWS) & (lens > 0)[:, None]
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        users = ops.pool_users(pooler, t[pooler], up(hist_idx), up(hist_off))
+        cand_off = np.concatenate([[0], np.cumsum(live.sum(axis=1))]).astype(np.int64)
+        scores = ops.score_users(users, torch.arange(301, dtype=torch.int32, device=dev), t["cand"], t["inv"],
+                                 up(lst[:, :k][live]), up(cand_off), int(cand_off[-1]))
+        torch.cuda.synchronize()
+        diff = np.abs(got["sums"][live].astype(np.float64) - scores.cpu().numpy().astype(np.float64))
+        worst = max(worst, float(diff.max()))
+        assert (diff <= SIM_EPS).all(), (k, float(diff.max()))
+    print(f"SUM_DIFF_MEASURED: max |sum_out - score_users| = {worst:.3e}")
+
+
+# ------------------------------------------------------------------ 3. top-T
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("pooler", POOLERS)
+@pytest.mark.parametrize("top", [1, 3, 8])
+def test_gpu_explain_top_lists(gpu_device, top, pooler, dtype):
+    """Every returned list, for every (user, entry): a valid selection of the stored
+    contributions under the strict order, within 2 tol of the reference's, and equal to the
+    reference's list wherever the reference's gaps exceed EPS_EXACT."""
+    assert EPS_EXACT <= EPS_EXACT_CAP
+    n_users, k = 301, 64
+    hist_idx, hist_off, lst = _inputs(n_users)
+    ref = _ref(pooler, dtype, gpu_device, n_users)
+    got = _run(pooler, dtype, gpu_device, hist_idx, hist_off, lst, top=top)
+    cols = np.arange(k)
+    pairs = kept = 0
+    for u in range(n_users):
+        h0, h1 = int(hist_off[u]), int(hist_off[u + 1])
+        h, valid = h1 - h0, ref["valid"][u]
+        if h == 0:
+            continue
+        n = min(top, h)
+        pos, val = got["pos"][u][valid], got["val"][u][valid]           # [Kv, top]
+        mat, a64 = got["matrix"][h0:h1][:, valid], ref["a"][h0:h1][:, valid]  # [H, Kv]
+        kv = cols[:pos.shape[0]]
+        assert (pos[:, :n] >= 0).all() and (pos[:, :n] < h).all()
+        assert (pos[:, n:] == -1).all() and np.isneginf(val[:, n:]).all()
+        assert (np.diff(np.sort(pos[:, :n], axis=1), axis=1) > 0).all(), "a position is listed twice"
+        assert np.array_equal(_bits(val[:, :n]), _bits(mat[pos[:, :n], kv[:, None]])), "top_val is not contrib_out"
+        step = np.diff(val[:, :n], axis=1)
+        assert (step <= 0).all() and (np.diff(pos[:, :n], axis=1)[step == 0] > 0).all(), "order"
+        if h > n:
+            chosen = np.zeros(mat.shape, bool)
+            chosen[pos[:, :n], kv[:, None]] = True
+            last_v, last_p = val[:, n - 1], pos[:, n - 1]
+            rest = np.where(chosen, NINF, mat)
+            assert (rest <= last_v).all(), "a left-out contribution is larger than the last one kept"
+            later = np.arange(h)[:, None] > last_p
+            assert (later | (rest < last_v)).all(), "an equal left-out contribution at a lower position"
+            rest64 = np.where(chosen, NINF, a64).max(axis=0)
+            assert (rest64 <= a64[last_p, kv] + 2 * SIM_EPS).all()
+        keep = (ref["gaps"][u][valid][:, :top] > EPS_EXACT).all(axis=1)
+        assert np.array_equal(pos[keep], ref["top_pos"][u][valid][:, :top][keep]), (u, "differs from the reference")
+        pairs += len(keep)
+        kept += int(keep.sum())
+    out = 1.0 - kept / pairs
+    print(f"left out by the gap rule (gap <= {EPS_EXACT:.1e}): {out:.2%} of {pairs} (user, entry) pairs")
+    assert out <= MAX_LEFT_OUT
+
+
+# ------------------------------------------------------------------ 4. ties, position independence
+def _same(a, b, names=("pos", "val", "sums", "matrix")):
+    return all(np.array_equal(_bits(a[n]), _bits(b[n])) for n in names if n in a and n in b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("pooler", POOLERS)
+def test_gpu_explain_ties_and_position_independence(gpu_device, pooler, dtype):
+    dev = gpu_device
+    rng = np.random.default_rng(43)
+    # one news two and three times in a history: within a tile quadrant, across quadrants, across tiles
+    hists = [np.array([7, 3, 7, 9, 3, 7, 11]), rng.integers(100, N_NEWS, 70), rng.integers(100, N_NEWS, 140)]
+    twice = [[(1, 4)], [(2, 40)], [(5, 70), (6, 139)]]
+    thrice = [[(0, 2, 5)], [(3, 35, 69)], [(1, 66, 130)]]
+    for hst, tw, th in zip(hists[1:], twice[1:], thrice[1:]):
+        for grp, row in zip(tw + th, (5, 6, 8, 9)):
+            hst[list(grp)] = row
+    hist_idx = np.concatenate(hists).astype(np.int32)
+    hist_off = np.concatenate([[0], np.cumsum([len(h) for h in hists])]).astype(np.int64)
+    lst = rng.integers(0, N_NEWS, (3, 17)).astype(np.int32)
+    lst[1, 4] = -1
+    base = _run(pooler, dtype, dev, hist_idx, hist_off, lst, top=8)
+    for u in range(3):
+        mat = base["matrix"][hist_off[u]:hist_off[u + 1]]
+        for grp in twice[u] + thrice[u]:
+            for b in grp[1:]:
+                assert np.array_equal(_bits(mat[grp[0]]), _bits(mat[b])), "occurrences of one news differ"
+        if u == 0:  # every position is listed: the occurrences follow one another in ascending position
+            for j in range(17):
+                where = {int(p): i for i, p in enumerate(base["pos"][u, j, :7])}
+                assert sorted(where) == list(range(7))
+                assert where[1] + 1 == where[4] and where[0] + 1 == where[2] and where[2] + 1 == where[5]
+    # (the top-8 of the long histories: wherever two occurrences are both listed, in ascending position)
+    for u in (1, 2):
+        for j in range(17):
+            p = base["pos"][u, j].tolist()
+            for grp in twice[u] + thrice[u]:
+                at = [p.index(g) for g in grp if g in p]
+                assert at == sorted(at) and (len(at) < 2 or at[-1] - at[0] == len(at) - 1)
+    # two runs: the same bits; with other outputs requested: the same bits
+    assert _same(base, _run(pooler, dtype, dev, hist_idx, hist_off, lst, top=8))
+    assert _same(base, _run(pooler, dtype, dev, hist_idx, hist_off, lst, top=8, want_sum=False, want_matrix=False))
+    assert _same(base, _run(pooler, dtype, dev, hist_idx, hist_off, lst, top=0, want_sum=True, want_matrix=False))
+    assert _same(base, _run(pooler, dtype, dev, hist_idx, hist_off, lst, top=0, want_sum=False, want_matrix=True))
+    t3 = _run(pooler, dtype, dev, hist_idx, hist_off, lst, top=3, want_sum=False, want_matrix=False, prefill=False)
+    assert np.array_equal(t3["pos"], base["pos"][:, :, :3]) and np.array_equal(_bits(t3["val"]), _bits(base["val"][:, :, :3]))
+    # permuted list columns, and fewer of them: the outputs' bits move with the columns
+    perm = rng.permutation(17)
+    moved = _run(pooler, dtype, dev, hist_idx, hist_off, lst[:, perm], top=8)
+    assert _same({n: v[:, perm] for n, v in base.items()}, moved)
+    fewer = _run(pooler, dtype, dev, hist_idx, hist_off, lst[:, 3:8], top=8)
+    assert _same({n: v[:, 3:8] for n, v in base.items()}, fewer)
+    # one user alone and among 4,099
+    n_many = 4099
+    lens = rng.integers(0, 34, n_many)
+    lens[2500] = len(hists[2])
+    off_many = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    idx_many = rng.integers(0, N_NEWS, int(off_many[-1])).astype(np.int32)
+    idx_many[off_many[2500]:off_many[2501]] = hists[2]
+    lst_many = rng.integers(0, N_NEWS, (n_many, 17)).astype(np.int32)
+    lst_many[2500] = lst[2]
+    many = _run(pooler, dtype, dev, idx_many, off_many, lst_many, top=8)
+    alone = _run(pooler, dtype, dev, hists[2].astype(np.int32), np.array([0, len(hists[2])]), lst[2:3], top=8)
+    assert np.array_equal(many["pos"][2500], alone["pos"][0]) and np.array_equal(_bits(many["val"][2500]), _bits(alone["val"][0]))
+    assert np.array_equal(_bits(many["sums"][2500]), _bits(alone["sums"][0]))
+    assert np.array_equal(_bits(many["matrix"][off_many[2500]:off_many[2501]]), _bits(alone["matrix"]))
+    assert _same({n: v[2:3] for n, v in base.items() if n != "matrix"}, alone)
+    assert not np.isnan(many["matrix"]).any() and not np.isnan(many["sums"]).any()
+    assert not (np.delete(many["pos"], 2500, axis=0) == 77).any()  # (the other histories are shorter than 77)
+
+
+# ------------------------------------------------------------------ 5. engine and API
+def _model(pooler, dev):
+    from news_recommendation_project_v2_amd.latent_attention import LatentAttentionModel
+    from news_recommendation_project_v2_amd.modeling_utils import FinalAttention
+    if pooler == "final":
+        sd, m = W.final_attention_state_dict(5), FinalAttention(1024, 4096)
+    else:
+        sd, m = W.latent_attention_state_dict(5, ln_random=True), LatentAttentionModel()
+    m.load_state_dict(sd)
+    return m.to(dev).eval()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pooler,dtype", [("final", torch.float32), ("latent", torch.bfloat16)])
+def test_gpu_engine_recommend_explained(gpu_device, pooler, dtype):
+    from news_recommendation_project_v2_amd.engine import PoolScoreEngine
+    rng = np.random.default_rng(45)
+    n_news, n_imp, k = 300, 60, 10
+    distinct = [rng.integers(0, n_news, n).astype(np.int32) for n in rng.integers(1, 9, 14)]
+    pick = rng.integers(0, 14, n_imp)  # repeated histories: the deduplicated path
+    hl = np.array([len(distinct[p]) for p in pick], dtype=np.int32)
+    hi = np.concatenate([distinct[p] for p in pick]).astype(np.int32)
+    off = np.concatenate([[0], np.cumsum(hl)])
+    eq = lambda a, b: all(torch.equal(x, y) for x, y in zip(a, b))
+    results = {}
+    for dedupe in (True, False):
+        eng = PoolScoreEngine(_model(pooler, gpu_device), dtype=dtype, device=gpu_device)
+        eng.load_news(W.news_table(5, n_news, 1024, name="explain"))
+        eng.load_impressions(hi, hl, np.zeros(0, np.int32), np.zeros(n_imp, np.int32), dedupe=dedupe)
+        assert (eng.user_idx is not None) == dedupe
+        plain = eng.recommend(k)
+        idx, scores, why, val = eng.recommend_explained(k, top=3)
+        assert eq((idx, scores), plain), "recommend_explained's lists are recommend's"
+        assert why.shape == val.shape == (n_imp, k, 3) and why.dtype == torch.int32 and val.dtype == torch.float32
+        pos, val2, sums = eng.explain(idx, top=3, want_sum=True)
+        assert torch.equal(val, val2), "recommend_explained differs from explain of recommend's lists"
+        torch.cuda.synchronize()
+        pos_h, why_h = pos.cpu().numpy(), why.cpu().numpy()
+        for i in range(n_imp):
+            n = min(3, int(hl[i]))
+            assert np.array_equal(why_h[i, :, :n], hi[off[i] + pos_h[i, :, :n]]) and (why_h[i, :, n:] == -1).all()
+        assert float((sums - scores).abs().max()) <= SIM_EPS, "the contributions do not add up to recommend's score"
+        assert eq(eng.recommend_explained(k, top=3, user_block=7), (idx, scores, why, val))
+        div = eng.recommend_diverse(k, 0.5)
+        didx, dscores, dwhy, dval = eng.recommend_explained(k, top=3, lam=0.5)
+        assert eq((didx, dscores), div), "with lam the lists are recommend_diverse's"
+        assert torch.equal(dval, eng.explain(didx, top=3)[1])
+        assert eq(eng.recommend(k), plain), "recommend changed after recommend_explained"
+        with pytest.raises(ValueError):
+            eng.explain(idx[:5])
+        results[dedupe] = (idx, scores, why, val, didx, dwhy, dval)
+    assert eq(results[True], results[False]), "dedupe changes the explanations"
+
+
+@pytest.mark.gpu
+def test_gpu_get_top_k_recommendations_explain(gpu_device):
+    from news_recommendation_project_v2_amd import data_model_helper as dmh
+    from news_recommendation_project_v2_amd.engine import PoolScoreEngine
+    from news_recommendation_project_v2_amd.evaluation import explanation_metrics
+    rng = np.random.default_rng(46)
+    n_news, n_imp, k = 200, 30, 6
+    hl = rng.integers(1, 9, n_imp).astype(np.int32)
+    hi = rng.integers(0, n_news, int(hl.sum())).astype(np.int32)
+    table = W.news_table(5, n_news, 1024, name="explain-api")
+    m = _model("final", gpu_device)
+    eng = PoolScoreEngine(m, dtype=dmh.COMPUTE_DTYPE, device=gpu_device)
+    eng.load_news(table)
+    eng.load_impressions(hi, hl, np.zeros(0, np.int32), np.zeros(n_imp, np.int32))
+    wi, ws, wn, wv = (t.cpu().numpy() for t in eng.recommend_explained(k, top=3))
+    got = dmh.get_top_k_recommendations(hi, hl, table, m, k)
+    assert sorted(got) == ["news_index", "scores"], "the default return shape changed"
+    assert np.array_equal(got["news_index"], wi) and np.array_equal(_bits(got["scores"]), _bits(ws))
+    exp = dmh.get_top_k_recommendations(hi, hl, table, m, k, explain=3)
+    assert sorted(exp) == ["news_index", "scores", "why_news", "why_share"]
+    assert np.array_equal(exp["news_index"], wi) and np.array_equal(_bits(exp["scores"]), _bits(ws))
+    assert np.array_equal(exp["why_news"], wn) and np.array_equal(_bits(exp["why_share"]), _bits(wv))
+    assert exp["why_news"].dtype == np.int32 and exp["why_share"].dtype == np.float32
+    met = explanation_metrics(exp["why_share"], exp["scores"])
+    assert met["recommendations"] == n_imp * k and 0.0 <= met["negative_top"] <= 1.0
+    assert met["top1_share"] <= met["topT_share"] + 1e-12
+    div = dmh.get_top_k_recommendations(hi, hl, table, m, k, diversify=0.3, pool=32, explain=2)
+    assert sorted(div) == ["ild", "news_index", "plain_scores", "scores", "why_news", "why_share"]
+    di, ds, dn, dv = (t.cpu().numpy() for t in eng.recommend_explained(k, top=2, lam=0.3, pool=32))
+    assert np.array_equal(div["news_index"], di) and np.array_equal(div["why_news"], dn)
+    assert np.array_equal(_bits(div["why_share"]), _bits(dv))
+    old = dmh.get_top_k_recommendations(hi, hl, table, m, k, diversify=0.3, pool=32)
+    assert sorted(old) == ["ild", "news_index", "plain_scores", "scores"]
+    assert all(np.array_equal(_bits(old[n]), _bits(div[n])) for n in old)
+
+
+@pytest.mark.gpu
+def test_gpu_recommend_script_explain(gpu_device, tmp_path, monkeypatch, capsys):
+    """scripts/recommend.py --synthetic --explain 3 writes the because-news beside the
+    recommendations and the metrics into its JSON line."""
+    import runpy
+    import sys
+    monkeypatch.syspath_prepend(str(REPO / "scripts"))
+    monkeypatch.setattr(sys, "argv", ["recommend.py", "--synthetic", "--num-impressions", "200", "-k", "5", "--explain", "3",
+                                      "--out-dir", str(tmp_path), "--ckpt", str(tmp_path / "none.pt")])
+    runpy.run_path(str(REPO / "scripts" / "recommend.py"), run_name="__main__")
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    rec = np.load(tmp_path / "recommendations.npy")
+    why = np.load(tmp_path / "recommendations_why.npy")
+    share = np.load(tmp_path / "recommendations_why_share.npy")
+    assert why.shape == rec.shape + (3,) == share.shape and why.dtype == np.int32
+    assert line["explain"] == 3 and 0 < line["explained"] <= int((rec >= 0).sum())
+    assert line["explained"] == int((why[:, :, 0] >= 0).sum())
+    assert np.isfinite(line["top1_share"]) and np.isfinite(line["topT_share"]) and 0.0 <= line["negative_top"] <= 1.0
+    assert np.array_equal(why >= 0, np.isfinite(share)) and (why >= -1).all() and (why[rec < 0] == -1).all()
+
+
+# ------------------------------------------------------------------ 6. refusals
+@pytest.mark.gpu
+def test_gpu_explain_refusals_leave_outputs_untouched(gpu_device):
+    from news_recommendation_project_v2_amd import _lib, ops
+    lib = _lib.load()
+    dev = gpu_device
+    t, tb = _tables(torch.float32, dev), _tables(torch.bfloat16, dev)
+    hist_idx, hist_off, lst = _inputs(3)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    hi, ho, li = up(hist_idx), up(hist_off), up(lst[:, :10])
+    outs = {"tp": torch.full((3, 10, 3), 77, dtype=torch.int32, device=dev),
+            "tv": torch.full((3, 10, 3), 7.5, dtype=torch.float32, device=dev),
+            "so": torch.full((3, 10), 7.5, dtype=torch.float32, device=dev),
+            "co": torch.full((len(hist_idx), 10), 7.5, dtype=torch.float32, device=dev)}
+    host = np.zeros(4096, dtype=np.float32)
+    err = lambda: lib.nr_last_error().decode()
+    p = lambda v: None if v is None else v if isinstance(v, int) else v.data_ptr()
+    P = {"final": _lib.NR_POOL_FINAL, "latent": _lib.NR_POOL_LATENT, "mean": _lib.NR_POOL_MEAN}
+
+    def call(pooler="latent", dtype=_lib.NR_F32, dim=1024, ht=t["latent"], hld=1024, N=N_NEWS, ct=t["cand"], cld=1024,
+             inv=t["inv"], U=3, hi=hi, ho=ho, li=li, K=10, T=3, **o):
+        o = {**outs, **o}
+        return lib.nr_explain_scores(P.get(pooler, pooler), dtype, dim, p(ht), hld, N, p(ct), cld, p(inv), U, p(hi),
+                                     p(ho), p(li), K, T, p(o["tp"]), p(o["tv"]), p(o["so"]), p(o["co"]), None)
+
+    refused = [
+        (dict(dim=512), UNSUPPORTED, "dim 512 unsupported"), (dict(pooler=_lib.NR_POOL_NONE), INVALID, "bad pooler"),
+        (dict(pooler=3), INVALID, "bad pooler"), (dict(dtype=_lib.NR_F16), INVALID, "bad dtype"),
+        (dict(dtype=9), INVALID, "bad dtype"), (dict(K=0), INVALID, "K = 0 outside"),
+        (dict(K=65), INVALID, "K = 65 outside"), (dict(T=0), INVALID, "T = 0 outside"),
+        (dict(T=9), INVALID, "T = 9 outside"), (dict(tp=None), INVALID, "go together"),
+        (dict(tv=None), INVALID, "go together"), (dict(tp=None, tv=None, so=None, co=None), INVALID, "no output"),
+        (dict(U=0), INVALID, "U = 0"), (dict(U=1 << 31), INVALID, "U = 2147483648"), (dict(N=0), INVALID, "N = 0"),
+        (dict(N=1 << 31), INVALID, "N = 2147483648"), (dict(hld=1000), INVALID, "leading dimension"),
+        (dict(cld=1000), INVALID, "leading dimension"),
+        (dict(pooler="final", ht=t["final"], hld=1024), INVALID, "leading dimension"),
+        (dict(hld=1026), INVALID, "16-byte"), (dict(dtype=_lib.NR_BF16, ht=tb["latent"], ct=tb["cand"], cld=1028),
+                                                INVALID, "16-byte"),
+        (dict(ht=t["latent"].data_ptr() + 4), INVALID, "16-byte"), (dict(ct=t["cand"].data_ptr() + 8), INVALID, "16-byte"),
+    ]
+    refused += [({n: None}, INVALID, "null pointer") for n in ("ht", "ct", "inv", "hi", "ho", "li")]
+    refused += [({n: host.ctypes.data}, INVALID, "not device memory")
+                for n in ("ht", "ct", "inv", "hi", "ho", "li", "tp", "tv", "so", "co")]
+    for kw, want, text in refused:
+        assert call(**kw) == want and text in err(), (kw, err())
+    torch.cuda.synchronize()
+    for n, o in outs.items():
+        assert bool((o == (77 if o.dtype == torch.int32 else 7.5)).all()), f"a refused call wrote {n}"
+    # the wrapper refuses the same before the library is reached
+    args = ("latent", t["latent"], t["cand"], t["inv"], hi, ho, li)
+    for bad in (dict(top=9), dict(top=-1), dict(top=0)):
+        with pytest.raises(_lib.NewsRecHIPError):
+            ops.explain_scores(*args, **bad)
+    with pytest.raises(_lib.NewsRecHIPError):
+        ops.explain_scores("max", *args[1:])
+    with pytest.raises(_lib.NewsRecHIPError):
+        ops.explain_scores("final", *args[1:])  # a FINAL row is x | p
+    with pytest.raises(_lib.NewsRecHIPError):
+        ops.explain_scores(*args[:6], li.long())
+    with pytest.raises(_lib.NewsRecHIPError):
+        ops.explain_scores(*args[:6], up(lst[:, :0]))
+    with pytest.raises(_lib.NewsRecHIPError):
+        ops.explain_scores(*args[:5], ho[:-1], li)
+    with pytest.raises(_lib.NewsRecHIPError):
+        ops.explain_scores("latent", tb["latent"], *args[2:])
+    with pytest.raises(_lib.NewsRecHIPError):
+        ops.explain_scores(*args, out=(outs["tp"], outs["tv"]))
+    with pytest.raises(_lib.NewsRecHIPError):
+        ops.explain_scores(*args, want_sum=True, out=(outs["tp"], outs["tv"], None, None))
+    # and the accepted call writes every output (the first user's history is empty: its sums are 0)
+    assert call() == 0, err()
+    torch.cuda.synchronize()
+    assert not bool((outs["tp"] == 77).any()) and not bool((outs["tv"] == 7.5).any())
+    assert not bool((outs["so"] == 7.5).any()) and not bool((outs["co"] == 7.5).any())
