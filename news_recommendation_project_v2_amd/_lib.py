@@ -23,7 +23,8 @@ HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip
 # the headers they include (every object is rebuilt when one changes), hashed after the sources
 HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CSRC / "nr_score_tile.h",
                INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
-               INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h")
+               INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h",
+               INCLUDE / "newsrec_filter.h")
 
 
 def hip_source_files() -> list:
@@ -173,6 +174,14 @@ EXPLAIN_SIGNATURES = {
     "nr_explain_scores": (_i, [_i, _i, _l, _p, _l, _l, _p, _l, _p, _l, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p]),
 }
 
+# catalogue filters of retrieval and ranks (include/newsrec_filter.h), bound by load() like SIGNATURES
+FILTER_SIGNATURES = {
+    "nr_topk_users_filtered": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _l,
+                                    _p]),
+    "nr_rank_targets_filtered": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p,
+                                      _l, _p]),
+}
+
 
 class ContrastiveSpec(ctypes.Structure):
     """struct nr_contrastive_spec (include/newsrec_contrastive.h)."""
@@ -230,7 +239,8 @@ def load() -> ctypes.CDLL:
             "(there is no CPU fallback for the MI355X hot path)")
     lib = ctypes.CDLL(os.fspath(LIB_PATH))
     for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES,
-                              **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES}.items():
+                              **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES,
+                              **FILTER_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

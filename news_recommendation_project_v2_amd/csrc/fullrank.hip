@@ -25,8 +25,13 @@
 //               lane exchange and added to rank[] per tile.  No target count is refused or
 //               truncated.  Counts of workgroups that ran side by side are summed by integer
 //               atomics into the zeroed rank[]: the sum does not depend on their order.
+//
+// nr_rank_targets_filtered (include/newsrec_filter.h) runs both kernels' filtered instantiations:
+// a target outside its user's window or mask gets the NaN threshold, and the counting pass
+// writes -inf over such rows of every score tile.
 #include "nr_score_tile.h"
 
+#include "../../include/newsrec_filter.h"
 #include "../../include/newsrec_fullrank.h"
 
 namespace nr {
@@ -36,13 +41,15 @@ constexpr int TCAP = 32;  // targets of a user whose thresholds and counters sta
 
 __device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
-template <typename TI>
+// FILT (here and in rank_count_kernel): the catalogue filter of include/newsrec_filter.h; the
+// unfiltered instantiations hold none of it.
+template <typename TI, bool FILT>
 __global__ __launch_bounds__(256) void rank_thresholds_kernel(int64_t U, int64_t N, int64_t Tn,
                                                               const TI* __restrict__ users,
                                                               const TI* __restrict__ tab, int64_t ldt,
                                                               const float* __restrict__ cinv,
                                                               const int32_t* __restrict__ excl_idx,
-                                                              const int64_t* __restrict__ excl_off,
+                                                              const int64_t* __restrict__ excl_off, FilterArgs flt,
                                                               const int32_t* __restrict__ tgt_idx,
                                                               const int64_t* __restrict__ tgt_off,
                                                               float* __restrict__ tsel, int32_t* __restrict__ rank) {
@@ -100,6 +107,10 @@ __global__ __launch_bounds__(256) void rank_thresholds_kernel(int64_t U, int64_t
         const int64_t e1 = excl_off[m0 + lo + 1];
         for (int64_t e = excl_off[m0 + lo]; e < e1; ++e) ok &= excl_idx[e] != t;
       }
+      if constexpr (FILT) {  // a target outside its user's window or mask: the NaN threshold of an excluded one
+        if (ok && flt.news_time) ok = in_window(flt.news_time[t], flt.q_lo[m0 + lo], flt.q_hi[m0 + lo]);
+        if (ok && flt.news_cat) ok = in_mask(flt.news_cat[t], flt.q_mask[m0 + lo]);
+      }
       tsel[j] = ok ? T[lo * TLD + tid] : __builtin_nanf("");
       if (!ok) rank[j] = -1;
     }
@@ -132,12 +143,12 @@ __device__ __forceinline__ int count_better(const int (&k)[64], int K, int32_t t
   return c;
 }
 
-template <typename TI>
+template <typename TI, bool FILT>
 __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, int64_t Tn,
                                                          const TI* __restrict__ users, const TI* __restrict__ tab,
                                                          int64_t ldt, const float* __restrict__ cinv,
                                                          const int32_t* __restrict__ excl_idx,
-                                                         const int64_t* __restrict__ excl_off,
+                                                         const int64_t* __restrict__ excl_off, FilterArgs flt,
                                                          const int32_t* __restrict__ tgt_idx,
                                                          const int64_t* __restrict__ tgt_off,
                                                          const float* __restrict__ tsel, int64_t span_rows,
@@ -149,6 +160,8 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
   __shared__ int tk_s[TCAP * TS];      // the users' first TCAP targets, [slot][user]: threshold keys,
   __shared__ int32_t tr_s[TCAP * TS];  //   rows,
   __shared__ int tc_s[TCAP * TS];      //   and counters (both threads of a user add to one)
+  __shared__ __attribute__((aligned(16))) int32_t ft_s[FILT ? ATTR_TIME_WORDS : 4];  // the tile's news times
+  __shared__ uint32_t fc_s[FILT ? ATTR_CAT_WORDS : 1];                                //   and categories
   float* T = reinterpret_cast<float*>(smem);
 
   const int tid = threadIdx.x;
@@ -164,6 +177,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
   const int su = tid >> 1, sh = tid & 1;
   const bool live = m0 + su < U;
   Excluded ex(ex_s, ov_mask, excl_idx, excl_off, m0, live, c0);
+  FilterOf<FILT> el(ft_s, fc_s, flt, m0, live);
   int64_t t0 = 0, t1 = 0;  // the user's targets (clamped into [0, T])
   if (live) {
     t0 = clamp64(tgt_off[m0 + su], 0, Tn);
@@ -187,6 +201,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
     if (tile == 0 || n0 == ex.cb + kChunk) ex.chunk_start(n0);
     const int nvalid = (int)min((int64_t)TS, N - n0);
     if (tid < TS) cinv_s[tid] = tid < nvalid ? cinv[n0 + tid] : 0.f;
+    if constexpr (FILT) el.stage(n0, N);
     st.scores(tab, ldt, rows_from(n0), tile + 1 < ntiles, rows_from(n0 + TS), nvalid);
     ex.knock_out_overflow(T, m0, n0);
     // ---- -inf over the user's staged excluded rows that fall in this tile (idempotent under duplicates)
@@ -195,6 +210,21 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
       for (int i = 0; i < ex.xn; ++i) {
         const int d = (int)ex_s[i * TS + su] - base;
         if (d >= 0 && d < TS) T[su * TLD + d] = NINF;
+      }
+    }
+    // ---- -inf over the rows outside the user's window or mask: each of its two threads over its
+    // own 64 columns (stores of -inf only, like the ones above: no store can undo another)
+    if constexpr (FILT) {
+      uint32_t elo, ehi;
+      el.rows64(sh, elo, ehi);
+      float* row = T + su * TLD + 64 * sh;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const uint32_t out = ~(h ? ehi : elo);
+        if (out == 0) continue;
+#pragma unroll
+        for (int i = 0; i < 32; ++i)
+          if ((out >> i) & 1u) row[32 * h + i] = NINF;
       }
     }
     __syncthreads();
@@ -257,12 +287,15 @@ extern "C" int64_t nr_rank_targets_workspace_bytes(int dtype, int64_t U, int64_t
   return nr::tk::rank_layout(dtype, U, N, T).total;
 }
 
-extern "C" int nr_rank_targets(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
-                               const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
-                               const int32_t* excl_idx, const int64_t* excl_off, int64_t T, const int32_t* tgt_idx,
-                               const int64_t* tgt_off, int32_t* rank, void* ws, int64_t ws_bytes, void* stream) {
-  using namespace nr::tk;
-  constexpr const char* fn = "nr_rank_targets";
+namespace nr {
+namespace tk {
+
+// nr_rank_targets and nr_rank_targets_filtered: one validation, one launch sequence.  A filter
+// with both pairs null runs the unfiltered kernels.
+static int rank_run(const char* fn, int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                    const void* cand_table, int64_t cand_ld, const float* cand_inv_norm, const int32_t* excl_idx,
+                    const int64_t* excl_off, const FilterArgs& flt, int64_t T, const int32_t* tgt_idx,
+                    const int64_t* tgt_off, int32_t* rank, void* ws, int64_t ws_bytes, void* stream) {
   nr::clear_error();
   if (dim != 1024) {
     nr::set_error("%s: dim %lld unsupported (1024 only)", fn, (long long)dim);
@@ -281,6 +314,9 @@ extern "C" int nr_rank_targets(int dtype, int64_t dim, int64_t U, const float* u
                    ((uintptr_t)users & 15) == 0,
                "%s: users and cand_table must be 16-byte aligned with 16-byte row strides", fn);
   NR_CHECK_ARG((excl_idx == nullptr) == (excl_off == nullptr), "%s: excl_idx and excl_off go together", fn);
+  NR_CHECK_ARG((flt.news_time == nullptr) == (flt.q_lo == nullptr) && (flt.news_time == nullptr) == (flt.q_hi == nullptr),
+               "%s: news_time, q_time_lo and q_time_hi go together", fn);
+  NR_CHECK_ARG((flt.news_cat == nullptr) == (flt.q_mask == nullptr), "%s: news_cat and q_cat_mask go together", fn);
   NR_CHECK_ARG(users && cand_table && cand_inv_norm && tgt_off && ws && (T == 0 || (tgt_idx && rank)),
                "%s: null pointer", fn);
   const RankLayout L = rank_layout(dtype, U, N, T);
@@ -288,6 +324,12 @@ extern "C" int nr_rank_targets(int dtype, int64_t dim, int64_t U, const float* u
                (long long)L.total);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
   NR_CHECK_DEVICE(fn, users, cand_table, cand_inv_norm, excl_idx, excl_off, tgt_idx, tgt_off, rank, ws);
+  {
+    const int32_t *news_time = flt.news_time, *q_time_lo = flt.q_lo, *q_time_hi = flt.q_hi;
+    const uint8_t* news_cat = flt.news_cat;
+    const uint64_t* q_cat_mask = flt.q_mask;
+    NR_CHECK_DEVICE(fn, news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask);
+  }
   if (T == 0) return NR_OK;
 
   hipStream_t st = (hipStream_t)stream;
@@ -303,25 +345,58 @@ extern "C" int nr_rank_targets(int dtype, int64_t dim, int64_t U, const float* u
   const int64_t nparts = (L.nchunks + span - 1) / span;
   const dim3 g0((unsigned)((U + TS - 1) / TS));
   const dim3 g1(g0.x, (unsigned)nparts);
+  const void* urows = users;
   if (dtype == NR_BF16) {
     __bf16* ub = (__bf16*)(w + L.ub);
     const int rcb = bf16_users_launch(U, users, ub, st, fn);
     if (rcb) return rcb;
-    hipLaunchKernelGGL(rank_thresholds_kernel<__bf16>, g0, dim3(256), 0, st, U, N, T, (const __bf16*)ub,
-                       (const __bf16*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, tgt_idx, tgt_off, tsel,
-                       rank);
-    NR_CHECK_LAUNCH(fn);
-    hipLaunchKernelGGL(rank_count_kernel<__bf16>, g1, dim3(256), 0, st, U, N, T, (const __bf16*)ub,
-                       (const __bf16*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, tgt_idx, tgt_off,
-                       (const float*)tsel, span * kChunk, rank);
-  } else {
-    hipLaunchKernelGGL(rank_thresholds_kernel<float>, g0, dim3(256), 0, st, U, N, T, users, (const float*)cand_table,
-                       cand_ld, cand_inv_norm, excl_idx, excl_off, tgt_idx, tgt_off, tsel, rank);
-    NR_CHECK_LAUNCH(fn);
-    hipLaunchKernelGGL(rank_count_kernel<float>, g1, dim3(256), 0, st, U, N, T, users, (const float*)cand_table,
-                       cand_ld, cand_inv_norm, excl_idx, excl_off, tgt_idx, tgt_off, (const float*)tsel,
-                       span * kChunk, rank);
+    urows = ub;
   }
-  NR_CHECK_LAUNCH(fn);
-  return NR_OK;
+  const int filtered = flt.any() ? 1 : 0;
+  return nr::with_dtype(dtype, [&](auto ti) {
+    using TI = typename decltype(ti)::type;
+    return nr::with_int<0, 1>(
+        filtered, [&] { return nr::unvalidated_code("filter", filtered); },
+        [&](auto fc) {
+          constexpr bool F = decltype(fc)::value != 0;
+          hipLaunchKernelGGL((rank_thresholds_kernel<TI, F>), g0, dim3(256), 0, st, U, N, T, (const TI*)urows,
+                             (const TI*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, flt, tgt_idx, tgt_off,
+                             tsel, rank);
+          NR_CHECK_LAUNCH(fn);
+          hipLaunchKernelGGL((rank_count_kernel<TI, F>), g1, dim3(256), 0, st, U, N, T, (const TI*)urows,
+                             (const TI*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, flt, tgt_idx, tgt_off,
+                             (const float*)tsel, span * kChunk, rank);
+          NR_CHECK_LAUNCH(fn);
+          return NR_OK;
+        });
+  });
 }
+
+}  // namespace tk
+}  // namespace nr
+
+extern "C" int nr_rank_targets(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                               const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
+                               const int32_t* excl_idx, const int64_t* excl_off, int64_t T, const int32_t* tgt_idx,
+                               const int64_t* tgt_off, int32_t* rank, void* ws, int64_t ws_bytes, void* stream) {
+  return nr::tk::rank_run("nr_rank_targets", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx,
+                          excl_off, nr::tk::FilterArgs{}, T, tgt_idx, tgt_off, rank, ws, ws_bytes, stream);
+}
+
+extern "C" int nr_rank_targets_filtered(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                                        const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
+                                        const int32_t* excl_idx, const int64_t* excl_off, const int32_t* news_time,
+                                        const int32_t* q_time_lo, const int32_t* q_time_hi, const uint8_t* news_cat,
+                                        const uint64_t* q_cat_mask, int64_t T, const int32_t* tgt_idx,
+                                        const int64_t* tgt_off, int32_t* rank, void* ws, int64_t ws_bytes,
+                                        void* stream) {
+  nr::tk::FilterArgs flt;
+  flt.news_time = news_time;
+  flt.q_lo = q_time_lo;
+  flt.q_hi = q_time_hi;
+  flt.news_cat = news_cat;
+  flt.q_mask = q_cat_mask;
+  return nr::tk::rank_run("nr_rank_targets_filtered", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm,
+                          excl_idx, excl_off, flt, T, tgt_idx, tgt_off, rank, ws, ws_bytes, stream);
+}
+

@@ -14,6 +14,8 @@
 //   Excluded       a user's excluded rows inside the current chunk, staged in LDS once per
 //                  chunk as 16-bit offsets; a user with more than XCAP of them has its rows set
 //                  to -inf in every score tile by the whole workgroup instead.
+//   Eligible       the catalogue filter (include/newsrec_filter.h) of the kernels' filtered
+//                  instantiations: a predicate on the finished score tile, never on the product.
 #pragma once
 
 #include "nr_common.h"
@@ -284,6 +286,119 @@ struct Excluded {
     if (any) __syncthreads();
   }
 };
+
+// The catalogue filter of include/newsrec_filter.h: per-news attributes, per-user window and
+// category mask.  A null pair passes every row.
+struct FilterArgs {
+  const int32_t* news_time = nullptr;
+  const int32_t* q_lo = nullptr;
+  const int32_t* q_hi = nullptr;
+  const uint8_t* news_cat = nullptr;
+  const uint64_t* q_mask = nullptr;
+  bool any() const { return news_time || news_cat; }
+};
+
+constexpr int ATTR_HALF = TS / 2 + 4;  // words between the two 64-row halves of the staged times (see Eligible)
+constexpr int ATTR_TIME_WORDS = ATTR_HALF + TS / 2;
+constexpr int ATTR_CAT_WORDS = TS / 4;
+
+// the predicate as include/newsrec_filter.h states it (one target at a time: rank_thresholds_kernel)
+__device__ __forceinline__ bool in_window(int32_t t, int32_t lo, int32_t hi) { return t >= lo && t <= hi; }
+__device__ __forceinline__ bool in_mask(uint32_t cat, uint64_t mask) { return cat < 64 && ((mask >> (cat & 63)) & 1) != 0; }
+
+// Threads 2u and 2u + 1 serve user u of the block: its window and mask live in their registers,
+// the tile's 128 times and 128 categories in LDS (staged once per tile next to cinv_s).  Thread
+// half sh reads rows [64 sh, 64 sh + 64): every lane of a half reads one address (a broadcast),
+// and the second half of the times sits 4 words past a whole number of bank rows, so the two
+// b128 addresses of a wave never meet in a bank.  A null pair is staged as zeros against the
+// widest window / the full mask, so the test has no branch on it.  The window test is one
+// unsigned compare, (t - lo) <= (hi - lo) in 32-bit wrap-around arithmetic (exact for every
+// lo <= hi); an empty window (lo > hi) is held as the mask 0 instead.
+struct Eligible {
+  static constexpr int SPARSE_MAX = 8;  // scan survivors per thread up to which only they are tested
+  int32_t* t_s;   // [ATTR_TIME_WORDS]
+  uint32_t* c_s;  // [ATTR_CAT_WORDS], one byte per news row
+  const int32_t* news_time;
+  const uint8_t* news_cat;
+  uint32_t lo, span, mask_lo, mask_hi;
+
+  __device__ __forceinline__ Eligible(int32_t* t_s_, uint32_t* c_s_, const FilterArgs& f, int64_t m0, bool live)
+      : t_s(t_s_), c_s(c_s_), news_time(f.news_time), news_cat(f.news_cat), lo((uint32_t)INT32_MIN), span(~0u),
+        mask_lo(~0u), mask_hi(~0u) {
+    const int su = threadIdx.x >> 1;
+    if (live && f.news_cat) {
+      const uint64_t m = f.q_mask[m0 + su];
+      mask_lo = (uint32_t)m;
+      mask_hi = (uint32_t)(m >> 32);
+    }
+    if (live && f.news_time) {
+      const int32_t a = f.q_lo[m0 + su], b = f.q_hi[m0 + su];
+      lo = (uint32_t)a;
+      span = (uint32_t)b - (uint32_t)a;
+      if (a > b) span = mask_lo = mask_hi = 0;
+    }
+  }
+  __device__ __forceinline__ bool row_ok(int32_t t, uint32_t cat) const {
+    return (uint32_t)t - lo <= span && cat < 64 && ((((cat & 32) ? mask_hi : mask_lo) >> (cat & 31)) & 1u) != 0;
+  }
+  // the attributes of news rows [n0, n0 + TS), clamped past the table as the row loads are
+  // (those rows' scores are -inf already).  Called by every thread, before ScoreTile::scores:
+  // its barriers order these stores before the reads below, the tile's closing barrier orders
+  // the reads before the next tile's stores.
+  __device__ __forceinline__ void stage(int64_t n0, int64_t N) {
+    const int t = threadIdx.x;
+    if (t < TS) {
+      const int64_t r = min(n0 + t, N - 1);
+      t_s[t + (t >> 6) * (ATTR_HALF - TS / 2)] = news_time ? news_time[r] : 0;
+      reinterpret_cast<uint8_t*>(c_s)[t] = news_cat ? news_cat[r] : (uint8_t)0;
+    }
+  }
+  // bit i of (elo | ehi << 32): tile row 64 sh + i is inside the user's window and mask
+  __device__ __forceinline__ void rows64(int sh, uint32_t& elo, uint32_t& ehi) const {
+    const int32_t* t = t_s + ATTR_HALF * sh;
+    const uint32_t* c = c_s + (TS / 8) * sh;
+    elo = ehi = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int4 tv = *reinterpret_cast<const int4*>(t + 4 * i);
+      const uint32_t cw = c[i];
+      const uint32_t b = (row_ok(tv.x, cw & 255u) ? 1u : 0u) | (row_ok(tv.y, (cw >> 8) & 255u) ? 2u : 0u) |
+                         (row_ok(tv.z, (cw >> 16) & 255u) ? 4u : 0u) | (row_ok(tv.w, cw >> 24) ? 8u : 0u);
+      if (i < 8) elo |= b << (4 * i);
+      else ehi |= b << (4 * (i - 8));
+    }
+  }
+  // Top-K's scan: clear the bits of (mlo | mhi << 32) -- the rows of this thread's half that beat
+  // the running K-th best -- whose rows are not eligible.  Once K rows are kept few rows pass
+  // the scan (K (1 + ln(rows / K)) over a whole walk), so only they are tested, one at a time;
+  // while a thread of the wave still has many (the list is filling: every finite score passes),
+  // all 64 rows are.  Both ways apply the same test.  Called by every thread.
+  __device__ __forceinline__ void keep_eligible(int sh, uint32_t& mlo, uint32_t& mhi) const {
+    if (__any(__popc(mlo) + __popc(mhi) > SPARSE_MAX)) {
+      uint32_t elo, ehi;
+      rows64(sh, elo, ehi);
+      mlo &= elo;
+      mhi &= ehi;
+      return;
+    }
+    const int32_t* t = t_s + ATTR_HALF * sh;
+    const uint8_t* c = reinterpret_cast<const uint8_t*>(c_s) + (TS / 2) * sh;
+    for (uint32_t b = mlo; b; b &= b - 1) {
+      const int i = __builtin_ctz(b);
+      if (!row_ok(t[i], c[i])) mlo &= ~(1u << i);
+    }
+    for (uint32_t b = mhi; b; b &= b - 1) {
+      const int i = __builtin_ctz(b);
+      if (!row_ok(t[32 + i], c[32 + i])) mhi &= ~(1u << i);
+    }
+  }
+};
+
+// what the unfiltered instantiations construct in its place: nothing
+struct NoFilter {
+  __device__ __forceinline__ NoFilter(int32_t*, uint32_t*, const FilterArgs&, int64_t, bool) {}
+};
+template <bool FILT> using FilterOf = std::conditional_t<FILT, Eligible, NoFilter>;
 
 }  // namespace tk
 }  // namespace nr

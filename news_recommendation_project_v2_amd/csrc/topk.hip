@@ -25,8 +25,12 @@
 //
 // Every comparison is on the strict total order (score descending, row ascending), so no
 // result depends on the order in which lanes or workgroups ran.
+//
+// nr_topk_users_filtered (include/newsrec_filter.h) is the same launch sequence with stage 1's
+// filtered instantiation: the catalogue predicate is applied to the scan's survivors.
 #include "nr_score_tile.h"
 
+#include "../../include/newsrec_filter.h"
 #include "../../include/newsrec_topk.h"
 
 namespace nr {
@@ -57,13 +61,17 @@ int bf16_users_launch(int64_t U, const float* users, __bf16* out, hipStream_t st
   return NR_OK;
 }
 
-template <typename TI>
+// FILT: the catalogue filter (include/newsrec_filter.h).  The predicate is ANDed into the scan's
+// masks, so an ineligible row never reaches the serial drain: while fewer than K rows are kept
+// every finite score passes the scan, and a selective filter would otherwise feed the heap loop
+// all of them.  The unfiltered instantiation holds none of it.
+template <typename TI, bool FILT>
 __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, const TI* __restrict__ users,
                                                           const TI* __restrict__ tab, int64_t ldt,
                                                           const float* __restrict__ cinv,
                                                           const int32_t* __restrict__ excl_idx,
-                                                          const int64_t* __restrict__ excl_off, int K,
-                                                          int64_t span_rows, Pair* __restrict__ part) {
+                                                          const int64_t* __restrict__ excl_off, FilterArgs flt,
+                                                          int K, int64_t span_rows, Pair* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) uint32_t smem[4 * TILE_WORDS];  // ring [2][news | users]; score tile
   __shared__ float ls[KMAX * TS];  // the users' sorted lists, [rank][user]
   __shared__ int32_t li[KMAX * TS];
@@ -71,6 +79,8 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
   __shared__ int cnt_s[TS];
   __shared__ uint16_t ex_s[XCAP * TS];
   __shared__ uint32_t ov_mask[TS / 32];
+  __shared__ __attribute__((aligned(16))) int32_t ft_s[FILT ? ATTR_TIME_WORDS : 4];  // the tile's news times
+  __shared__ uint32_t fc_s[FILT ? ATTR_CAT_WORDS : 1];                                //   and categories
   float* T = reinterpret_cast<float*>(smem);
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -87,6 +97,7 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
   const int su = tid >> 1, sh = tid & 1;
   const bool live = m0 + su < U;
   Excluded ex(ex_s, ov_mask, excl_idx, excl_off, m0, live, c0);
+  FilterOf<FILT> el(ft_s, fc_s, flt, m0, live);
   int cnt = 0;            // rows kept so far (a heap in LDS, the worst at slot 0)
   float thr = NINF;       // the worst's score once K are kept; -inf until then (every finite score passes)
 
@@ -100,6 +111,7 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
     if (tile == 0 || n0 == ex.cb + kChunk) ex.chunk_start(n0);
     const int nvalid = (int)min((int64_t)TS, N - n0);
     if (tid < TS) cinv_s[tid] = tid < nvalid ? cinv[n0 + tid] : 0.f;
+    if constexpr (FILT) el.stage(n0, N);
     st.scores(tab, ldt, rows_from(n0), tile + 1 < ntiles, rows_from(n0 + TS), nvalid);
     ex.knock_out_overflow(T, m0, n0);
     // ---- scan against the running K-th best; what passes and is not excluded is kept (ascending row)
@@ -114,6 +126,7 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
         else mhi |= b << (4 * (i - 8));
       }
     }
+    if constexpr (FILT) el.keep_eligible(sh, mlo, mhi);
     const uint32_t plo = __shfl_down(mlo, 1, 64), phi = __shfl_down(mhi, 1, 64);
     if (sh == 0 && live) {
       // 32 columns of the row at a time, in ascending row order
@@ -318,12 +331,15 @@ extern "C" int64_t nr_topk_workspace_bytes(int dtype, int64_t U, int64_t N, int6
   return nr::tk::layout(dtype, U, N, K).total;
 }
 
-extern "C" int nr_topk_users(int dtype, int64_t dim, int64_t U, const float* users, int64_t N, const void* cand_table,
-                             int64_t cand_ld, const float* cand_inv_norm, const int32_t* excl_idx,
-                             const int64_t* excl_off, int64_t K, int32_t* top_idx, float* top_scores, void* ws,
-                             int64_t ws_bytes, void* stream) {
-  using namespace nr::tk;
-  constexpr const char* fn = "nr_topk_users";
+namespace nr {
+namespace tk {
+
+// nr_topk_users and nr_topk_users_filtered: one validation, one launch sequence.  A filter with
+// both pairs null runs the unfiltered stage 1.
+static int topk_run(const char* fn, int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                    const void* cand_table, int64_t cand_ld, const float* cand_inv_norm, const int32_t* excl_idx,
+                    const int64_t* excl_off, const FilterArgs& flt, int64_t K, int32_t* top_idx, float* top_scores,
+                    void* ws, int64_t ws_bytes, void* stream) {
   nr::clear_error();
   if (dim != 1024) {
     nr::set_error("%s: dim %lld unsupported (1024 only)", fn, (long long)dim);
@@ -342,12 +358,21 @@ extern "C" int nr_topk_users(int dtype, int64_t dim, int64_t U, const float* use
                    ((uintptr_t)users & 15) == 0,
                "%s: users and cand_table must be 16-byte aligned with 16-byte row strides", fn);
   NR_CHECK_ARG((excl_idx == nullptr) == (excl_off == nullptr), "%s: excl_idx and excl_off go together", fn);
+  NR_CHECK_ARG((flt.news_time == nullptr) == (flt.q_lo == nullptr) && (flt.news_time == nullptr) == (flt.q_hi == nullptr),
+               "%s: news_time, q_time_lo and q_time_hi go together", fn);
+  NR_CHECK_ARG((flt.news_cat == nullptr) == (flt.q_mask == nullptr), "%s: news_cat and q_cat_mask go together", fn);
   NR_CHECK_ARG(users && cand_table && cand_inv_norm && top_idx && top_scores && ws, "%s: null pointer", fn);
   const Layout L = layout(dtype, U, N, K);
   NR_CHECK_ARG(ws_bytes >= L.total, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes,
                (long long)L.total);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
   NR_CHECK_DEVICE(fn, users, cand_table, cand_inv_norm, excl_idx, excl_off, top_idx, top_scores, ws);
+  {
+    const int32_t *news_time = flt.news_time, *q_time_lo = flt.q_lo, *q_time_hi = flt.q_hi;
+    const uint8_t* news_cat = flt.news_cat;
+    const uint64_t* q_cat_mask = flt.q_mask;
+    NR_CHECK_DEVICE(fn, news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask);
+  }
 
   hipStream_t st = (hipStream_t)stream;
   char* w = (char*)ws;
@@ -361,16 +386,26 @@ extern "C" int nr_topk_users(int dtype, int64_t dim, int64_t U, const float* use
   const int64_t span = chunk_span(U, L.nchunks);
   const int64_t nparts = (L.nchunks + span - 1) / span;
   const dim3 g1((unsigned)((U + TS - 1) / TS), (unsigned)nparts);
+  const void* urows = users;
   if (dtype == NR_BF16) {
     __bf16* ub = (__bf16*)(w + L.ub);
     const int rcb = bf16_users_launch(U, users, ub, st, fn);
     if (rcb) return rcb;
-    hipLaunchKernelGGL(topk_stage1_kernel<__bf16>, g1, dim3(256), 0, st, U, N, (const __bf16*)ub,
-                       (const __bf16*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, (int)K, span * kChunk, part);
-  } else {
-    hipLaunchKernelGGL(topk_stage1_kernel<float>, g1, dim3(256), 0, st, U, N, users, (const float*)cand_table, cand_ld,
-                       cand_inv_norm, excl_idx, excl_off, (int)K, span * kChunk, part);
+    urows = ub;
   }
+  const int filtered = flt.any() ? 1 : 0;
+  const int rc1 = nr::with_dtype(dtype, [&](auto ti) {
+    using TI = typename decltype(ti)::type;
+    return nr::with_int<0, 1>(
+        filtered, [&] { return nr::unvalidated_code("filter", filtered); },
+        [&](auto fc) {
+          hipLaunchKernelGGL((topk_stage1_kernel<TI, decltype(fc)::value != 0>), g1, dim3(256), 0, st, U, N,
+                             (const TI*)urows, (const TI*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, flt,
+                             (int)K, span * kChunk, part);
+          return NR_OK;
+        });
+  });
+  if (rc1) return rc1;
   NR_CHECK_LAUNCH(fn);
   const dim3 gw((unsigned)((U + 3) / 4));
   hipLaunchKernelGGL(topk_merge_kernel, gw, dim3(256), 0, st, U, (int)K, (int)nparts, (const Pair*)part, top_idx, cnt,
@@ -383,3 +418,31 @@ extern "C" int nr_topk_users(int dtype, int64_t dim, int64_t U, const float* use
   NR_CHECK_LAUNCH(fn);
   return NR_OK;
 }
+
+}  // namespace tk
+}  // namespace nr
+
+extern "C" int nr_topk_users(int dtype, int64_t dim, int64_t U, const float* users, int64_t N, const void* cand_table,
+                             int64_t cand_ld, const float* cand_inv_norm, const int32_t* excl_idx,
+                             const int64_t* excl_off, int64_t K, int32_t* top_idx, float* top_scores, void* ws,
+                             int64_t ws_bytes, void* stream) {
+  return nr::tk::topk_run("nr_topk_users", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx,
+                          excl_off, nr::tk::FilterArgs{}, K, top_idx, top_scores, ws, ws_bytes, stream);
+}
+
+extern "C" int nr_topk_users_filtered(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                                      const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
+                                      const int32_t* excl_idx, const int64_t* excl_off, const int32_t* news_time,
+                                      const int32_t* q_time_lo, const int32_t* q_time_hi, const uint8_t* news_cat,
+                                      const uint64_t* q_cat_mask, int64_t K, int32_t* top_idx, float* top_scores,
+                                      void* ws, int64_t ws_bytes, void* stream) {
+  nr::tk::FilterArgs flt;
+  flt.news_time = news_time;
+  flt.q_lo = q_time_lo;
+  flt.q_hi = q_time_hi;
+  flt.news_cat = news_cat;
+  flt.q_mask = q_cat_mask;
+  return nr::tk::topk_run("nr_topk_users_filtered", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm,
+                          excl_idx, excl_off, flt, K, top_idx, top_scores, ws, ws_bytes, stream);
+}
+

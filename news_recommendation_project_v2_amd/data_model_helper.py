@@ -142,6 +142,7 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
                               news_embeddings: torch.Tensor, attention_model: torch.nn.Module, k: int,
                               exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
                               dtype=None, diversify: Optional[float] = None, pool: Optional[int] = None,
+                              news_time=None, news_category=None, time_window=None, categories=None,
                               explain: Optional[int] = None) -> dict:
     """The k news of the WHOLE table that the model recommends per impression:
     ``{"news_index": int32 [I, k], "scores": float32 [I, k]}`` on the host, score
@@ -170,7 +171,13 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     of the score (all of a history's shares add up to the score), value descending;
     ``(-1, -inf)`` for a missing recommendation and past the history's length
     (evaluation.explanation_metrics summarises them).  Without ``explain`` the result is as
-    described above."""
+    described above.
+
+    Catalogue filters (include/newsrec_filter.h): ``news_time`` int32 [N] with ``time_window``
+    = (lo, hi) keeps the news with lo <= news_time <= hi, ``news_category`` [N] ids (0 .. 63)
+    with ``categories`` = a 64-bit mask keeps the news whose category's bit is set; window
+    and mask are scalars or one value per impression.  Every mode above then draws from the
+    eligible news only."""
     if diversify is None and pool is not None:
         raise ValueError("get_top_k_recommendations: pool needs diversify")
     if explain is not None and not 1 <= int(explain) <= 8:
@@ -180,28 +187,34 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
                   dtype=dtype)
     n = len(history_len_list)
     eng.load_impressions(history_rev_index, history_len_list, np.zeros(0, np.int32), np.zeros(n, np.int32))
+    flt = {}
+    if time_window is not None or categories is not None:
+        eng.set_catalogue(news_time=news_time, news_cat=news_category)
+        flt = {"time_window": time_window, "categories": categories}
     why = {}
     if explain is not None:
-        idx, scores, why_news, why_val = eng.recommend_explained(k, top=int(explain), lam=diversify,
-                                                                 pool=64 if pool is None else pool,
-                                                                 exclude_history=exclude_history)
+        explained = eng.recommend_explained_filtered if flt else eng.recommend_explained
+        idx, scores, why_news, why_val = explained(k, top=int(explain), lam=diversify,
+                                                   pool=64 if pool is None else pool,
+                                                   exclude_history=exclude_history, **flt)
         why = {"why_news": _host(why_news), "why_share": _host(why_val)}
         if diversify is None:
             return {"news_index": _host(idx), "scores": _host(scores), **why}
     if diversify is not None:
         idx, scores, ild, plain = eng.recommend_diverse(k, diversify, pool=64 if pool is None else pool,
                                                         exclude_history=exclude_history, want_ild=True,
-                                                        want_plain=True)
+                                                        want_plain=True, **flt)
         return {"news_index": _host(idx), "scores": _host(scores), "ild": _host(ild), "plain_scores": _host(plain),
                 **why}
-    idx, scores = eng.recommend(k, exclude_history=exclude_history)
+    idx, scores = eng.recommend(k, exclude_history=exclude_history, **flt)
     return {"news_index": _host(idx), "scores": _host(scores)}
 
 
 def get_full_table_ranks(history_rev_index: np.ndarray, history_len_list: np.ndarray, target_index: np.ndarray,
                          target_len_list: np.ndarray, news_embeddings: torch.Tensor, attention_model: torch.nn.Module,
                          exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
-                         dtype=None) -> dict:
+                         dtype=None, news_time=None, news_category=None, time_window=None,
+                         categories=None) -> dict:
     """Where the given news stand among ALL news of the table for each impression's
     user: ``{"ranks": int32 [T]}`` on the host, in the order of ``target_index``
     (``target_len_list[i]`` rows of ``news_embeddings`` for impression i, e.g. its
@@ -216,13 +229,19 @@ def get_full_table_ranks(history_rev_index: np.ndarray, history_len_list: np.nda
     The reference has no counterpart: its AUC / MRR / nDCG are taken over the handful
     of candidates an impression lists.  This is PoolScoreEngine.rank_targets (the
     users x table MFMA product of the top-K path with a counting epilogue,
-    include/newsrec_fullrank.h)."""
+    include/newsrec_fullrank.h).  ``news_time`` / ``news_category`` / ``time_window`` /
+    ``categories`` are get_top_k_recommendations' catalogue filters: only the eligible news
+    are counted, and a target its impression's filter leaves out gets -1."""
     eng = _engine(attention_model, news_embeddings, query_news_embeddings if isinstance(query_news_embeddings,
                                                                                         torch.Tensor) else None,
                   dtype=dtype)
     n = len(history_len_list)
     eng.load_impressions(history_rev_index, history_len_list, np.zeros(0, np.int32), np.zeros(n, np.int32))
-    return {"ranks": _host(eng.rank_targets(target_index, target_len_list, exclude_history=exclude_history))}
+    flt = {}
+    if time_window is not None or categories is not None:
+        eng.set_catalogue(news_time=news_time, news_cat=news_category)
+        flt = {"time_window": time_window, "categories": categories}
+    return {"ranks": _host(eng.rank_targets(target_index, target_len_list, exclude_history=exclude_history, **flt))}
 
 
 def get_embeddings(model_path: str, news_list: Iterable[str], news_text_dict: dict[str, str]):

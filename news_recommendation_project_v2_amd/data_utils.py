@@ -255,6 +255,46 @@ def distinct_segments(idx: np.ndarray, lens: np.ndarray):
     return group, first
 
 
+def catalogue_first_seen(impression_time: np.ndarray, hist_idx: np.ndarray, hist_len: np.ndarray,
+                         cand_idx: np.ndarray, cand_len: np.ndarray, n_news: int) -> np.ndarray:
+    """int32 [n_news]: for each news the smallest time of an impression that lists it as a
+    candidate or carries it in its history -- the moment the catalogue is known to hold it
+    (the ``news_time`` of PoolScoreEngine.set_catalogue for as-of retrieval).  A news that
+    appears nowhere gets INT32_MAX, so no window ever contains it."""
+    t = np.asarray(impression_time, dtype=np.int32)
+    first = np.full(int(n_news), np.iinfo(np.int32).max, dtype=np.int32)
+    for idx, lens in ((hist_idx, hist_len), (cand_idx, cand_len)):
+        lens = np.asarray(lens, dtype=np.int64)
+        if len(lens) != len(t):
+            raise ValueError("Number of rows should be consistent")
+        idx = np.asarray(idx, dtype=np.int64)
+        if int(lens.sum()) != len(idx):
+            raise ValueError(f"lengths sum to {int(lens.sum())} but {len(idx)} indices were given")
+        if len(idx) and (idx.min() < 0 or idx.max() >= n_news):
+            raise IndexError(f"news index outside the {n_news} news")
+        np.minimum.at(first, idx, np.repeat(t, lens))
+    return first
+
+
+MIND_TIME_FORMAT = "%m/%d/%Y %I:%M:%S %p"  # the Time column of behaviors.tsv: 11/15/2019 8:55:22 AM
+
+
+def read_behavior_times(source, origin=None):
+    """The Time column of a MIND behaviours file (tab-separated, no header: ImpressionID,
+    UserID, Time, History, Impressions; a path or an open text file): (ImpressionID int64
+    [I], int32 [I] seconds since the split's first impression -- or since ``origin``, a
+    pandas Timestamp, when given)."""
+    import pandas as pd
+    df = pd.read_csv(source, sep="\t", header=None, usecols=[0, 2], names=["ImpressionID", "Time"],
+                     dtype={"ImpressionID": np.int64, "Time": str})
+    when = pd.to_datetime(df["Time"], format=MIND_TIME_FORMAT)
+    start = when.min() if origin is None else origin
+    secs = np.asarray((when - start).dt.total_seconds(), dtype=np.float64)
+    if len(secs) and (secs.min() < np.iinfo(np.int32).min or secs.max() > np.iinfo(np.int32).max):
+        raise ValueError("behaviour times span more than int32 seconds")
+    return df["ImpressionID"].to_numpy(dtype=np.int64), np.round(secs).astype(np.int32)
+
+
 def rank_group_preds(pred_scores: np.ndarray, imp_counts: np.ndarray) -> np.ndarray:
     """Per-impression dense descending ranks (data_utils.py:414-415), computed by
     the HIP kernel ``nr_dense_rank`` and grouped into an object array of int64

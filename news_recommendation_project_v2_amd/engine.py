@@ -78,6 +78,20 @@ def _upload(x, dev: torch.device, dtype: Optional[torch.dtype] = None) -> torch.
     return (t if dtype is None or t.dtype == dtype else t.to(dtype)).contiguous()
 
 
+class _Queries:
+    """The distinct (history, time window, category mask) tuples of the loaded impressions
+    under a catalogue filter: retrieval and ranks run once per query."""
+
+    def __init__(self, user: np.ndarray, sel: np.ndarray, lo, hi, mask, dev):
+        self.n = len(user)
+        self.user_host, self.sel_host = user, sel
+        self.user = _upload(user.astype(np.int64), dev)  # the query's pooled user row
+        self.sel = _upload(sel.astype(np.int64), dev)    # the impression's query
+        self.lo = None if lo is None else _upload(lo, dev)
+        self.hi = None if hi is None else _upload(hi, dev)
+        self.mask = None if mask is None else _upload(mask, dev)
+
+
 class PoolScoreEngine:
     def __init__(self, model: torch.nn.Module, dtype: torch.dtype = torch.float32,
                  device: Optional[torch.device] = None):
@@ -92,6 +106,8 @@ class PoolScoreEngine:
         self.hist_table = None
         self._ws = None
         self._users = None  # f32 [distinct histories, D], reused across steps
+        self.news_time = None  # int32 [N] / uint8 [N]: set_catalogue
+        self.news_cat = None
 
     # ------------------------------------------------------------ inputs
     def load_news(self, news_embeddings: torch.Tensor, query_news_embeddings: Optional[torch.Tensor] = None):
@@ -103,6 +119,84 @@ class PoolScoreEngine:
             self.hist_src = self.cand_table
         self._check_rows()
         return self
+
+    def set_catalogue(self, news_time=None, news_cat=None):
+        """Per-news attributes for the catalogue filters of recommend, recommend_diverse,
+        recommend_explained and rank_targets: ``news_time`` int32 [N] (any unit; e.g. the
+        time a news was first seen) and ``news_cat`` [N] category ids (0 .. 63 can be asked
+        for; 64 .. 255 never match).  None drops an attribute."""
+        n = None if self.cand_table is None else self.cand_table.shape[0]
+        up = {}
+        for name, arr, dt in (("news_time", news_time, np.int32), ("news_cat", news_cat, np.uint8)):
+            if arr is None:
+                up[name] = None
+                continue
+            a = np.asarray(arr)
+            if a.ndim != 1 or (n is not None and len(a) != n):
+                raise ValueError(f"{name} must have one entry per news" + ("" if n is None else f" ({n})"))
+            if not np.issubdtype(a.dtype, np.integer) or (len(a) and (a.min() < np.iinfo(dt).min
+                                                                     or a.max() > np.iinfo(dt).max)):
+                raise ValueError(f"{name} must be integers in the range of {np.dtype(dt).name}")
+            up[name] = _upload(np.ascontiguousarray(a, dtype=dt), self.device)
+        self.news_time, self.news_cat = up["news_time"], up["news_cat"]
+        return self
+
+    def _queries(self, time_window, categories) -> Optional[_Queries]:
+        """None without a filter argument (today's paths run), else the distinct queries.
+        ``time_window`` = (lo, hi), ``categories`` = a 64-bit mask; each a scalar or one
+        value per impression."""
+        if time_window is None and categories is None:
+            return None
+        n = self.n_imp
+        lo = hi = mask = None
+        keys = [self.user_idx.cpu().numpy().astype(np.int64) if self.user_idx is not None
+                else np.arange(n, dtype=np.int64)]
+        if time_window is not None:
+            if self.news_time is None:
+                raise ValueError("time_window needs set_catalogue(news_time=...)")
+            lo_in, hi_in = time_window
+            lo = np.broadcast_to(np.asarray(lo_in, dtype=np.int64), (n,))
+            hi = np.broadcast_to(np.asarray(hi_in, dtype=np.int64), (n,))
+            i32 = np.iinfo(np.int32)
+            lo, hi = np.clip(lo, i32.min, i32.max).astype(np.int32), np.clip(hi, i32.min, i32.max).astype(np.int32)
+            keys += [lo.astype(np.int64), hi.astype(np.int64)]
+        if categories is not None:
+            if self.news_cat is None:
+                raise ValueError("categories needs set_catalogue(news_cat=...)")
+            # Python ints, int64 or uint64 arrays: the same 64 bits, carried as int64
+            m = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in np.asarray(categories).reshape(-1).tolist()],
+                         dtype=np.uint64).view(np.int64)
+            mask = np.ascontiguousarray(np.broadcast_to(m, (n,)))
+            keys.append(mask)
+        if self.news_time is not None and self.news_time.numel() != self.cand_table.shape[0] or (
+                self.news_cat is not None and self.news_cat.numel() != self.cand_table.shape[0]):
+            raise ValueError("the catalogue attributes must have one entry per news")
+        if n == 0:
+            e = np.zeros(0, np.int64)
+            return _Queries(e, e, lo, hi, mask, self.device)
+        _, first, sel = np.unique(np.stack(keys, axis=1), axis=0, return_index=True, return_inverse=True)
+        sel = np.asarray(sel).reshape(-1)
+        pick = lambda a: None if a is None else np.ascontiguousarray(a[first])
+        return _Queries(keys[0][first], sel, pick(lo), pick(hi), pick(mask), self.device)
+
+    def _query_block(self, q: _Queries, users, hidx, hoff, a: int, b: int, exclude_history: bool):
+        """Queries [a, b): their pooled rows gathered (f32, so a block bounds them), their
+        exclusion CSR gathered from the histories, and the filter tensors of the ops call."""
+        qu = q.user[a:b]
+        eidx = eoff = None
+        if exclude_history:
+            ln = hoff[qu + 1] - hoff[qu]
+            eoff = torch.zeros(b - a + 1, dtype=torch.int64, device=self.device)
+            torch.cumsum(ln, 0, out=eoff[1:])
+            total = int(eoff[-1])
+            pos = (torch.arange(total, dtype=torch.int64, device=self.device)
+                   + torch.repeat_interleave(hoff[qu] - eoff[:-1], ln, output_size=total))
+            eidx = hidx[pos] if total else torch.zeros(0, dtype=torch.int32, device=self.device)
+        flt = dict(news_time=self.news_time if q.lo is not None else None,
+                   time_lo=None if q.lo is None else q.lo[a:b], time_hi=None if q.hi is None else q.hi[a:b],
+                   news_cat=self.news_cat if q.mask is not None else None,
+                   cat_mask=None if q.mask is None else q.mask[a:b])
+        return users[qu], eidx, eoff, flt
 
     def load_impressions(self, hist_idx, hist_len, cand_idx, cand_len, dedupe: Optional[bool] = None):
         """Upload the CSR index arrays.  ``dedupe`` (default: automatic) pools
@@ -203,9 +297,11 @@ class PoolScoreEngine:
         self.inv_norms()
         return self.pool_score(want_users=want_users, scores=scores)
 
-    def _recommend_distinct(self, k: int, exclude_history: bool, user_block: Optional[int]):
+    def _recommend_distinct(self, k: int, exclude_history: bool, user_block: Optional[int],
+                            q: Optional[_Queries] = None):
         """recommend's lists per DISTINCT history (the deduplicated CSR when
-        load_impressions built it, else one per impression): (idx [n_u, k], scores [n_u, k])."""
+        load_impressions built it, else one per impression): (idx [n_u, k], scores [n_u, k]).
+        Under a catalogue filter ``q``: per distinct query, [q.n, k]."""
         self.hist_table = self.transform(out=self.hist_table)
         self.inv_norms()
         if self.user_idx is not None:
@@ -213,16 +309,24 @@ class PoolScoreEngine:
         else:
             hidx, hoff = self.hist_idx, self.hist_off
         n_u = hoff.numel() - 1
-        idx = torch.empty((n_u, k), dtype=torch.int32, device=self.device)
-        scores = torch.empty((n_u, k), dtype=torch.float32, device=self.device)
-        if n_u == 0:
+        n_rows = n_u if q is None else q.n
+        idx = torch.empty((n_rows, k), dtype=torch.int32, device=self.device)
+        scores = torch.empty((n_rows, k), dtype=torch.float32, device=self.device)
+        if n_rows == 0:
             return idx, scores
         if self._users is None or self._users.shape[0] != n_u:
             self._users = torch.empty((n_u, 1024), dtype=torch.float32, device=self.device)
         users = ops.pool_users(self.pooler, self.hist_table, hidx, hoff, out=self._users)
-        blk = n_u if not user_block else max(1, min(int(user_block), n_u))
+        blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
         need = ops.topk_workspace_bytes(self.dtype, blk, self.cand_table.shape[0], k)
         self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, self.device)
+        if q is not None:  # users are pooled once per distinct history, searched once per distinct query
+            for a in range(0, q.n, blk):
+                b = min(a + blk, q.n)
+                rows, eidx, eoff, flt = self._query_block(q, users, hidx, hoff, a, b, exclude_history)
+                ops.topk_users_filtered(rows, self.cand_table, self.cand_inv, k, excl_idx=eidx, excl_off=eoff,
+                                        out=(idx[a:b], scores[a:b]), workspace=self._topk_ws, **flt)
+            return idx, scores
         for u0 in range(0, n_u, blk):
             u1 = min(u0 + blk, n_u)
             eoff = None
@@ -235,7 +339,14 @@ class PoolScoreEngine:
                            out=(idx[u0:u1], scores[u0:u1]), workspace=self._topk_ws)
         return idx, scores
 
-    def recommend(self, k: int, exclude_history: bool = True, user_block: Optional[int] = None):
+    def _expansion(self, q: Optional[_Queries]) -> Optional[torch.Tensor]:
+        """Row of the distinct lists behind each impression (None: one list per impression)."""
+        if q is not None:
+            return q.sel
+        return None if self.user_idx is None else self.user_idx.long()
+
+    def recommend(self, k: int, exclude_history: bool = True, user_block: Optional[int] = None,
+                  time_window=None, categories=None):
         """The k best news of the WHOLE table per impression (ops.topk_users over the
         pooled users): (idx int32 [I, k], scores f32 [I, k]), score descending, ties by
         ascending row, (-1, -inf) where fewer than k rows are eligible; the scores are
@@ -243,15 +354,23 @@ class PoolScoreEngine:
         leaves an impression's own history out of its list.  Distinct histories are
         pooled and searched once (the deduplicated CSR when load_impressions built it).
         ``user_block`` bounds the workspace by running the users in blocks of that many
-        rows; the results do not depend on it."""
-        idx, scores = self._recommend_distinct(k, exclude_history, user_block)
-        if self.user_idx is not None and idx.shape[0]:
-            sel = self.user_idx.long()
+        rows; the results do not depend on it.
+
+        Catalogue filters (set_catalogue): ``time_window`` = (lo, hi) keeps the news with lo <=
+        news_time <= hi (inclusive; lo > hi is empty), ``categories`` = a 64-bit mask keeps
+        the news whose category's bit is set; each a scalar or one value per impression.
+        Users are still pooled once per distinct history; the table is searched once per
+        distinct (history, lo, hi, mask).  Without either argument nothing changes."""
+        q = self._queries(time_window, categories)
+        idx, scores = self._recommend_distinct(k, exclude_history, user_block, q)
+        sel = self._expansion(q)
+        if sel is not None and idx.shape[0]:
             return idx[sel], scores[sel]
         return idx, scores
 
     def recommend_diverse(self, k: int, lam: float, pool: int = 64, exclude_history: bool = True,
-                          user_block: Optional[int] = None, want_ild: bool = False, want_plain: bool = False):
+                          user_block: Optional[int] = None, want_ild: bool = False, want_plain: bool = False,
+                          time_window=None, categories=None):
         """recommend's lists re-ranked for diversity (ops.rerank_mmr, greedy MMR): the
         ``pool`` best news per distinct history are retrieved as recommend(pool) does,
         k of them are picked one at a time, each maximising lam * score - (1 - lam) *
@@ -261,25 +380,27 @@ class PoolScoreEngine:
         f32 [I, 2]: the intra-list diversity (mean 1 - cosine over the pairs) of
         recommend(k)'s list and of the returned one; with ``want_plain`` also recommend(k)'s
         scores f32 [I, k] (the pool's first k), for comparing the relevance given up.
-        lam = 1 returns recommend(k)."""
-        idx, scores, ild, pscores = self._diverse_distinct(k, lam, pool, exclude_history, user_block, want_ild)
+        lam = 1 returns recommend(k).  ``time_window`` / ``categories`` filter the retrieved pool
+        as in recommend; the re-ranking itself sees only that pool."""
+        q = self._queries(time_window, categories)
+        idx, scores, ild, pscores = self._diverse_distinct(k, lam, pool, exclude_history, user_block, want_ild, q)
         k = int(k)
-        if idx.shape[0] and self.user_idx is not None:
-            sel = self.user_idx.long()
+        sel = self._expansion(q)
+        if idx.shape[0] and sel is not None:
             idx, scores = idx[sel], scores[sel]
             ild = ild[sel] if want_ild else None
             pscores = pscores[sel] if want_plain else pscores
         return (idx, scores) + ((ild,) if want_ild else ()) + ((pscores[:, :k].contiguous(),) if want_plain else ())
 
     def _diverse_distinct(self, k: int, lam: float, pool: int, exclude_history: bool, user_block: Optional[int],
-                          want_ild: bool = False):
+                          want_ild: bool = False, q: Optional[_Queries] = None):
         """recommend_diverse's lists per DISTINCT history: (idx [n_u, k], scores [n_u, k], ild
         [n_u, 2] or None, the retrieved pool's scores [n_u, pool])."""
         k, pool = int(k), int(pool)
         if pool < k:
             raise ValueError(f"recommend_diverse: pool = {pool} < k = {k}")
         # lam = 1 keeps recommend's order: its list is the first k of any pool, so only k are retrieved
-        pidx, pscores = self._recommend_distinct(k if float(lam) == 1.0 else pool, exclude_history, user_block)
+        pidx, pscores = self._recommend_distinct(k if float(lam) == 1.0 else pool, exclude_history, user_block, q)
         n_u = pidx.shape[0]
         idx = torch.empty((n_u, k), dtype=torch.int32, device=self.device)
         scores = torch.empty((n_u, k), dtype=torch.float32, device=self.device)
@@ -326,11 +447,25 @@ class PoolScoreEngine:
         pad and past the history's length.  The lists are retrieved and explained once per
         distinct history (the deduplicated CSR when load_impressions built it) and only
         then expanded to the impressions; the result does not depend on that."""
+        return self.recommend_explained_filtered(k, top=top, lam=lam, pool=pool, exclude_history=exclude_history,
+                                                 user_block=user_block)
+
+    def recommend_explained_filtered(self, k: int, time_window=None, categories=None, top: int = 3,
+                                     lam: Optional[float] = None, pool: int = 64, exclude_history: bool = True,
+                                     user_block: Optional[int] = None):
+        """recommend_explained under recommend's catalogue filters ``time_window`` /
+        ``categories``: the filtered lists are expanded to the impressions first and explained
+        against each impression's own history.  Without a filter argument it is
+        recommend_explained itself."""
+        q = self._queries(time_window, categories)
         if lam is None:
-            idx, scores = self._recommend_distinct(int(k), exclude_history, user_block)
+            idx, scores = self._recommend_distinct(int(k), exclude_history, user_block, q)
         else:
-            idx, scores, _, _ = self._diverse_distinct(k, lam, pool, exclude_history, user_block)
-        if self.user_idx is not None:
+            idx, scores, _, _ = self._diverse_distinct(k, lam, pool, exclude_history, user_block, q=q)
+        if q is not None:
+            idx, scores = idx[q.sel].contiguous(), scores[q.sel].contiguous()
+            hidx, hoff = self.hist_idx, self.hist_off
+        elif self.user_idx is not None:
             hidx, hoff = self.uhist_idx, self.uhist_off
         else:
             hidx, hoff = self.hist_idx, self.hist_off
@@ -345,12 +480,13 @@ class PoolScoreEngine:
             why = torch.where(pos >= 0, hidx[row], torch.full_like(pos, -1))
         else:
             why = torch.full_like(pos, -1)
-        if self.user_idx is not None:
+        if q is None and self.user_idx is not None:
             sel = self.user_idx.long()
             idx, scores, why, val = idx[sel], scores[sel], why[sel], val[sel]
         return idx, scores, why, val
 
-    def rank_targets(self, tgt_idx, tgt_len, exclude_history: bool = True, user_block: Optional[int] = None):
+    def rank_targets(self, tgt_idx, tgt_len, exclude_history: bool = True, user_block: Optional[int] = None,
+                     time_window=None, categories=None):
         """Full-table ranks of given news per impression (ops.rank_targets over the pooled
         users): int32 [T] in the caller's target order, ``tgt_len[i]`` targets (rows of the
         news table, e.g. the clicked candidates) for impression i.  A rank is the number
@@ -359,7 +495,9 @@ class PoolScoreEngine:
         outside the table.  The targets with rank < k are exactly recommend(k)'s rows.
         Distinct histories are pooled once: with the deduplicated CSR the impressions'
         targets are grouped under their distinct user (a stable sort) and the ranks
-        scattered back.  ``user_block`` bounds the workspace; the results depend on neither."""
+        scattered back.  ``user_block`` bounds the workspace; the results depend on neither.
+        ``time_window`` / ``categories`` (as in recommend) count only the eligible news, and a
+        target that its impression's filter leaves out gets -1."""
         tgt_idx = np.ascontiguousarray(tgt_idx, dtype=np.int32)
         tgt_len = np.asarray(tgt_len, dtype=np.int64)
         if len(tgt_len) != self.n_imp:
@@ -371,33 +509,41 @@ class PoolScoreEngine:
             hidx, hoff = self.uhist_idx, self.uhist_off
         else:
             hidx, hoff = self.hist_idx, self.hist_off
+        q = self._queries(time_window, categories)
         n_u = hoff.numel() - 1
         n_t = len(tgt_idx)
         ranks = torch.empty(n_t, dtype=torch.int32, device=self.device)
         if n_t == 0 or n_u == 0:
             return ranks
+        n_rows = n_u if q is None else q.n  # the rows the kernel sees: distinct histories, or distinct queries
         order = None
-        if self.user_idx is not None:  # the impressions' targets under their distinct user, in impression order
-            owner = np.repeat(self.user_idx.cpu().numpy().astype(np.int64), tgt_len)
+        if q is not None or self.user_idx is not None:  # the impressions' targets under their distinct row, in impression order
+            owner = np.repeat(q.sel_host if q is not None else self.user_idx.cpu().numpy().astype(np.int64), tgt_len)
             order = np.argsort(owner, kind="stable")
             tgt_idx = tgt_idx[order]
-            toff = lengths_to_offsets(np.bincount(owner, minlength=n_u))
+            toff = lengths_to_offsets(np.bincount(owner, minlength=n_rows))
         else:
             toff = lengths_to_offsets(tgt_len)
         if self._users is None or self._users.shape[0] != n_u:
             self._users = torch.empty((n_u, 1024), dtype=torch.float32, device=self.device)
         users = ops.pool_users(self.pooler, self.hist_table, hidx, hoff, out=self._users)
         tidx_d = _upload(tgt_idx, self.device)
-        blk = n_u if not user_block else max(1, min(int(user_block), n_u))
+        blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
         n_news = self.cand_table.shape[0]
-        most = max(int(toff[min(u0 + blk, n_u)] - toff[u0]) for u0 in range(0, n_u, blk))
+        most = max(int(toff[min(u0 + blk, n_rows)] - toff[u0]) for u0 in range(0, n_rows, blk))
         need = ops.rank_targets_workspace_bytes(self.dtype, blk, n_news, most)
         self._rank_ws = ops.grow_workspace(getattr(self, "_rank_ws", None), max(need, 256), self.device)
         sorted_ranks = ranks if order is None else torch.empty_like(ranks)
-        for u0 in range(0, n_u, blk):
-            u1 = min(u0 + blk, n_u)
+        for u0 in range(0, n_rows, blk):
+            u1 = min(u0 + blk, n_rows)
             a, b = int(toff[u0]), int(toff[u1])
             if a == b:
+                continue
+            if q is not None:
+                rows, eidx, eoff, flt = self._query_block(q, users, hidx, hoff, u0, u1, exclude_history)
+                ops.rank_targets_filtered(rows, self.cand_table, self.cand_inv, tidx_d[a:b],
+                                          _upload(toff[u0:u1 + 1] - a, self.device), excl_idx=eidx, excl_off=eoff,
+                                          out=sorted_ranks[a:b], workspace=self._rank_ws, **flt)
                 continue
             eidx = eoff = None
             if exclude_history:

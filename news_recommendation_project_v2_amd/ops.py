@@ -310,16 +310,31 @@ def topk_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) 
     return need
 
 
+def _check_filter(what: str, n_users: int, n_news: int, news_time, time_lo, time_hi, news_cat, cat_mask) -> list:
+    """Host checks of a catalogue filter (include/newsrec_filter.h); the five pointers in
+    the C order.  The uint64 masks travel as int64 tensors (the same 64 bits)."""
+    if (news_time is None) != (time_lo is None) or (news_time is None) != (time_hi is None):
+        raise _lib.NewsRecHIPError(f"{what}: news_time, time_lo and time_hi go together")
+    if (news_cat is None) != (cat_mask is None):
+        raise _lib.NewsRecHIPError(f"{what}: news_cat and cat_mask go together")
+    for t, name, dt, n in ((news_time, "news_time", torch.int32, n_news), (time_lo, "time_lo", torch.int32, n_users),
+                           (time_hi, "time_hi", torch.int32, n_users), (news_cat, "news_cat", torch.uint8, n_news),
+                           (cat_mask, "cat_mask", torch.int64, n_users)):
+        if t is not None and (t.dtype != dt or t.dim() != 1 or t.numel() != n or not t.is_contiguous()):
+            raise _lib.NewsRecHIPError(f"{what}: {name} must be contiguous {dt} [{n}]")
+    return [_ptr(news_time), _ptr(time_lo), _ptr(time_hi), _ptr(news_cat), _ptr(cat_mask)]
+
+
 def topk_users(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int,
                excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
-               out=None, workspace: Optional[torch.Tensor] = None):
+               out=None, workspace: Optional[torch.Tensor] = None, _filter=None):
     """The k best rows of ``cand_table`` per user row (nr_topk_users): returns
     (idx int32 [U, k], scores f32 [U, k]), score descending, ties by ascending row,
     a short tail as (-1, -inf); the scores are score_users' bit for bit.  The CSR
     (excl_idx int32, excl_off int64 [U + 1]) lists rows a user must not get; its
     entries are range-checked here (one small sync).  ``out`` = (idx, scores) to
     write into."""
-    dev = _dev(users, cand_table, cand_inv_norm, excl_idx, excl_off, workspace, *(out or ()))
+    dev = _dev(users, cand_table, cand_inv_norm, excl_idx, excl_off, workspace, *(out or ()), *(_filter or ()))
     if users.dtype != torch.float32 or users.dim() != 2 or not users.is_contiguous():
         raise _lib.NewsRecHIPError("topk_users: users must be contiguous f32 [U, D]")
     n_users, dim = users.shape
@@ -352,9 +367,30 @@ def topk_users(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: tor
             raise _lib.NewsRecHIPError(f"topk_users: out must be contiguous (int32, f32) of shape {(n_users, k)}")
     dt = _dtype(cand_table, "cand_table")
     ws = grow_workspace(workspace, topk_workspace_bytes(cand_table.dtype, n_users, n_news, k), dev)
+    if _filter is not None:
+        fptr = _check_filter("topk_users_filtered", n_users, n_news, *_filter)
+        _lib.call("nr_topk_users_filtered", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
+                  _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, k, _ptr(idx), _ptr(scores), _ptr(ws),
+                  ws.numel(), _stream(dev))
+        return idx, scores
     _lib.call("nr_topk_users", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm),
               _ptr(excl_idx), _ptr(excl_off), k, _ptr(idx), _ptr(scores), _ptr(ws), ws.numel(), _stream(dev))
     return idx, scores
+
+
+def topk_users_filtered(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int,
+                        news_time: Optional[torch.Tensor] = None, time_lo: Optional[torch.Tensor] = None,
+                        time_hi: Optional[torch.Tensor] = None, news_cat: Optional[torch.Tensor] = None,
+                        cat_mask: Optional[torch.Tensor] = None, excl_idx: Optional[torch.Tensor] = None,
+                        excl_off: Optional[torch.Tensor] = None, out=None, workspace: Optional[torch.Tensor] = None):
+    """topk_users under a catalogue filter (nr_topk_users_filtered): row c is eligible for
+    user u when it is not excluded, ``time_lo[u] <= news_time[c] <= time_hi[u]`` (int32 [N],
+    int32 [U]; both bounds inclusive, lo > hi is an empty window) and bit ``news_cat[c]``
+    (uint8 [N]; 64 or more is never eligible) of ``cat_mask[u]`` (int64 [U], read as
+    uint64) is set.  Either pair may be left out; with neither the result is topk_users'
+    bit for bit.  Everything else is topk_users' contract with "eligible" so defined."""
+    return topk_users(users, cand_table, cand_inv_norm, k, excl_idx=excl_idx, excl_off=excl_off, out=out,
+                      workspace=workspace, _filter=(news_time, time_lo, time_hi, news_cat, cat_mask))
 
 
 def rank_targets_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, n_targets: int) -> int:
@@ -370,7 +406,7 @@ def rank_targets_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, 
 def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, tgt_idx: torch.Tensor,
                  tgt_off: torch.Tensor, excl_idx: Optional[torch.Tensor] = None,
                  excl_off: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 workspace: Optional[torch.Tensor] = None, _filter=None) -> torch.Tensor:
     """Full-table ranks of target rows (nr_rank_targets): for the targets
     tgt_idx[tgt_off[u]:tgt_off[u + 1]] (int32, int64 [U + 1]) of user row u, int32 [T]
     with the number of eligible rows of ``cand_table`` that beat the target in top-K's
@@ -379,7 +415,8 @@ def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: t
     rank < k are exactly the rows topk_users returns.  The exclusion CSR is as
     topk_users takes it; its entries and the target offsets are checked here (one
     small sync).  ``out`` = int32 [T] to write into."""
-    dev = _dev(users, cand_table, cand_inv_norm, tgt_idx, tgt_off, excl_idx, excl_off, workspace, out)
+    dev = _dev(users, cand_table, cand_inv_norm, tgt_idx, tgt_off, excl_idx, excl_off, workspace, out,
+               *(_filter or ()))
     if users.dtype != torch.float32 or users.dim() != 2 or not users.is_contiguous():
         raise _lib.NewsRecHIPError("rank_targets: users must be contiguous f32 [U, D]")
     n_users, dim = users.shape
@@ -414,12 +451,33 @@ def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: t
         raise _lib.NewsRecHIPError(f"rank_targets: out must be contiguous int32 of shape {(n_tgt,)}")
     dt = _dtype(cand_table, "cand_table")
     ws = grow_workspace(workspace, max(rank_targets_workspace_bytes(cand_table.dtype, n_users, n_news, n_tgt), 256), dev)
+    fptr = None if _filter is None else _check_filter("rank_targets_filtered", n_users, n_news, *_filter)
     if n_tgt == 0:
+        return out
+    if fptr is not None:
+        _lib.call("nr_rank_targets_filtered", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
+                  _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, n_tgt, _ptr(tgt_idx), _ptr(tgt_off),
+                  _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
         return out
     _lib.call("nr_rank_targets", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm),
               _ptr(excl_idx), _ptr(excl_off), n_tgt, _ptr(tgt_idx), _ptr(tgt_off), _ptr(out), _ptr(ws), ws.numel(),
               _stream(dev))
     return out
+
+
+def rank_targets_filtered(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor,
+                          tgt_idx: torch.Tensor, tgt_off: torch.Tensor, news_time: Optional[torch.Tensor] = None,
+                          time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
+                          news_cat: Optional[torch.Tensor] = None, cat_mask: Optional[torch.Tensor] = None,
+                          excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rank_targets under topk_users_filtered's catalogue filter (nr_rank_targets_filtered):
+    only eligible rows are counted, and a target that is itself ineligible -- excluded,
+    outside its user's window or of an unwanted category -- gets -1.  For k <= 64 the
+    targets with rank < k are exactly the rows topk_users_filtered returns."""
+    return rank_targets(users, cand_table, cand_inv_norm, tgt_idx, tgt_off, excl_idx=excl_idx, excl_off=excl_off,
+                        out=out, workspace=workspace, _filter=(news_time, time_lo, time_hi, news_cat, cat_mask))
 
 
 def rerank_mmr(cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, list_idx: torch.Tensor, list_rel: torch.Tensor,

@@ -104,6 +104,19 @@ def mind_impressions(n_news: int, n_imp: int, seed: int = 1234, mean_hist: float
     return Impressions(n_news, hist_idx, hist_len, cand_idx, cand_len, labels)
 
 
+def catalogue_attributes(n_news: int, n_imp: int, seed: int = 1234, n_categories: int = 18,
+                         span_seconds: int = 7 * 86400):
+    """Seeded impression times and news categories for the catalogue filters:
+    (impression_time int32 [n_imp], ascending seconds over ``span_seconds`` as a behaviours
+    file lists them; news_category uint8 [n_news] in [0, n_categories)).  They come from a
+    generator stream of their own, so mind_impressions' arrays for the same seed are
+    untouched by asking for them."""
+    rng = np.random.default_rng([int(seed), 0xCA7A106])
+    when = np.sort(rng.integers(0, int(span_seconds), int(n_imp))).astype(np.int32)
+    cats = rng.integers(0, int(n_categories), int(n_news)).astype(np.uint8)
+    return when, cats
+
+
 def mind_shaped(name: str = "mind_large_dev", seed: int = 1234, **kw) -> Impressions:
     n_news, n_imp = SHAPES[name]
     return mind_impressions(n_news, n_imp, seed=seed, **kw)

@@ -8,6 +8,7 @@ has no counterpart -- it only scores the candidates an impression lists).
     python scripts/recommend.py --synthetic --evaluate [--ks 10,64,100]
     python scripts/recommend.py --synthetic --diversify 0.7 [--pool 64]
     python scripts/recommend.py --synthetic --explain 3
+    python scripts/recommend.py --synthetic --evaluate --as-of [--fresh 48] [--categories 0,3,7]
 
 Prints one JSON line per run and writes {out-dir}/recommendations.npy: an int32
 [I, K] array of rows of the split's news list (-1 where fewer than K are eligible).
@@ -26,6 +27,16 @@ news list, -1 where there are fewer) whose clicks contributed most to its score,
 {out-dir}/recommendations_why_share.npy with those contributions; the JSON line gains
 evaluation.explanation_metrics (the mean share of a score carried by its largest and by
 its T largest contributions, and how often the largest one is negative).
+--as-of makes retrieval and --evaluate time-aware: a news enters the catalogue at the time
+of the first impression that lists it or carries it in a history
+(data_utils.catalogue_first_seen), and each impression sees only the news that entered at
+or before its own time; --fresh HOURS also drops the news that entered more than HOURS
+before it.  An impression's clicked candidates are always eligible under --as-of, because
+the impression itself lists them (not so under --fresh or --categories: those targets get
+rank -1 and count as misses).  --categories A,B,... keeps the news of those categories
+(names of data-dir/categories.json; ids with --synthetic).  The JSON line gains
+mean_eligible_news, the mean size of the catalogue an impression sees: it is nearly empty
+at the start of a split, which the metrics of the first impressions reflect.
 """
 from __future__ import annotations
 
@@ -49,6 +60,60 @@ from news_recommendation_project_v2_amd.modeling_utils import FinalAttention  # 
 from news_recommendation_project_v2_amd.pipeline import Pipeline  # noqa: E402
 
 
+def catalogue_filter(args, out, ctx) -> dict:
+    """get_top_k_recommendations' filter arguments for --as-of / --fresh / --categories ({} without them)."""
+    if not args.as_of and args.categories is None:
+        return {}
+    from news_recommendation_project_v2_amd import synthetic
+    from news_recommendation_project_v2_amd.data_utils import catalogue_first_seen, read_behavior_times
+    news_list = list(out["news_list"])
+    n_news, n_imp = len(news_list), len(out["history_len_list"])
+    flt = {}
+    if args.synthetic:
+        rows = np.array([int(str(n)[1:]) for n in news_list], dtype=np.int64)  # "N<id>" of synthetic.to_behaviors
+        when, cats = synthetic.catalogue_attributes(int(rows.max()) + 1, n_imp, seed=1234)
+        news_cat = cats[rows]
+    if args.as_of:
+        if not args.synthetic:
+            ids, secs = read_behavior_times(args.data_dir / "raw" / args.split / "behaviors.tsv")
+            at = dict(zip(ids.tolist(), secs.tolist()))
+            when = np.array([at[int(i)] for i in out["ImpressionID"]], dtype=np.int32)
+        flt["news_time"] = catalogue_first_seen(when, out["history_rev_ind_array"][0], out["history_len_list"],
+                                                out["impression_rev_ind_array"][0], out["impression_len_list"], n_news)
+        lo = (when.astype(np.int64) - int(round(args.fresh * 3600)) if args.fresh is not None
+              else np.full(n_imp, np.iinfo(np.int32).min, np.int64))
+        flt["time_window"] = (np.maximum(lo, np.iinfo(np.int32).min).astype(np.int32), when.astype(np.int32))
+    if args.categories is not None:
+        want = [c.strip() for c in args.categories.split(",") if c.strip()]
+        if args.synthetic:
+            ids = [int(c) for c in want]
+        else:
+            names = json.loads((args.data_dir / "categories.json").read_text())
+            ids = [int(names[c]) for c in want]
+            per_news = ctx.get("news_category", {})
+            news_cat = np.array([per_news.get(n, 255) for n in news_list], dtype=np.float64)
+            news_cat = np.where(np.isfinite(news_cat) & (news_cat >= 0) & (news_cat < 64), news_cat, 255).astype(np.uint8)
+        if any(not 0 <= c < 64 for c in ids):
+            raise SystemExit("--categories: only category ids 0 .. 63 can be asked for")
+        flt["news_category"] = np.asarray(news_cat, dtype=np.uint8)
+        flt["categories"] = np.array([sum(1 << c for c in set(ids))], dtype=np.uint64)
+    return flt
+
+
+def mean_eligible(flt: dict) -> float:
+    """Mean number of news inside an impression's window and mask (the exclusion of its own history aside)."""
+    ok = np.ones(len(flt["news_time"] if "news_time" in flt else flt["news_category"]), dtype=bool)
+    if "categories" in flt:
+        wanted = np.array([(int(flt["categories"][0]) >> c) & 1 for c in range(64)], dtype=bool)
+        ok &= (flt["news_category"] < 64) & wanted[np.minimum(flt["news_category"], 63)]
+        if "news_time" not in flt:
+            return float(ok.sum())
+    t = np.sort(flt["news_time"][ok].astype(np.int64))
+    lo, hi = flt["time_window"]
+    n = np.searchsorted(t, hi.astype(np.int64), "right") - np.searchsorted(t, lo.astype(np.int64), "left")
+    return float(np.maximum(n, 0).mean()) if len(n) else 0.0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pooler", choices=["final", "latent"], default="final")
@@ -70,9 +135,18 @@ def main():
     ap.add_argument("--pool", type=int, default=None, metavar="M", help="news retrieved before --diversify picks K (64)")
     ap.add_argument("--explain", type=int, default=None, metavar="T",
                     help="also write the T history news (1..8) that contributed most to each recommendation")
+    ap.add_argument("--as-of", action="store_true",
+                    help="each impression sees the news first seen at or before its own time (a clicked candidate "
+                         "is always eligible: its own impression lists it)")
+    ap.add_argument("--fresh", type=float, default=None, metavar="HOURS",
+                    help="with --as-of: only the news first seen in the last HOURS before the impression")
+    ap.add_argument("--categories", default=None, metavar="A,B,...",
+                    help="only news of these categories (names; ids with --synthetic)")
     args = ap.parse_args()
     if args.pool is not None and args.diversify is None:
         ap.error("--pool needs --diversify")
+    if args.fresh is not None and not args.as_of:
+        ap.error("--fresh needs --as-of")
 
     model = FinalAttention(1024, 4096) if args.pooler == "final" else LatentAttentionModel()
     ckpt = args.ckpt or Path("models") / ("final_attn" if args.pooler == "final" else "latent_attn") / "Epoch_5.pt"
@@ -97,6 +171,7 @@ def main():
         loader = LoadEmbeddingComponent(args.emb_dir or Path("new_embeddings"))
     out, _ = Pipeline(f"recommend_{args.split}", [("init_transform", TransformData()),
                                                   ("load_embedding", loader)]).transform(ctx)
+    flt = catalogue_filter(args, out, ctx)
     t0 = time.perf_counter()
     rec = dmh.get_top_k_recommendations(out["history_rev_ind_array"][0], out["history_len_list"],
                                         out["news_embeddings"], model, args.k,
@@ -104,7 +179,7 @@ def main():
                                         dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
                                         **({} if args.diversify is None else
                                            {"diversify": args.diversify, "pool": args.pool}),
-                                        **({} if args.explain is None else {"explain": args.explain}))
+                                        **({} if args.explain is None else {"explain": args.explain}), **flt)
     ms = (time.perf_counter() - t0) * 1e3
     idx, scores = rec["news_index"], rec["scores"]
     args.out_dir.mkdir(parents=True, exist_ok=True)
@@ -116,6 +191,9 @@ def main():
             "news": int(out["news_embeddings"].shape[0]), "filled": float(have.mean()) if idx.size else 1.0,
             "mean_top1_score": float(scores[:, 0][have[:, 0]].mean()) if have[:, :1].any() else None,
             "ms": round(ms, 1), "out": str(path)}
+    if flt:
+        line.update(as_of=args.as_of, fresh_hours=args.fresh, categories=args.categories,
+                    mean_eligible_news=mean_eligible(flt))
     if args.diversify is not None:
         from news_recommendation_project_v2_amd.evaluation import diversity_metrics
         line.update(diversify=args.diversify, pool=args.pool or 64)
@@ -138,7 +216,8 @@ def main():
         ranks = dmh.get_full_table_ranks(out["history_rev_ind_array"][0], out["history_len_list"],
                                          np.asarray(out["impression_rev_ind_array"][0])[clicked], tgt_len,
                                          out["news_embeddings"], model, exclude_history=not args.keep_history,
-                                         dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)["ranks"]
+                                         dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
+                                         **flt)["ranks"]
         line["evaluate_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
         metrics = retrieval_metrics(ranks, tgt_len, ks=[int(k) for k in args.ks.split(",")])
         line["impressions_evaluated"] = metrics.pop("impressions")  # ("impressions" stays the number recommended for)
