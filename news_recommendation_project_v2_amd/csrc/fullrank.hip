@@ -162,26 +162,16 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
   __shared__ int tc_s[TCAP * TS];      //   and counters (both threads of a user add to one)
   __shared__ __attribute__((aligned(16))) int32_t ft_s[FILT ? ATTR_TIME_WORDS : 4];  // the tile's news times
   __shared__ uint32_t fc_s[FILT ? ATTR_CAT_WORDS : 1];                                //   and categories
-  float* T = reinterpret_cast<float*>(smem);
 
-  const int tid = threadIdx.x;
-  const int64_t m0 = (int64_t)blockIdx.x * TS;
-  const int64_t c0 = (int64_t)blockIdx.y * span_rows;
-  const int64_t c1 = min(N, c0 + span_rows);
-  const int ntiles = (int)((c1 - c0 + TS - 1) / TS);
   const float NINF = -__builtin_inff();
-
-  ScoreTile<TI> st(smem, cinv_s, users, m0, U);
-
+  ChunkWalk<TI, FILT> w(smem, cinv_s, ex_s, ov_mask, ft_s, fc_s, U, N, users, tab, ldt, cinv, excl_idx, excl_off, flt,
+                        span_rows);
   // threads 2u and 2u + 1 serve user u of the block: 64 scores of a tile each
-  const int su = tid >> 1, sh = tid & 1;
-  const bool live = m0 + su < U;
-  Excluded ex(ex_s, ov_mask, excl_idx, excl_off, m0, live, c0);
-  FilterOf<FILT> el(ft_s, fc_s, flt, m0, live);
+  const int su = w.su, sh = w.sh;
   int64_t t0 = 0, t1 = 0;  // the user's targets (clamped into [0, T])
-  if (live) {
-    t0 = clamp64(tgt_off[m0 + su], 0, Tn);
-    t1 = clamp64(tgt_off[m0 + su + 1], t0, Tn);
+  if (w.live) {
+    t0 = clamp64(tgt_off[w.m0 + su], 0, Tn);
+    t1 = clamp64(tgt_off[w.m0 + su + 1], t0, Tn);
   }
   // the first TCAP targets of the user stay in LDS for the whole walk (the two threads stage
   // alternate slots; read after the first tile's barriers)
@@ -192,22 +182,12 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
     tc_s[j * TS + su] = 0;
   }
 
-  auto rows_from = [&](int64_t n0) __attribute__((always_inline)) {
-    return [=](int r) __attribute__((always_inline)) { return min(n0 + r, N - 1); };
-  };
-  st.gload(tab, ldt, rows_from(c0), 0);
-  for (int tile = 0; tile < ntiles; ++tile) {
-    const int64_t n0 = c0 + (int64_t)tile * TS;
-    if (tile == 0 || n0 == ex.cb + kChunk) ex.chunk_start(n0);
-    const int nvalid = (int)min((int64_t)TS, N - n0);
-    if (tid < TS) cinv_s[tid] = tid < nvalid ? cinv[n0 + tid] : 0.f;
-    if constexpr (FILT) el.stage(n0, N);
-    st.scores(tab, ldt, rows_from(n0), tile + 1 < ntiles, rows_from(n0 + TS), nvalid);
-    ex.knock_out_overflow(T, m0, n0);
+  // (the epilogue changes nothing it captures: by value, so its operands stay the kernel's own values)
+  w.run([=, &w](int64_t n0, float* T) __attribute__((always_inline)) {
     // ---- -inf over the user's staged excluded rows that fall in this tile (idempotent under duplicates)
-    if (sh == 0 && ex.xn <= XCAP) {
-      const int base = (int)(n0 - ex.cb);
-      for (int i = 0; i < ex.xn; ++i) {
+    if (sh == 0 && w.ex.xn <= XCAP) {
+      const int base = (int)(n0 - w.ex.cb);
+      for (int i = 0; i < w.ex.xn; ++i) {
         const int d = (int)ex_s[i * TS + su] - base;
         if (d >= 0 && d < TS) T[su * TLD + d] = NINF;
       }
@@ -216,7 +196,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
     // own 64 columns (stores of -inf only, like the ones above: no store can undo another)
     if constexpr (FILT) {
       uint32_t elo, ehi;
-      el.rows64(sh, elo, ehi);
+      w.el.rows64(sh, elo, ehi);
       float* row = T + su * TLD + 64 * sh;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -253,8 +233,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
         if (sh == 0 && c) atomicAdd(&rank[j], c);
       }
     }
-    __syncthreads();  // the next tile's operands overwrite the score tile
-  }
+  });
   // (the closing barrier of the last tile is behind every LDS add)
   for (int j = sh; j < nl; j += 2) {
     const int c = tc_s[j * TS + su];
@@ -263,28 +242,21 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
 }
 
 struct RankLayout {
-  int64_t nchunks, ub, tsel, total;
+  int64_t tsel, total;  // (the NR_BF16 users sit at offset 0)
 };
-static RankLayout rank_layout(int dtype, int64_t U, int64_t N, int64_t T) {
+static RankLayout rank_layout(int dtype, int64_t U, int64_t T) {
   RankLayout L{};
-  L.nchunks = (N + kChunk - 1) / kChunk;
-  L.ub = 0;
   L.tsel = align256(dtype == NR_BF16 ? U * D * 2 : 0);
   L.total = L.tsel + align256(T * 4);
   return L;
-}
-
-static bool rank_shape_ok(int dtype, int64_t U, int64_t N, int64_t T) {
-  return ok_dtype(dtype) && U >= 1 && U < (1ll << 31) && N >= 1 && N <= kChunk * kMaxChunks && T >= 0 &&
-         T < (1ll << 31);
 }
 
 }  // namespace tk
 }  // namespace nr
 
 extern "C" int64_t nr_rank_targets_workspace_bytes(int dtype, int64_t U, int64_t N, int64_t T) {
-  if (!nr::tk::rank_shape_ok(dtype, U, N, T)) return -1;
-  return nr::tk::rank_layout(dtype, U, N, T).total;
+  if (!nr::tk::scan_shape_ok(dtype, U, N) || T < 0 || T >= (1ll << 31)) return -1;
+  return nr::tk::rank_layout(dtype, U, T).total;
 }
 
 namespace nr {
@@ -292,83 +264,41 @@ namespace tk {
 
 // nr_rank_targets and nr_rank_targets_filtered: one validation, one launch sequence.  A filter
 // with both pairs null runs the unfiltered kernels.
-static int rank_run(const char* fn, int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
-                    const void* cand_table, int64_t cand_ld, const float* cand_inv_norm, const int32_t* excl_idx,
-                    const int64_t* excl_off, const FilterArgs& flt, int64_t T, const int32_t* tgt_idx,
-                    const int64_t* tgt_off, int32_t* rank, void* ws, int64_t ws_bytes, void* stream) {
-  nr::clear_error();
-  if (dim != 1024) {
-    nr::set_error("%s: dim %lld unsupported (1024 only)", fn, (long long)dim);
-    return NR_ERR_UNSUPPORTED;
-  }
-  NR_CHECK_ARG(nr::ok_dtype(dtype), "%s: bad dtype %d", fn, dtype);
-  NR_CHECK_ARG(U >= 1 && U < (1ll << 31), "%s: U = %lld outside [1, 2^31)", fn, (long long)U);
-  NR_CHECK_ARG(N >= 1, "%s: N = %lld < 1", fn, (long long)N);
-  if (N > kChunk * kMaxChunks) {
-    nr::set_error("%s: N = %lld unsupported (at most %lld rows)", fn, (long long)N, (long long)(kChunk * kMaxChunks));
-    return NR_ERR_UNSUPPORTED;
-  }
-  NR_CHECK_ARG(T >= 0 && T < (1ll << 31), "%s: T = %lld outside [0, 2^31)", fn, (long long)T);
-  NR_CHECK_ARG(cand_ld >= dim, "%s: cand_ld = %lld < dim", fn, (long long)cand_ld);
-  NR_CHECK_ARG(cand_ld % (dtype == NR_F32 ? 4 : 8) == 0 && ((uintptr_t)cand_table & 15) == 0 &&
-                   ((uintptr_t)users & 15) == 0,
-               "%s: users and cand_table must be 16-byte aligned with 16-byte row strides", fn);
-  NR_CHECK_ARG((excl_idx == nullptr) == (excl_off == nullptr), "%s: excl_idx and excl_off go together", fn);
-  NR_CHECK_ARG((flt.news_time == nullptr) == (flt.q_lo == nullptr) && (flt.news_time == nullptr) == (flt.q_hi == nullptr),
-               "%s: news_time, q_time_lo and q_time_hi go together", fn);
-  NR_CHECK_ARG((flt.news_cat == nullptr) == (flt.q_mask == nullptr), "%s: news_cat and q_cat_mask go together", fn);
-  NR_CHECK_ARG(users && cand_table && cand_inv_norm && tgt_off && ws && (T == 0 || (tgt_idx && rank)),
-               "%s: null pointer", fn);
-  const RankLayout L = rank_layout(dtype, U, N, T);
+static int rank_run(const char* fn, const ScanArgs& a, int64_t T, const int32_t* tgt_idx, const int64_t* tgt_off,
+                    int32_t* rank, void* ws, int64_t ws_bytes) {
+  auto t_ok = [&] {
+    NR_CHECK_ARG(T >= 0 && T < (1ll << 31), "%s: T = %lld outside [0, 2^31)", fn, (long long)T);
+    return NR_OK;
+  };
+  if (const int rc = check_scan(fn, a, no_check, t_ok)) return rc;
+  NR_CHECK_ARG(tgt_off && ws && (T == 0 || (tgt_idx && rank)), "%s: null pointer", fn);
+  const RankLayout L = rank_layout(a.dtype, a.U, T);
   NR_CHECK_ARG(ws_bytes >= L.total, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes,
                (long long)L.total);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
-  NR_CHECK_DEVICE(fn, users, cand_table, cand_inv_norm, excl_idx, excl_off, tgt_idx, tgt_off, rank, ws);
-  {
-    const int32_t *news_time = flt.news_time, *q_time_lo = flt.q_lo, *q_time_hi = flt.q_hi;
-    const uint8_t* news_cat = flt.news_cat;
-    const uint64_t* q_cat_mask = flt.q_mask;
-    NR_CHECK_DEVICE(fn, news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask);
-  }
+  if (const int rc = check_scan_device(fn, a, "tgt_idx, tgt_off, rank, ws", {tgt_idx, tgt_off, rank, ws})) return rc;
   if (T == 0) return NR_OK;
 
-  hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)ws;
-  float* tsel = (float*)(w + L.tsel);
+  hipStream_t st = (hipStream_t)a.stream;
+  float* tsel = (float*)((char*)ws + L.tsel);
   if (hipMemsetAsync(rank, 0, (size_t)T * 4, st) != hipSuccess) {
     nr::set_error("%s: hipMemsetAsync failed: %s", fn, hipGetErrorString(hipGetLastError()));
     return NR_ERR_HIP;
   }
-  // chunks run side by side only while the user blocks alone do not fill the device, as in
-  // nr_topk_users; the counts do not depend on it
-  const int64_t span = chunk_span(U, L.nchunks);
-  const int64_t nparts = (L.nchunks + span - 1) / span;
-  const dim3 g0((unsigned)((U + TS - 1) / TS));
-  const dim3 g1(g0.x, (unsigned)nparts);
-  const void* urows = users;
-  if (dtype == NR_BF16) {
-    __bf16* ub = (__bf16*)(w + L.ub);
-    const int rcb = bf16_users_launch(U, users, ub, st, fn);
-    if (rcb) return rcb;
-    urows = ub;
-  }
-  const int filtered = flt.any() ? 1 : 0;
-  return nr::with_dtype(dtype, [&](auto ti) {
+  ScanLaunch sl;
+  if (const int rc = scan_prepare(fn, a, ws, sl)) return rc;
+  return with_scan_types(a, [&](auto ti, auto filt) {
     using TI = typename decltype(ti)::type;
-    return nr::with_int<0, 1>(
-        filtered, [&] { return nr::unvalidated_code("filter", filtered); },
-        [&](auto fc) {
-          constexpr bool F = decltype(fc)::value != 0;
-          hipLaunchKernelGGL((rank_thresholds_kernel<TI, F>), g0, dim3(256), 0, st, U, N, T, (const TI*)urows,
-                             (const TI*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, flt, tgt_idx, tgt_off,
-                             tsel, rank);
-          NR_CHECK_LAUNCH(fn);
-          hipLaunchKernelGGL((rank_count_kernel<TI, F>), g1, dim3(256), 0, st, U, N, T, (const TI*)urows,
-                             (const TI*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, flt, tgt_idx, tgt_off,
-                             (const float*)tsel, span * kChunk, rank);
-          NR_CHECK_LAUNCH(fn);
-          return NR_OK;
-        });
+    constexpr bool F = decltype(filt)::value;
+    hipLaunchKernelGGL((rank_thresholds_kernel<TI, F>), sl.g0, dim3(256), 0, st, a.U, a.N, T, (const TI*)sl.urows,
+                       (const TI*)a.cand_table, a.cand_ld, a.cand_inv_norm, a.excl_idx, a.excl_off, a.flt, tgt_idx,
+                       tgt_off, tsel, rank);
+    NR_CHECK_LAUNCH(fn);
+    hipLaunchKernelGGL((rank_count_kernel<TI, F>), sl.g1, dim3(256), 0, st, a.U, a.N, T, (const TI*)sl.urows,
+                       (const TI*)a.cand_table, a.cand_ld, a.cand_inv_norm, a.excl_idx, a.excl_off, a.flt, tgt_idx,
+                       tgt_off, (const float*)tsel, sl.span_rows, rank);
+    NR_CHECK_LAUNCH(fn);
+    return NR_OK;
   });
 }
 
@@ -379,8 +309,9 @@ extern "C" int nr_rank_targets(int dtype, int64_t dim, int64_t U, const float* u
                                const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
                                const int32_t* excl_idx, const int64_t* excl_off, int64_t T, const int32_t* tgt_idx,
                                const int64_t* tgt_off, int32_t* rank, void* ws, int64_t ws_bytes, void* stream) {
-  return nr::tk::rank_run("nr_rank_targets", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx,
-                          excl_off, nr::tk::FilterArgs{}, T, tgt_idx, tgt_off, rank, ws, ws_bytes, stream);
+  return nr::tk::rank_run("nr_rank_targets",
+                          {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, {}, stream}, T,
+                          tgt_idx, tgt_off, rank, ws, ws_bytes);
 }
 
 extern "C" int nr_rank_targets_filtered(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
@@ -390,13 +321,8 @@ extern "C" int nr_rank_targets_filtered(int dtype, int64_t dim, int64_t U, const
                                         const uint64_t* q_cat_mask, int64_t T, const int32_t* tgt_idx,
                                         const int64_t* tgt_off, int32_t* rank, void* ws, int64_t ws_bytes,
                                         void* stream) {
-  nr::tk::FilterArgs flt;
-  flt.news_time = news_time;
-  flt.q_lo = q_time_lo;
-  flt.q_hi = q_time_hi;
-  flt.news_cat = news_cat;
-  flt.q_mask = q_cat_mask;
-  return nr::tk::rank_run("nr_rank_targets_filtered", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm,
-                          excl_idx, excl_off, flt, T, tgt_idx, tgt_off, rank, ws, ws_bytes, stream);
+  return nr::tk::rank_run("nr_rank_targets_filtered",
+                          {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off,
+                           {news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask}, stream},
+                          T, tgt_idx, tgt_off, rank, ws, ws_bytes);
 }
-

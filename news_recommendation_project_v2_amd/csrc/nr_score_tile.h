@@ -14,8 +14,12 @@
 //   Excluded       a user's excluded rows inside the current chunk, staged in LDS once per
 //                  chunk as 16-bit offsets; a user with more than XCAP of them has its rows set
 //                  to -inf in every score tile by the whole workgroup instead.
-//   Eligible       the catalogue filter (include/newsrec_filter.h) of the kernels' filtered
-//                  instantiations: a predicate on the finished score tile, never on the product.
+//   FilterOf<FILT> the catalogue filter (include/newsrec_filter.h): Eligible in the filtered
+//                  instantiations, a predicate on the finished score tile, never on the product.
+//   ChunkWalk      a workgroup's walk over its run of chunks with the three above: everything
+//                  around the kernel's own epilogue over a finished score tile (a heap, a count).
+//   ScanArgs       host side: what nr_topk_users* and nr_rank_targets* take alike, with its
+//                  validation, launch preparation and (dtype, filtered) -> <TI, FILT> dispatch.
 #pragma once
 
 #include "nr_common.h"
@@ -399,6 +403,145 @@ struct NoFilter {
   __device__ __forceinline__ NoFilter(int32_t*, uint32_t*, const FilterArgs&, int64_t, bool) {}
 };
 template <bool FILT> using FilterOf = std::conditional_t<FILT, Eligible, NoFilter>;
+
+// One workgroup's walk over news rows [c0, min(N, c0 + span_rows)) of the table against users
+// [m0, m0 + TS).  The kernel declares the __shared__ arrays and hands them in; run() calls
+// epilogue(n0, T) once per finished score tile T of rows [n0, n0 + TS) and closes the tile with
+// the barrier behind which the next tile's operands overwrite T.  Threads 2 su and 2 su + 1
+// (sh = 0, 1) serve user su of the block, which exists if `live`.
+template <typename TI, bool FILT>
+struct ChunkWalk {
+  int64_t N, m0, c0, ldt;
+  int ntiles, su, sh;
+  bool live;
+  const TI* tab;
+  const float* cinv;
+  ScoreTile<TI> st;
+  Excluded ex;
+  FilterOf<FILT> el;
+
+  __device__ __forceinline__ ChunkWalk(uint32_t* smem, float* cinv_s, uint16_t* ex_s, uint32_t* ov_mask, int32_t* ft_s,
+                                       uint32_t* fc_s, int64_t U, int64_t N_, const TI* users, const TI* tab_,
+                                       int64_t ldt_, const float* cinv_, const int32_t* excl_idx,
+                                       const int64_t* excl_off, const FilterArgs& flt, int64_t span_rows)
+      : N(N_), m0((int64_t)blockIdx.x * TS), c0((int64_t)blockIdx.y * span_rows), ldt(ldt_),
+        ntiles((int)((min(N_, c0 + span_rows) - c0 + TS - 1) / TS)), su(threadIdx.x >> 1), sh(threadIdx.x & 1),
+        live(m0 + su < U), tab(tab_), cinv(cinv_), st(smem, cinv_s, users, m0, U),
+        ex(ex_s, ov_mask, excl_idx, excl_off, m0, live, c0), el(ft_s, fc_s, flt, m0, live) {}
+
+  template <typename Epilogue>
+  __device__ __forceinline__ void run(Epilogue epilogue) {
+    const int tid = threadIdx.x;
+    // a run of consecutive table rows from n0, clamped past the table (their scores are -inf)
+    auto rows_from = [&](int64_t n0) __attribute__((always_inline)) {
+      return [n0, last = N - 1](int r) __attribute__((always_inline)) { return min(n0 + r, last); };
+    };
+    st.gload(tab, ldt, rows_from(c0), 0);
+    for (int tile = 0; tile < ntiles; ++tile) {
+      const int64_t n0 = c0 + (int64_t)tile * TS;
+      if (tile == 0 || n0 == ex.cb + kChunk) ex.chunk_start(n0);
+      const int nvalid = (int)min((int64_t)TS, N - n0);
+      if (tid < TS) st.cinv_s[tid] = tid < nvalid ? cinv[n0 + tid] : 0.f;
+      if constexpr (FILT) el.stage(n0, N);
+      st.scores(tab, ldt, rows_from(n0), tile + 1 < ntiles, rows_from(n0 + TS), nvalid);
+      ex.knock_out_overflow(st.tile(), m0, n0);
+      epilogue(n0, st.tile());
+      __syncthreads();  // the next tile's operands overwrite the score tile
+    }
+  }
+};
+
+// ---- host side: what the entries over the whole table (nr_topk_users*, nr_rank_targets*) share
+struct ScanArgs {
+  int dtype;
+  int64_t dim, U;
+  const float* users;
+  int64_t N;
+  const void* cand_table;
+  int64_t cand_ld;
+  const float* cand_inv_norm;
+  const int32_t* excl_idx;
+  const int64_t* excl_off;
+  FilterArgs flt;
+  void* stream;
+};
+
+static inline int64_t chunks_of(int64_t N) { return (N + kChunk - 1) / kChunk; }
+static inline bool scan_shape_ok(int dtype, int64_t U, int64_t N) {
+  return ok_dtype(dtype) && U >= 1 && U < (1ll << 31) && N >= 1 && N <= kChunk * kMaxChunks;
+}
+static inline int no_check() { return NR_OK; }
+
+// The shared validation.  A feature's own size check (K, T) runs where that feature has always
+// had it, behind the dtype check or behind those of N; its output and workspace checks follow.
+template <typename AfterDtype, typename AfterN>
+static int check_scan(const char* fn, const ScanArgs& a, AfterDtype after_dtype, AfterN after_n) {
+  nr::clear_error();
+  if (a.dim != 1024) {
+    nr::set_error("%s: dim %lld unsupported (1024 only)", fn, (long long)a.dim);
+    return NR_ERR_UNSUPPORTED;
+  }
+  NR_CHECK_ARG(nr::ok_dtype(a.dtype), "%s: bad dtype %d", fn, a.dtype);
+  if (const int rc = after_dtype()) return rc;
+  NR_CHECK_ARG(a.U >= 1 && a.U < (1ll << 31), "%s: U = %lld outside [1, 2^31)", fn, (long long)a.U);
+  NR_CHECK_ARG(a.N >= 1, "%s: N = %lld < 1", fn, (long long)a.N);
+  if (a.N > kChunk * kMaxChunks) {
+    nr::set_error("%s: N = %lld unsupported (at most %lld rows)", fn, (long long)a.N, (long long)(kChunk * kMaxChunks));
+    return NR_ERR_UNSUPPORTED;
+  }
+  if (const int rc = after_n()) return rc;
+  NR_CHECK_ARG(a.cand_ld >= a.dim, "%s: cand_ld = %lld < dim", fn, (long long)a.cand_ld);
+  NR_CHECK_ARG(a.cand_ld % (a.dtype == NR_F32 ? 4 : 8) == 0 && ((uintptr_t)a.cand_table & 15) == 0 &&
+                   ((uintptr_t)a.users & 15) == 0,
+               "%s: users and cand_table must be 16-byte aligned with 16-byte row strides", fn);
+  NR_CHECK_ARG((a.excl_idx == nullptr) == (a.excl_off == nullptr), "%s: excl_idx and excl_off go together", fn);
+  const FilterArgs& f = a.flt;
+  NR_CHECK_ARG((f.news_time == nullptr) == (f.q_lo == nullptr) && (f.news_time == nullptr) == (f.q_hi == nullptr),
+               "%s: news_time, q_time_lo and q_time_hi go together", fn);
+  NR_CHECK_ARG((f.news_cat == nullptr) == (f.q_mask == nullptr), "%s: news_cat and q_cat_mask go together", fn);
+  NR_CHECK_ARG(a.users && a.cand_table && a.cand_inv_norm, "%s: null pointer", fn);
+  return NR_OK;
+}
+
+// NR_CHECK_DEVICE over a scan's pointers, the feature's own (`outs`) between the scan's and the filter's
+static inline int check_scan_device(const char* fn, const ScanArgs& a, const char* out_names,
+                                    std::initializer_list<const void*> outs) {
+  if (const int rc = nr::check_device_ptrs(fn, "users, cand_table, cand_inv_norm, excl_idx, excl_off",
+                                           {a.users, a.cand_table, a.cand_inv_norm, a.excl_idx, a.excl_off}))
+    return rc;
+  if (const int rc = nr::check_device_ptrs(fn, out_names, outs)) return rc;
+  return nr::check_device_ptrs(fn, "news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask",
+                               {a.flt.news_time, a.flt.q_lo, a.flt.q_hi, a.flt.news_cat, a.flt.q_mask});
+}
+
+// What a scan launches with: the users operand (NR_BF16: converted into `ub`, U * D * 2 bytes of
+// the workspace), the grids of user blocks and of (user block, run of chunks).  A workgroup keeps
+// one running state over chunk_span consecutive chunks: the longer its walk, the fewer rows ever
+// pass top-K's threshold (K (1 + ln(rows / K)) of them).  No result depends on it.
+struct ScanLaunch {
+  const void* urows;
+  dim3 g0, g1;
+  int64_t span_rows;  // news rows per workgroup of g1
+};
+static inline int scan_prepare(const char* fn, const ScanArgs& a, void* ub, ScanLaunch& L) {
+  const int64_t nchunks = chunks_of(a.N), span = chunk_span(a.U, nchunks);
+  L.g0 = dim3((unsigned)((a.U + TS - 1) / TS));
+  L.g1 = dim3(L.g0.x, (unsigned)((nchunks + span - 1) / span));
+  L.span_rows = span * kChunk;
+  L.urows = a.users;
+  if (a.dtype == NR_BF16) {
+    if (const int rc = bf16_users_launch(a.U, a.users, (__bf16*)ub, (hipStream_t)a.stream, fn)) return rc;
+    L.urows = ub;
+  }
+  return NR_OK;
+}
+
+// f(TypeTag<TI>, std::bool_constant<FILT>) for the scan's dtype and whether it carries a filter
+template <typename F>
+static int with_scan_types(const ScanArgs& a, F&& f) {
+  return nr::with_dtype(
+      a.dtype, [&](auto ti) { return a.flt.any() ? f(ti, std::true_type{}) : f(ti, std::false_type{}); });
+}
 
 }  // namespace tk
 }  // namespace nr

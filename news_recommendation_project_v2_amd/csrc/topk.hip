@@ -3,21 +3,13 @@
 //
 //   prep     NR_BF16 only: users f32 -> bf16 rows in the workspace (round to nearest even)
 //   stage 1  grid (user blocks of 128, runs of chunks of kChunk news rows).  A workgroup walks its
-//            chunks in 128-row tiles (nr_score_tile.h, shared with fullrank.hip: the tile main
-//            loop and the exclusion staging exist once): gemm_kernel's main loop (128 x 128 tile, K in
-//            128-byte row slices through a two-stage LDS ring, the next slice's global loads
-//            in flight over the MFMAs; f32 on v_mfma_f32_32x32x2_f32, bf16 on
-//            v_mfma_f32_16x16x32_bf16) with the NEWS rows as the A operand, so a lane's
-//            accumulator registers are 4 consecutive news of one user.  Epilogue, per tile:
-//            scale by cand_inv (-inf past N), 16-byte stores into an LDS score tile that
-//            aliases the operand ring, then two threads per user scan the row against the
-//            user's running K-th best (-inf until K are kept) and the first of them keeps
-//            the few that pass and are not excluded in the user's list in LDS, a binary
-//            heap with the worst kept entry at the root.  A user's excluded rows inside
-//            the current chunk are staged in LDS once per chunk and looked up per passing
-//            candidate; a user with more than XCAP of them has its rows set to -inf in
-//            every score tile by the whole workgroup instead.  The list goes out
-//            rank-sorted as K (score, row) pairs per (user, run of chunks).
+//            chunks in 128-row score tiles (nr_score_tile.h, shared with fullrank.hip: the tile
+//            main loop, the exclusion staging and the walk exist once).  Epilogue, per tile:
+//            two threads per user scan the row against the user's running K-th best (-inf
+//            until K are kept) and the first of them keeps the few that pass and are not
+//            excluded in the user's list in LDS, a binary heap with the worst kept entry at
+//            the root.  The list goes out rank-sorted as K (score, row) pairs per (user, run
+//            of chunks).
 //   stage 2  one wave per user: a K-round merge of the chunk lists' heads (ties by row),
 //            the survivors' rows (0 in place of a missing one: never row -1) to top_idx;
 //            the evaluation path's scoring kernel over them (score_users_dispatch) into
@@ -81,39 +73,19 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
   __shared__ uint32_t ov_mask[TS / 32];
   __shared__ __attribute__((aligned(16))) int32_t ft_s[FILT ? ATTR_TIME_WORDS : 4];  // the tile's news times
   __shared__ uint32_t fc_s[FILT ? ATTR_CAT_WORDS : 1];                                //   and categories
-  float* T = reinterpret_cast<float*>(smem);
 
   const int tid = threadIdx.x, lane = tid & 63;
-  const int64_t m0 = (int64_t)blockIdx.x * TS;
-  // this workgroup's news rows: span_rows = a whole number of chunks, one running list over them
-  const int64_t c0 = (int64_t)blockIdx.y * span_rows;
-  const int64_t c1 = min(N, c0 + span_rows);
-  const int ntiles = (int)((c1 - c0 + TS - 1) / TS);
   const float NINF = -__builtin_inff();
-
-  ScoreTile<TI> st(smem, cinv_s, users, m0, U);
-
+  // this workgroup's news rows: span_rows = a whole number of chunks, one running list over them
+  ChunkWalk<TI, FILT> w(smem, cinv_s, ex_s, ov_mask, ft_s, fc_s, U, N, users, tab, ldt, cinv, excl_idx, excl_off, flt,
+                        span_rows);
   // selection state: threads 2u and 2u + 1 serve user u of the block; 2u owns its list
-  const int su = tid >> 1, sh = tid & 1;
-  const bool live = m0 + su < U;
-  Excluded ex(ex_s, ov_mask, excl_idx, excl_off, m0, live, c0);
-  FilterOf<FILT> el(ft_s, fc_s, flt, m0, live);
+  const int su = w.su, sh = w.sh;
+  const int64_t m0 = w.m0;
   int cnt = 0;            // rows kept so far (a heap in LDS, the worst at slot 0)
   float thr = NINF;       // the worst's score once K are kept; -inf until then (every finite score passes)
 
-  // a run of consecutive table rows from n0, clamped past the table (their scores are -inf)
-  auto rows_from = [&](int64_t n0) __attribute__((always_inline)) {
-    return [=](int r) __attribute__((always_inline)) { return min(n0 + r, N - 1); };
-  };
-  st.gload(tab, ldt, rows_from(c0), 0);
-  for (int tile = 0; tile < ntiles; ++tile) {
-    const int64_t n0 = c0 + (int64_t)tile * TS;
-    if (tile == 0 || n0 == ex.cb + kChunk) ex.chunk_start(n0);
-    const int nvalid = (int)min((int64_t)TS, N - n0);
-    if (tid < TS) cinv_s[tid] = tid < nvalid ? cinv[n0 + tid] : 0.f;
-    if constexpr (FILT) el.stage(n0, N);
-    st.scores(tab, ldt, rows_from(n0), tile + 1 < ntiles, rows_from(n0 + TS), nvalid);
-    ex.knock_out_overflow(T, m0, n0);
+  w.run([&](int64_t n0, float* T) __attribute__((always_inline)) {
     // ---- scan against the running K-th best; what passes and is not excluded is kept (ascending row)
     uint32_t mlo = 0, mhi = 0;
     {
@@ -126,9 +98,9 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
         else mhi |= b << (4 * (i - 8));
       }
     }
-    if constexpr (FILT) el.keep_eligible(sh, mlo, mhi);
+    if constexpr (FILT) w.el.keep_eligible(sh, mlo, mhi);
     const uint32_t plo = __shfl_down(mlo, 1, 64), phi = __shfl_down(mhi, 1, 64);
-    if (sh == 0 && live) {
+    if (sh == 0 && w.live) {
       // 32 columns of the row at a time, in ascending row order
       auto drain = [&](uint32_t bits, int col0) __attribute__((always_inline)) {
         while (bits) {
@@ -137,7 +109,7 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
           const float s = T[su * TLD + col];
           const int32_t row = (int32_t)(n0 + col);
           // a later row never beats an equal score already kept, so the compare is strict
-          if (!(s > thr) || ex.staged(row)) continue;  // (the threshold may have risen since the scan)
+          if (!(s > thr) || w.ex.staged(row)) continue;  // (the threshold may have risen since the scan)
           // the list is a binary heap with the WORST kept entry (lowest score, then highest
           // row) at slot 0: log2 K steps per kept row
           int i;
@@ -183,8 +155,7 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
       drain(phi, 96);
     }
     thr = __shfl(thr, lane & ~1, 64);
-    __syncthreads();  // the next tile's operands overwrite the score tile
-  }
+  });
   // ---- K (score, row) pairs per (user, chunk), best first (a rank sort of the kept
   // list); a short list ends in (-inf, -1)
   if (sh == 0) cnt_s[su] = cnt;
@@ -301,7 +272,7 @@ struct Layout {
 };
 static Layout layout(int dtype, int64_t U, int64_t N, int64_t K) {
   Layout L{};
-  L.nchunks = (N + kChunk - 1) / kChunk;
+  L.nchunks = chunks_of(N);
   int64_t o = 0;
   auto take = [&](int64_t bytes) {
     const int64_t at = o;
@@ -317,17 +288,13 @@ static Layout layout(int dtype, int64_t U, int64_t N, int64_t K) {
   return L;
 }
 
-static bool shape_ok(int dtype, int64_t U, int64_t N, int64_t K) {
-  return ok_dtype(dtype) && U >= 1 && U < (1ll << 31) && N >= 1 && N <= kChunk * kMaxChunks && K >= 1 && K <= KMAX;
-}
-
 }  // namespace tk
 }  // namespace nr
 
 extern "C" int64_t nr_topk_chunk_rows(void) { return nr::tk::kChunk; }
 
 extern "C" int64_t nr_topk_workspace_bytes(int dtype, int64_t U, int64_t N, int64_t K) {
-  if (!nr::tk::shape_ok(dtype, U, N, K)) return -1;
+  if (!nr::tk::scan_shape_ok(dtype, U, N) || K < 1 || K > nr::tk::KMAX) return -1;
   return nr::tk::layout(dtype, U, N, K).total;
 }
 
@@ -336,83 +303,44 @@ namespace tk {
 
 // nr_topk_users and nr_topk_users_filtered: one validation, one launch sequence.  A filter with
 // both pairs null runs the unfiltered stage 1.
-static int topk_run(const char* fn, int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
-                    const void* cand_table, int64_t cand_ld, const float* cand_inv_norm, const int32_t* excl_idx,
-                    const int64_t* excl_off, const FilterArgs& flt, int64_t K, int32_t* top_idx, float* top_scores,
-                    void* ws, int64_t ws_bytes, void* stream) {
-  nr::clear_error();
-  if (dim != 1024) {
-    nr::set_error("%s: dim %lld unsupported (1024 only)", fn, (long long)dim);
-    return NR_ERR_UNSUPPORTED;
-  }
-  NR_CHECK_ARG(nr::ok_dtype(dtype), "%s: bad dtype %d", fn, dtype);
-  NR_CHECK_ARG(K >= 1 && K <= KMAX, "%s: K = %lld outside [1, %d]", fn, (long long)K, KMAX);
-  NR_CHECK_ARG(U >= 1 && U < (1ll << 31), "%s: U = %lld outside [1, 2^31)", fn, (long long)U);
-  NR_CHECK_ARG(N >= 1, "%s: N = %lld < 1", fn, (long long)N);
-  if (N > kChunk * kMaxChunks) {
-    nr::set_error("%s: N = %lld unsupported (at most %lld rows)", fn, (long long)N, (long long)(kChunk * kMaxChunks));
-    return NR_ERR_UNSUPPORTED;
-  }
-  NR_CHECK_ARG(cand_ld >= dim, "%s: cand_ld = %lld < dim", fn, (long long)cand_ld);
-  NR_CHECK_ARG(cand_ld % (dtype == NR_F32 ? 4 : 8) == 0 && ((uintptr_t)cand_table & 15) == 0 &&
-                   ((uintptr_t)users & 15) == 0,
-               "%s: users and cand_table must be 16-byte aligned with 16-byte row strides", fn);
-  NR_CHECK_ARG((excl_idx == nullptr) == (excl_off == nullptr), "%s: excl_idx and excl_off go together", fn);
-  NR_CHECK_ARG((flt.news_time == nullptr) == (flt.q_lo == nullptr) && (flt.news_time == nullptr) == (flt.q_hi == nullptr),
-               "%s: news_time, q_time_lo and q_time_hi go together", fn);
-  NR_CHECK_ARG((flt.news_cat == nullptr) == (flt.q_mask == nullptr), "%s: news_cat and q_cat_mask go together", fn);
-  NR_CHECK_ARG(users && cand_table && cand_inv_norm && top_idx && top_scores && ws, "%s: null pointer", fn);
-  const Layout L = layout(dtype, U, N, K);
+static int topk_run(const char* fn, const ScanArgs& a, int64_t K, int32_t* top_idx, float* top_scores, void* ws,
+                    int64_t ws_bytes) {
+  auto k_ok = [&] {
+    NR_CHECK_ARG(K >= 1 && K <= KMAX, "%s: K = %lld outside [1, %d]", fn, (long long)K, KMAX);
+    return NR_OK;
+  };
+  if (const int rc = check_scan(fn, a, k_ok, no_check)) return rc;
+  NR_CHECK_ARG(top_idx && top_scores && ws, "%s: null pointer", fn);
+  const Layout L = layout(a.dtype, a.U, a.N, K);
   NR_CHECK_ARG(ws_bytes >= L.total, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes,
                (long long)L.total);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
-  NR_CHECK_DEVICE(fn, users, cand_table, cand_inv_norm, excl_idx, excl_off, top_idx, top_scores, ws);
-  {
-    const int32_t *news_time = flt.news_time, *q_time_lo = flt.q_lo, *q_time_hi = flt.q_hi;
-    const uint8_t* news_cat = flt.news_cat;
-    const uint64_t* q_cat_mask = flt.q_mask;
-    NR_CHECK_DEVICE(fn, news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask);
-  }
+  if (const int rc = check_scan_device(fn, a, "top_idx, top_scores, ws", {top_idx, top_scores, ws})) return rc;
 
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)a.stream;
+  const int64_t U = a.U;
   char* w = (char*)ws;
   int32_t* cnt = (int32_t*)(w + L.cnt);
   int32_t* uidx = (int32_t*)(w + L.uidx);
   int64_t* coff = (int64_t*)(w + L.coff);
   Pair* part = (Pair*)(w + L.part);
-  // A workgroup keeps one running list over `span` consecutive chunks: the longer its walk, the
-  // fewer rows ever pass its threshold (K (1 + ln(rows / K)) of them), so chunks only run side
-  // by side while the user blocks alone do not fill the device.  The survivors do not depend on it.
-  const int64_t span = chunk_span(U, L.nchunks);
-  const int64_t nparts = (L.nchunks + span - 1) / span;
-  const dim3 g1((unsigned)((U + TS - 1) / TS), (unsigned)nparts);
-  const void* urows = users;
-  if (dtype == NR_BF16) {
-    __bf16* ub = (__bf16*)(w + L.ub);
-    const int rcb = bf16_users_launch(U, users, ub, st, fn);
-    if (rcb) return rcb;
-    urows = ub;
-  }
-  const int filtered = flt.any() ? 1 : 0;
-  const int rc1 = nr::with_dtype(dtype, [&](auto ti) {
+  ScanLaunch sl;
+  if (const int rc = scan_prepare(fn, a, w + L.ub, sl)) return rc;
+  const int rc1 = with_scan_types(a, [&](auto ti, auto filt) {
     using TI = typename decltype(ti)::type;
-    return nr::with_int<0, 1>(
-        filtered, [&] { return nr::unvalidated_code("filter", filtered); },
-        [&](auto fc) {
-          hipLaunchKernelGGL((topk_stage1_kernel<TI, decltype(fc)::value != 0>), g1, dim3(256), 0, st, U, N,
-                             (const TI*)urows, (const TI*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, flt,
-                             (int)K, span * kChunk, part);
-          return NR_OK;
-        });
+    hipLaunchKernelGGL((topk_stage1_kernel<TI, decltype(filt)::value>), sl.g1, dim3(256), 0, st, U, a.N,
+                       (const TI*)sl.urows, (const TI*)a.cand_table, a.cand_ld, a.cand_inv_norm, a.excl_idx, a.excl_off,
+                       a.flt, (int)K, sl.span_rows, part);
+    return NR_OK;
   });
   if (rc1) return rc1;
   NR_CHECK_LAUNCH(fn);
   const dim3 gw((unsigned)((U + 3) / 4));
-  hipLaunchKernelGGL(topk_merge_kernel, gw, dim3(256), 0, st, U, (int)K, (int)nparts, (const Pair*)part, top_idx, cnt,
+  hipLaunchKernelGGL(topk_merge_kernel, gw, dim3(256), 0, st, U, (int)K, (int)sl.g1.y, (const Pair*)part, top_idx, cnt,
                      uidx, coff);
   NR_CHECK_LAUNCH(fn);
-  const int rc = nr::score_users_dispatch(dtype, users, uidx, cand_table, cand_ld, cand_inv_norm, top_idx, coff, U,
-                                          top_scores, st);
+  const int rc = nr::score_users_dispatch(a.dtype, a.users, uidx, a.cand_table, a.cand_ld, a.cand_inv_norm, top_idx,
+                                          coff, U, top_scores, st);
   if (rc) return rc;
   hipLaunchKernelGGL(topk_sort_kernel, gw, dim3(256), 0, st, U, (int)K, (const int32_t*)cnt, top_idx, top_scores);
   NR_CHECK_LAUNCH(fn);
@@ -426,8 +354,9 @@ extern "C" int nr_topk_users(int dtype, int64_t dim, int64_t U, const float* use
                              int64_t cand_ld, const float* cand_inv_norm, const int32_t* excl_idx,
                              const int64_t* excl_off, int64_t K, int32_t* top_idx, float* top_scores, void* ws,
                              int64_t ws_bytes, void* stream) {
-  return nr::tk::topk_run("nr_topk_users", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx,
-                          excl_off, nr::tk::FilterArgs{}, K, top_idx, top_scores, ws, ws_bytes, stream);
+  return nr::tk::topk_run("nr_topk_users",
+                          {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, {}, stream}, K,
+                          top_idx, top_scores, ws, ws_bytes);
 }
 
 extern "C" int nr_topk_users_filtered(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
@@ -436,13 +365,8 @@ extern "C" int nr_topk_users_filtered(int dtype, int64_t dim, int64_t U, const f
                                       const int32_t* q_time_lo, const int32_t* q_time_hi, const uint8_t* news_cat,
                                       const uint64_t* q_cat_mask, int64_t K, int32_t* top_idx, float* top_scores,
                                       void* ws, int64_t ws_bytes, void* stream) {
-  nr::tk::FilterArgs flt;
-  flt.news_time = news_time;
-  flt.q_lo = q_time_lo;
-  flt.q_hi = q_time_hi;
-  flt.news_cat = news_cat;
-  flt.q_mask = q_cat_mask;
-  return nr::tk::topk_run("nr_topk_users_filtered", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm,
-                          excl_idx, excl_off, flt, K, top_idx, top_scores, ws, ws_bytes, stream);
+  return nr::tk::topk_run("nr_topk_users_filtered",
+                          {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off,
+                           {news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask}, stream},
+                          K, top_idx, top_scores, ws, ws_bytes);
 }
-

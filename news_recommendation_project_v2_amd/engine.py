@@ -198,6 +198,40 @@ class PoolScoreEngine:
                    cat_mask=None if q.mask is None else q.mask[a:b])
         return users[qu], eidx, eoff, flt
 
+    def _distinct_hist(self):
+        """The history CSR with one segment per DISTINCT history: (hidx, hoff), the
+        deduplicated CSR when load_impressions built it, else the impressions' own."""
+        if self.user_idx is not None:
+            return self.uhist_idx, self.uhist_off
+        return self.hist_idx, self.hist_off
+
+    def _pooled_users(self, hidx, hoff) -> torch.Tensor:
+        """The histories' pooled rows, f32 [n_u, D], in a buffer reused across calls."""
+        n_u = hoff.numel() - 1
+        if self._users is None or self._users.shape[0] != n_u:
+            self._users = torch.empty((n_u, 1024), dtype=torch.float32, device=self.device)
+        return ops.pool_users(self.pooler, self.hist_table, hidx, hoff, out=self._users)
+
+    def _blocks(self, q: Optional[_Queries], users, hidx, hoff, n_rows: int, blk: int, exclude_history: bool,
+                wanted=None):
+        """The rows a scan of the table sees -- distinct histories, or with ``q`` distinct queries
+        -- in blocks of ``blk``: yields (a, b, rows, eidx, eoff, flt) with the pooled rows
+        [a, b), their exclusion CSR (None without ``exclude_history``) and the filter arguments
+        of the ops call ({} without ``q``).  Without ``q`` these are views: the offsets rebased
+        on the device, the indices' tail shared.  ``wanted(a, b)`` false skips a block unbuilt."""
+        for a in range(0, n_rows, blk):
+            b = min(a + blk, n_rows)
+            if wanted is not None and not wanted(a, b):
+                continue
+            if q is not None:
+                yield (a, b) + self._query_block(q, users, hidx, hoff, a, b, exclude_history)
+                continue
+            eidx = eoff = None
+            if exclude_history:
+                eoff = hoff[a:b + 1] - hoff[a:a + 1] if a else hoff[:b + 1]
+                eidx = hidx[int(self._hoff_host(hoff)[a]):] if a else hidx
+            yield a, b, users[a:b], eidx, eoff, {}
+
     def load_impressions(self, hist_idx, hist_len, cand_idx, cand_len, dedupe: Optional[bool] = None):
         """Upload the CSR index arrays.  ``dedupe`` (default: automatic) pools
         each DISTINCT history once (MIND repeats a user's history on every
@@ -280,10 +314,7 @@ class PoolScoreEngine:
 
     def pool_score(self, want_users: bool = False, scores: Optional[torch.Tensor] = None):
         if self.user_idx is not None:  # distinct histories pooled once, then scored per impression
-            n_u = self.uhist_off.numel() - 1
-            if self._users is None or self._users.shape[0] != n_u:
-                self._users = torch.empty((n_u, 1024), dtype=torch.float32, device=self.device)
-            users = ops.pool_users(self.pooler, self.hist_table, self.uhist_idx, self.uhist_off, out=self._users)
+            users = self._pooled_users(self.uhist_idx, self.uhist_off)
             s = ops.score_users(users, self.user_idx, self.cand_table, self.cand_inv, self.cand_idx, self.cand_off,
                                 self.n_cand, scores=scores)
             return s, (users[self.user_idx.long()] if want_users else None)
@@ -304,39 +335,20 @@ class PoolScoreEngine:
         Under a catalogue filter ``q``: per distinct query, [q.n, k]."""
         self.hist_table = self.transform(out=self.hist_table)
         self.inv_norms()
-        if self.user_idx is not None:
-            hidx, hoff = self.uhist_idx, self.uhist_off
-        else:
-            hidx, hoff = self.hist_idx, self.hist_off
-        n_u = hoff.numel() - 1
-        n_rows = n_u if q is None else q.n
+        hidx, hoff = self._distinct_hist()
+        n_rows = hoff.numel() - 1 if q is None else q.n
         idx = torch.empty((n_rows, k), dtype=torch.int32, device=self.device)
         scores = torch.empty((n_rows, k), dtype=torch.float32, device=self.device)
         if n_rows == 0:
             return idx, scores
-        if self._users is None or self._users.shape[0] != n_u:
-            self._users = torch.empty((n_u, 1024), dtype=torch.float32, device=self.device)
-        users = ops.pool_users(self.pooler, self.hist_table, hidx, hoff, out=self._users)
+        users = self._pooled_users(hidx, hoff)  # pooled once per distinct history, searched once per distinct query
         blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
         need = ops.topk_workspace_bytes(self.dtype, blk, self.cand_table.shape[0], k)
         self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, self.device)
-        if q is not None:  # users are pooled once per distinct history, searched once per distinct query
-            for a in range(0, q.n, blk):
-                b = min(a + blk, q.n)
-                rows, eidx, eoff, flt = self._query_block(q, users, hidx, hoff, a, b, exclude_history)
-                ops.topk_users_filtered(rows, self.cand_table, self.cand_inv, k, excl_idx=eidx, excl_off=eoff,
-                                        out=(idx[a:b], scores[a:b]), workspace=self._topk_ws, **flt)
-            return idx, scores
-        for u0 in range(0, n_u, blk):
-            u1 = min(u0 + blk, n_u)
-            eoff = None
-            if exclude_history:
-                # the block's own CSR: offsets rebased on the device, indices shared
-                eoff = hoff[u0:u1 + 1] - hoff[u0:u0 + 1] if u0 else hoff[:u1 + 1]
-                eidx = hidx[int(self._hoff_host(hoff)[u0]):] if u0 else hidx
-            ops.topk_users(users[u0:u1], self.cand_table, self.cand_inv, k,
-                           excl_idx=eidx if exclude_history else None, excl_off=eoff,
-                           out=(idx[u0:u1], scores[u0:u1]), workspace=self._topk_ws)
+        for a, b, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history):
+            (ops.topk_users_filtered if flt else ops.topk_users)(
+                rows, self.cand_table, self.cand_inv, k, excl_idx=eidx, excl_off=eoff, out=(idx[a:b], scores[a:b]),
+                workspace=self._topk_ws, **flt)
         return idx, scores
 
     def _expansion(self, q: Optional[_Queries]) -> Optional[torch.Tensor]:
@@ -465,10 +477,8 @@ class PoolScoreEngine:
         if q is not None:
             idx, scores = idx[q.sel].contiguous(), scores[q.sel].contiguous()
             hidx, hoff = self.hist_idx, self.hist_off
-        elif self.user_idx is not None:
-            hidx, hoff = self.uhist_idx, self.uhist_off
         else:
-            hidx, hoff = self.hist_idx, self.hist_off
+            hidx, hoff = self._distinct_hist()
         n_u, top = idx.shape[0], int(top)
         if n_u == 0:
             return (idx, scores, torch.empty((0, int(k), top), dtype=torch.int32, device=self.device),
@@ -505,10 +515,7 @@ class PoolScoreEngine:
         _check_segments(tgt_idx, tgt_len, "target")
         self.hist_table = self.transform(out=self.hist_table)
         self.inv_norms()
-        if self.user_idx is not None:
-            hidx, hoff = self.uhist_idx, self.uhist_off
-        else:
-            hidx, hoff = self.hist_idx, self.hist_off
+        hidx, hoff = self._distinct_hist()
         q = self._queries(time_window, categories)
         n_u = hoff.numel() - 1
         n_t = len(tgt_idx)
@@ -524,9 +531,7 @@ class PoolScoreEngine:
             toff = lengths_to_offsets(np.bincount(owner, minlength=n_rows))
         else:
             toff = lengths_to_offsets(tgt_len)
-        if self._users is None or self._users.shape[0] != n_u:
-            self._users = torch.empty((n_u, 1024), dtype=torch.float32, device=self.device)
-        users = ops.pool_users(self.pooler, self.hist_table, hidx, hoff, out=self._users)
+        users = self._pooled_users(hidx, hoff)
         tidx_d = _upload(tgt_idx, self.device)
         blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
         n_news = self.cand_table.shape[0]
@@ -534,25 +539,13 @@ class PoolScoreEngine:
         need = ops.rank_targets_workspace_bytes(self.dtype, blk, n_news, most)
         self._rank_ws = ops.grow_workspace(getattr(self, "_rank_ws", None), max(need, 256), self.device)
         sorted_ranks = ranks if order is None else torch.empty_like(ranks)
-        for u0 in range(0, n_rows, blk):
-            u1 = min(u0 + blk, n_rows)
+        has_targets = lambda u0, u1: toff[u0] != toff[u1]
+        for u0, u1, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history,
+                                                          wanted=has_targets):
             a, b = int(toff[u0]), int(toff[u1])
-            if a == b:
-                continue
-            if q is not None:
-                rows, eidx, eoff, flt = self._query_block(q, users, hidx, hoff, u0, u1, exclude_history)
-                ops.rank_targets_filtered(rows, self.cand_table, self.cand_inv, tidx_d[a:b],
-                                          _upload(toff[u0:u1 + 1] - a, self.device), excl_idx=eidx, excl_off=eoff,
-                                          out=sorted_ranks[a:b], workspace=self._rank_ws, **flt)
-                continue
-            eidx = eoff = None
-            if exclude_history:
-                # the block's own CSR: offsets rebased on the device, indices shared
-                eoff = hoff[u0:u1 + 1] - hoff[u0:u0 + 1] if u0 else hoff[:u1 + 1]
-                eidx = hidx[int(self._hoff_host(hoff)[u0]):] if u0 else hidx
-            ops.rank_targets(users[u0:u1], self.cand_table, self.cand_inv, tidx_d[a:b],
-                             _upload(toff[u0:u1 + 1] - a, self.device), excl_idx=eidx, excl_off=eoff,
-                             out=sorted_ranks[a:b], workspace=self._rank_ws)
+            (ops.rank_targets_filtered if flt else ops.rank_targets)(
+                rows, self.cand_table, self.cand_inv, tidx_d[a:b], _upload(toff[u0:u1 + 1] - a, self.device),
+                excl_idx=eidx, excl_off=eoff, out=sorted_ranks[a:b], workspace=self._rank_ws, **flt)
         if order is not None:
             ranks[_upload(order, self.device)] = sorted_ranks
         return ranks

@@ -221,6 +221,62 @@ def _check_csr(idx: torch.Tensor, off: torch.Tensor, name: str) -> None:
         raise _lib.NewsRecHIPError(f"{name}_off must be contiguous int64")
 
 
+def _check_inv_norm(cand_inv_norm: torch.Tensor, n_news: int, contiguous: bool = True) -> None:
+    if (cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < n_news
+            or (contiguous and not cand_inv_norm.is_contiguous())):
+        raise _lib.NewsRecHIPError(f"cand_inv_norm must be {'contiguous ' if contiguous else ''}f32 with one entry per "
+                                   "candidate-table row")
+
+
+def _check_scan(what: str, users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor,
+                excl_idx: Optional[torch.Tensor], excl_off: Optional[torch.Tensor]):
+    """Host checks of a scan of the whole table (topk_users, rank_targets): returns (n_users,
+    dim, n_news, ld, dt, excl_idx), the exclusion rows range-checked (one small sync) and an
+    empty list replaced by a one-slot dummy."""
+    if users.dtype != torch.float32 or users.dim() != 2 or not users.is_contiguous():
+        raise _lib.NewsRecHIPError(f"{what}: users must be contiguous f32 [U, D]")
+    n_users, dim = users.shape
+    n_news = cand_table.shape[0]
+    ld = _rowmajor(cand_table, "cand_table")
+    if cand_table.shape[1] != dim:
+        raise _lib.NewsRecHIPError(f"{what}: users and cand_table must share their width")
+    _check_inv_norm(cand_inv_norm, n_news)
+    if (excl_idx is None) != (excl_off is None):
+        raise _lib.NewsRecHIPError(f"{what}: excl_idx and excl_off go together")
+    if excl_idx is not None:
+        _check_csr(excl_idx, excl_off, "excl")
+        if excl_off.numel() != n_users + 1:
+            raise _lib.NewsRecHIPError(f"{what}: excl_off must have U + 1 entries")
+        if excl_idx.numel():
+            lo, hi = (int(v) for v in torch.aminmax(excl_idx))
+            if lo < 0 or hi >= n_news:
+                raise IndexError(f"{what}: excluded row {lo if lo < 0 else hi} is outside the {n_news} table rows")
+        else:  # no storage behind an empty tensor; the kernel never reads it
+            excl_idx = torch.zeros(1, dtype=torch.int32, device=users.device)
+    return n_users, dim, n_news, ld, _dtype(cand_table, "cand_table"), excl_idx
+
+
+def _outputs(what: str, spec, out, dev, real_slots: bool = False):
+    """The optional outputs of ``what``: ``spec`` = (name, dtype, shape, wanted) per output,
+    ``out`` = the caller's tuple (None: allocate the wanted ones).  Returns (bufs, res): one
+    tensor or None per output for the call, and the wanted ones to return.  ``real_slots``
+    puts a real (unwritten) slot behind a zero-element tensor, whose data_ptr() is 0."""
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if want else None for _, dtype, shape, want in spec)
+    elif len(out) != len(spec):
+        raise _lib.NewsRecHIPError(f"{what}: out must be ({', '.join(name for name, *_ in spec)}), None for the ones "
+                                   "not wanted")
+    for t, (name, dtype, shape, want) in zip(out, spec):
+        if want and t is None:
+            raise _lib.NewsRecHIPError(f"{what}: out has no {name}")
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise _lib.NewsRecHIPError(f"{what}: out {name} must be contiguous {dtype} of shape {shape}")
+    res = tuple(t for t, (_, _, _, want) in zip(out, spec) if want)
+    if real_slots:
+        out = [t if t is None or t.numel() else torch.empty(1, dtype=t.dtype, device=dev) for t in out]
+    return out, res
+
+
 def pool_score(pooler: str, hist_table: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor,
                hist_idx: torch.Tensor, hist_off: torch.Tensor, cand_idx: torch.Tensor, cand_off: torch.Tensor,
                n_cand: int, want_users: bool = False, scores: Optional[torch.Tensor] = None):
@@ -235,8 +291,7 @@ def pool_score(pooler: str, hist_table: torch.Tensor, cand_table: torch.Tensor, 
         raise _lib.NewsRecHIPError("hist_off and cand_off must both have n_imp + 1 entries")
     if hist_table.dtype != cand_table.dtype:
         raise _lib.NewsRecHIPError("hist_table and cand_table must share a dtype")
-    if cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < cand_table.shape[0]:
-        raise _lib.NewsRecHIPError("cand_inv_norm must be f32 with one entry per candidate-table row")
+    _check_inv_norm(cand_inv_norm, cand_table.shape[0], contiguous=False)
     n_imp = hist_off.numel() - 1
     dim = cand_table.shape[1]
     # empty CSR arrays have no storage; the kernel never reads them (offsets are
@@ -335,27 +390,8 @@ def topk_users(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: tor
     entries are range-checked here (one small sync).  ``out`` = (idx, scores) to
     write into."""
     dev = _dev(users, cand_table, cand_inv_norm, excl_idx, excl_off, workspace, *(out or ()), *(_filter or ()))
-    if users.dtype != torch.float32 or users.dim() != 2 or not users.is_contiguous():
-        raise _lib.NewsRecHIPError("topk_users: users must be contiguous f32 [U, D]")
-    n_users, dim = users.shape
-    n_news = cand_table.shape[0]
-    ld = _rowmajor(cand_table, "cand_table")
-    if cand_table.shape[1] != dim:
-        raise _lib.NewsRecHIPError("topk_users: users and cand_table must share their width")
-    if cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < n_news or not cand_inv_norm.is_contiguous():
-        raise _lib.NewsRecHIPError("cand_inv_norm must be contiguous f32 with one entry per candidate-table row")
-    if (excl_idx is None) != (excl_off is None):
-        raise _lib.NewsRecHIPError("topk_users: excl_idx and excl_off go together")
-    if excl_idx is not None:
-        _check_csr(excl_idx, excl_off, "excl")
-        if excl_off.numel() != n_users + 1:
-            raise _lib.NewsRecHIPError("topk_users: excl_off must have U + 1 entries")
-        if excl_idx.numel():
-            lo, hi = (int(v) for v in torch.aminmax(excl_idx))
-            if lo < 0 or hi >= n_news:
-                raise IndexError(f"topk_users: excluded row {lo if lo < 0 else hi} is outside the {n_news} table rows")
-        else:  # no storage behind an empty tensor; the kernel never reads it
-            excl_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_users, dim, n_news, ld, dt, excl_idx = _check_scan("topk_users", users, cand_table, cand_inv_norm, excl_idx,
+                                                         excl_off)
     k = int(k)
     if out is None:
         idx = torch.empty((n_users, k), dtype=torch.int32, device=dev)
@@ -365,16 +401,11 @@ def topk_users(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: tor
         if (idx.dtype != torch.int32 or scores.dtype != torch.float32 or idx.shape != (n_users, k)
                 or scores.shape != (n_users, k) or not idx.is_contiguous() or not scores.is_contiguous()):
             raise _lib.NewsRecHIPError(f"topk_users: out must be contiguous (int32, f32) of shape {(n_users, k)}")
-    dt = _dtype(cand_table, "cand_table")
     ws = grow_workspace(workspace, topk_workspace_bytes(cand_table.dtype, n_users, n_news, k), dev)
-    if _filter is not None:
-        fptr = _check_filter("topk_users_filtered", n_users, n_news, *_filter)
-        _lib.call("nr_topk_users_filtered", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
-                  _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, k, _ptr(idx), _ptr(scores), _ptr(ws),
-                  ws.numel(), _stream(dev))
-        return idx, scores
-    _lib.call("nr_topk_users", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm),
-              _ptr(excl_idx), _ptr(excl_off), k, _ptr(idx), _ptr(scores), _ptr(ws), ws.numel(), _stream(dev))
+    fptr = [] if _filter is None else _check_filter("topk_users_filtered", n_users, n_news, *_filter)
+    _lib.call("nr_topk_users" if _filter is None else "nr_topk_users_filtered", dt, dim, n_users, _ptr(users), n_news,
+              _ptr(cand_table), ld, _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, k, _ptr(idx),
+              _ptr(scores), _ptr(ws), ws.numel(), _stream(dev))
     return idx, scores
 
 
@@ -417,15 +448,8 @@ def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: t
     small sync).  ``out`` = int32 [T] to write into."""
     dev = _dev(users, cand_table, cand_inv_norm, tgt_idx, tgt_off, excl_idx, excl_off, workspace, out,
                *(_filter or ()))
-    if users.dtype != torch.float32 or users.dim() != 2 or not users.is_contiguous():
-        raise _lib.NewsRecHIPError("rank_targets: users must be contiguous f32 [U, D]")
-    n_users, dim = users.shape
-    n_news = cand_table.shape[0]
-    ld = _rowmajor(cand_table, "cand_table")
-    if cand_table.shape[1] != dim:
-        raise _lib.NewsRecHIPError("rank_targets: users and cand_table must share their width")
-    if cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < n_news or not cand_inv_norm.is_contiguous():
-        raise _lib.NewsRecHIPError("cand_inv_norm must be contiguous f32 with one entry per candidate-table row")
+    n_users, dim, n_news, ld, dt, excl_idx = _check_scan("rank_targets", users, cand_table, cand_inv_norm, excl_idx,
+                                                         excl_off)
     _check_csr(tgt_idx, tgt_off, "tgt")
     n_tgt = tgt_idx.numel()
     if tgt_off.numel() != n_users + 1:
@@ -433,35 +457,17 @@ def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: t
     if (int(tgt_off[0]) != 0 or int(tgt_off[-1]) != n_tgt
             or (n_users > 1 and not bool((tgt_off[1:] >= tgt_off[:-1]).all()))):
         raise _lib.NewsRecHIPError(f"rank_targets: tgt_off must ascend from 0 to the {n_tgt} targets")
-    if (excl_idx is None) != (excl_off is None):
-        raise _lib.NewsRecHIPError("rank_targets: excl_idx and excl_off go together")
-    if excl_idx is not None:
-        _check_csr(excl_idx, excl_off, "excl")
-        if excl_off.numel() != n_users + 1:
-            raise _lib.NewsRecHIPError("rank_targets: excl_off must have U + 1 entries")
-        if excl_idx.numel():
-            lo, hi = (int(v) for v in torch.aminmax(excl_idx))
-            if lo < 0 or hi >= n_news:
-                raise IndexError(f"rank_targets: excluded row {lo if lo < 0 else hi} is outside the {n_news} table rows")
-        else:  # no storage behind an empty tensor; the kernel never reads it
-            excl_idx = torch.zeros(1, dtype=torch.int32, device=dev)
     if out is None:
         out = torch.empty(n_tgt, dtype=torch.int32, device=dev)
     elif out.dtype != torch.int32 or out.shape != (n_tgt,) or not out.is_contiguous():
         raise _lib.NewsRecHIPError(f"rank_targets: out must be contiguous int32 of shape {(n_tgt,)}")
-    dt = _dtype(cand_table, "cand_table")
     ws = grow_workspace(workspace, max(rank_targets_workspace_bytes(cand_table.dtype, n_users, n_news, n_tgt), 256), dev)
-    fptr = None if _filter is None else _check_filter("rank_targets_filtered", n_users, n_news, *_filter)
+    fptr = [] if _filter is None else _check_filter("rank_targets_filtered", n_users, n_news, *_filter)
     if n_tgt == 0:
         return out
-    if fptr is not None:
-        _lib.call("nr_rank_targets_filtered", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
-                  _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, n_tgt, _ptr(tgt_idx), _ptr(tgt_off),
-                  _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
-        return out
-    _lib.call("nr_rank_targets", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm),
-              _ptr(excl_idx), _ptr(excl_off), n_tgt, _ptr(tgt_idx), _ptr(tgt_off), _ptr(out), _ptr(ws), ws.numel(),
-              _stream(dev))
+    _lib.call("nr_rank_targets" if _filter is None else "nr_rank_targets_filtered", dt, dim, n_users, _ptr(users),
+              n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, n_tgt,
+              _ptr(tgt_idx), _ptr(tgt_off), _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
     return out
 
 
@@ -496,8 +502,7 @@ def rerank_mmr(cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, list_idx: 
     ld = _rowmajor(cand_table, "cand_table")
     n_news, dim = cand_table.shape
     dt = _dtype(cand_table, "cand_table")
-    if cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < n_news or not cand_inv_norm.is_contiguous():
-        raise _lib.NewsRecHIPError("cand_inv_norm must be contiguous f32 with one entry per candidate-table row")
+    _check_inv_norm(cand_inv_norm, n_news)
     if list_idx.dtype != torch.int32 or list_idx.dim() != 2 or not list_idx.is_contiguous():
         raise _lib.NewsRecHIPError("rerank_mmr: list_idx must be contiguous int32 [U, M]")
     if list_rel.dtype != torch.float32 or list_rel.shape != list_idx.shape or not list_rel.is_contiguous():
@@ -511,16 +516,7 @@ def rerank_mmr(cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, list_idx: 
     spec = (("idx", torch.int32, (n_users, k), True), ("rel", torch.float32, (n_users, k), True),
             ("pos", torch.int32, (n_users, k), want_pos), ("ild", torch.float32, (n_users, 2), want_ild),
             ("sim", torch.float32, (n_users, m, m), want_sim))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if want else None for _, dtype, shape, want in spec)
-    elif len(out) != len(spec):
-        raise _lib.NewsRecHIPError("rerank_mmr: out must be (idx, rel, pos, ild, sim), None for the ones not wanted")
-    for t, (name, dtype, shape, want) in zip(out, spec):
-        if want and t is None:
-            raise _lib.NewsRecHIPError(f"rerank_mmr: out has no {name}")
-        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
-            raise _lib.NewsRecHIPError(f"rerank_mmr: out {name} must be contiguous {dtype} of shape {shape}")
-    res = tuple(t for t, (_, _, _, want) in zip(out, spec) if want)
+    out, res = _outputs("rerank_mmr", spec, out, dev)
     if n_users == 0:
         return res
     _lib.call("nr_rerank_mmr", dt, dim, n_users, n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm), _ptr(list_idx),
@@ -554,8 +550,7 @@ def explain_scores(pooler: str, hist_table: torch.Tensor, cand_table: torch.Tens
     if hist_table.shape[1] != (2 * dim if pooler == "final" else dim):
         raise _lib.NewsRecHIPError(f"explain_scores: hist_table rows must be {'2 x ' if pooler == 'final' else ''}"
                                    f"{dim} wide for the {pooler} pooler")
-    if cand_inv_norm.dtype != torch.float32 or cand_inv_norm.numel() < n_news or not cand_inv_norm.is_contiguous():
-        raise _lib.NewsRecHIPError("cand_inv_norm must be contiguous f32 with one entry per candidate-table row")
+    _check_inv_norm(cand_inv_norm, n_news)
     if list_idx.dtype != torch.int32 or list_idx.dim() != 2 or not list_idx.is_contiguous():
         raise _lib.NewsRecHIPError("explain_scores: list_idx must be contiguous int32 [U, K]")
     n_users, k = list_idx.shape
@@ -571,24 +566,12 @@ def explain_scores(pooler: str, hist_table: torch.Tensor, cand_table: torch.Tens
     n_hist = hist_idx.numel()
     spec = (("top_pos", torch.int32, (n_users, k, top), top > 0), ("top_val", torch.float32, (n_users, k, top), top > 0),
             ("sums", torch.float32, (n_users, k), want_sum), ("matrix", torch.float32, (n_hist, k), want_matrix))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if want else None for _, dtype, shape, want in spec)
-    elif len(out) != len(spec):
-        raise _lib.NewsRecHIPError("explain_scores: out must be (top_pos, top_val, sums, matrix), None for the ones "
-                                   "not wanted")
-    for t, (name, dtype, shape, want) in zip(out, spec):
-        if want and t is None:
-            raise _lib.NewsRecHIPError(f"explain_scores: out has no {name}")
-        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
-            raise _lib.NewsRecHIPError(f"explain_scores: out {name} must be contiguous {dtype} of shape {shape}")
-    res = tuple(t for t, (_, _, _, want) in zip(out, spec) if want)
+    bufs, res = _outputs("explain_scores", spec, out, dev, real_slots=True)
     if n_users == 0:
         return res
     if want_matrix and int(hist_off[-1]) != n_hist:  # the matrix has one row per CSR row (one small sync)
         raise _lib.NewsRecHIPError(f"explain_scores: hist_off ends at {int(hist_off[-1])}, hist_idx has {n_hist} rows")
     hidx = hist_idx if n_hist else torch.zeros(1, dtype=torch.int32, device=dev)
-    # zero-element tensors report data_ptr() == 0: give the kernel a real (unwritten) slot
-    bufs = [t if t is None or t.numel() else torch.empty(1, dtype=t.dtype, device=dev) for t in out]
     _lib.call("nr_explain_scores", POOLERS[pooler], dt, dim, _ptr(hist_table), hld, n_news, _ptr(cand_table), ld,
               _ptr(cand_inv_norm), n_users, _ptr(hidx), _ptr(hist_off), _ptr(list_idx), k, max(top, 1),
               *(_ptr(t) for t in bufs), _stream(dev))

@@ -22,9 +22,10 @@ import pytest
 import torch
 
 import filter_ref
-import topk_ref
+import retrieval_cases
 from conftest import REPO
 from news_recommendation_project_v2_amd import weights as W
+from retrieval_cases import _chunk, _model, _random_users_table
 
 D = 1024
 DTYPES = [torch.float32, torch.bfloat16]
@@ -34,33 +35,13 @@ ALL = -1  # every bit of the mask
 SHAPES = ["3x1000", "130x1000", "3x2c+77", "130x2c+77"]
 
 
-def _chunk():
-    from news_recommendation_project_v2_amd import _lib
-    return int(_lib.load().nr_topk_chunk_rows())
-
-
 def _shape(name):
     return {"3x1000": (3, 1000), "130x1000": (130, 1000), "3x2c+77": (3, 2 * _chunk() + 77),
             "130x2c+77": (130, 2 * _chunk() + 77)}[name]
 
 
-def _rounded(x, dtype):
-    return torch.from_numpy(np.asarray(x, dtype=np.float32)).to(dtype).double().numpy()
-
-
-def _random_users_table(U, N, seed, zero_user=None):
-    rng = np.random.default_rng(seed)
-    table = rng.standard_normal((N, D)).astype(np.float32) * rng.uniform(0.5, 2.0, (N, 1)).astype(np.float32) + 0.05
-    users = rng.standard_normal((U, D)).astype(np.float32) * 0.7 + 0.05
-    if zero_user is not None:
-        users[zero_user] = 0.0
-    return rng, users, table
-
-
 def _csr(lists):
-    off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int64)
-    idx = (np.concatenate([np.asarray(l, dtype=np.int32) for l in lists]) if off[-1] else np.zeros(0, np.int32))
-    return idx.astype(np.int32), off
+    return retrieval_cases._csr(lists, "cpu")[:2]
 
 
 class Filter:
@@ -81,19 +62,7 @@ class Filter:
                     cat_mask=up(self.mask))
 
 
-class Case:
-    """Operands on the device and the float64 reference scores of the same operands."""
-
-    def __init__(self, users, table, dtype, dev):
-        from news_recommendation_project_v2_amd import ops
-        self.dtype, self.dev = dtype, dev
-        self.users = torch.from_numpy(np.ascontiguousarray(users, dtype=np.float32)).to(dev)
-        self.table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float32)).to(dev).to(dtype).contiguous()
-        self.inv = ops.row_inv_norm(self.table, 1e-8)
-        u64 = _rounded(users, dtype) if dtype == torch.bfloat16 else np.asarray(users, dtype=np.float32).astype(np.float64)
-        self.ref = topk_ref.cosine_scores(u64, self.table.double().cpu().numpy(), self.inv.double().cpu().numpy())
-        self.U, self.N = self.ref.shape
-
+class Case(retrieval_cases.Case):
     def _excl(self, excl):
         if excl is None:
             return {}
@@ -217,38 +186,14 @@ def _planted(k, n_news, dtype, dev, seed, spread=None, n_users=3):
     first rows and the last ones.  Every second planted row is then made ineligible, alternately
     by time (outside the window [0, 1000]) and by category (outside the mask of bits 0 .. 9)."""
     rng = np.random.default_rng(seed)
-    P = k + 8
-    q, _ = np.linalg.qr(rng.standard_normal((D, n_users)))
-    e = q.T
-    noise = rng.standard_normal((n_news, D))
-    noise -= (noise @ e.T) @ e
-    noise /= np.sqrt((noise * noise).sum(1, keepdims=True))
-    table = (-0.56 * e.sum(0))[None, :] + np.sqrt(1.0 - n_users * 0.56 ** 2) * noise
-    where = rng.permutation(n_news if spread is None else spread)[:n_users * P].reshape(n_users, P)
-    if spread is not None:
-        far = (np.arange(P) // 2) % 2 == 1
-        where[:, far] = n_news - 1 - where[:, far]
-    for u in range(n_users):
-        for j in range(P):
-            c = 0.9 - 0.02 * j
-            table[where[u, j]] = c * e[u] + np.sqrt(1.0 - c * c) * noise[where[u, j]]
-    table *= rng.uniform(0.5, 2.0, (n_news, 1))
-    users = e * np.array([1.0, 0.37, 12.5])[:n_users, None]
-    case = Case(users, table, dtype, dev)
-    excl = [np.concatenate([where[v] for v in range(n_users) if v != u]) for u in range(n_users)]
+    case, where, excl = retrieval_cases._planted(Case, k, n_news, dtype, dev, rng, n_users, spread,
+                                                 far=(np.arange(k + 8) // 2) % 2 == 1)
     news_time = rng.integers(0, 1001, n_news).astype(np.int32)
     news_cat = rng.integers(0, 10, n_news).astype(np.uint8)
     news_time[where[:, 1::4].reshape(-1)] = 1001 + rng.integers(0, 5000, where[:, 1::4].size)
     news_cat[where[:, 3::4].reshape(-1)] = rng.integers(10, 256, where[:, 3::4].size)
     flt = Filter(n_users, n_news, news_time, 0, 1000, news_cat, (1 << 10) - 1)
     assert not flt.elig[:, where[:, 1::2].reshape(-1)].any() and flt.elig[:, where[:, 0::2].reshape(-1)].all()
-    # before any call: the planted scores are >= 1e-2 apart and >= 1e-2 above the rest
-    for u in range(n_users):
-        ref = case.ref[u].copy()
-        ref[excl[u]] = -np.inf
-        top = ref[where[u]]
-        assert (top[:-1] - top[1:] >= 1e-2).all(), "planted scores closer than 1e-2"
-        assert top[-1] - np.delete(ref, where[u]).max() >= 1e-2, "last planted score within 1e-2 of the rest"
     return case, where, _csr(excl), flt
 
 
@@ -368,17 +313,6 @@ def test_gpu_filter_ranks_below_k_are_the_topk_rows(gpu_device, dtype):
 
 
 # ------------------------------------------------------------------ 7. engine
-def _model(pooler, dev):
-    from news_recommendation_project_v2_amd.latent_attention import LatentAttentionModel
-    from news_recommendation_project_v2_amd.modeling_utils import FinalAttention
-    if pooler == "final":
-        sd, m = W.final_attention_state_dict(5), FinalAttention(1024, 4096)
-    else:
-        sd, m = W.latent_attention_state_dict(5, ln_random=True), LatentAttentionModel()
-    m.load_state_dict(sd)
-    return m.to(dev).eval()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("pooler,dtype", [("final", torch.float32), ("latent", torch.bfloat16)])
 def test_gpu_engine_filters(gpu_device, pooler, dtype):

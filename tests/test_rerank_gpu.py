@@ -23,6 +23,7 @@ import torch
 
 import rerank_ref
 from news_recommendation_project_v2_amd import weights as W
+from retrieval_cases import _model
 
 D = 1024
 N_NEWS = 3000
@@ -344,17 +345,6 @@ def test_gpu_rerank_refusals_leave_outputs_untouched(gpu_device):
 
 
 # ------------------------------------------------------------------ 5. engine
-def _model(pooler, dev):
-    from news_recommendation_project_v2_amd.latent_attention import LatentAttentionModel
-    from news_recommendation_project_v2_amd.modeling_utils import FinalAttention
-    if pooler == "final":
-        sd, m = W.final_attention_state_dict(5), FinalAttention(1024, 4096)
-    else:
-        sd, m = W.latent_attention_state_dict(5, ln_random=True), LatentAttentionModel()
-    m.load_state_dict(sd)
-    return m.to(dev).eval()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("pooler,dtype", [("final", torch.float32), ("latent", torch.bfloat16)])
 def test_gpu_engine_recommend_diverse(gpu_device, pooler, dtype):

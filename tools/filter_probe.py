@@ -12,8 +12,11 @@ times with device events, after a warm-up of every shape:
 
   unfiltered       ops.topk_users / ops.rank_targets (one target per user), no exclusions
   parent           the same two entries of the library given with --parent-lib (a build of
-                   the commit before the filters), called through ctypes on the same
-                   buffers: the unfiltered instantiation must not have changed
+                   an earlier commit), called through ctypes on the same buffers: the
+                   unfiltered instantiation must not have changed.  Where that library has
+                   the filtered entries, parent_allpass times them too, and parent_equal
+                   records whether both builds return the same idx, scores and ranks, bit
+                   for bit, for the unfiltered, all-pass and f10.s cases
   allpass          the filtered entries with a window and a mask that pass every row: the
                    cost of the predicate itself
   f50 / f10 / f1   a window that leaves 50 % / 10 % / 1 % of the table eligible, the eligible
@@ -63,9 +66,13 @@ def torch_route(users, table, inv, elig, k, block):
 
 
 def parent_entries(path, users, table, inv, k, tgt, toff, dev):
-    """Closures over the parent library's nr_topk_users / nr_rank_targets on the given buffers."""
+    """The parent library's entries on the given buffers: topk(flt) and rank(flt) return closures
+    over nr_topk_users / nr_rank_targets (flt None) or their _filtered forms (flt = the five
+    filter tensors in the C order); ``filtered`` tells whether that library has the latter."""
     lib = ctypes.CDLL(str(path))
-    for name, (res, args) in {**_lib.TOPK_SIGNATURES, **_lib.FULLRANK_SIGNATURES}.items():
+    filtered = hasattr(lib, "nr_topk_users_filtered")
+    for name, (res, args) in {**_lib.TOPK_SIGNATURES, **_lib.FULLRANK_SIGNATURES,
+                              **(_lib.FILTER_SIGNATURES if filtered else {})}.items():
         getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
     U, N = users.shape[0], table.shape[0]
     p = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -75,18 +82,20 @@ def parent_entries(path, users, table, inv, k, tgt, toff, dev):
     os_ = torch.empty((U, k), dtype=torch.float32, device=dev)
     rk = torch.empty(U, dtype=torch.int32, device=dev)
     st = lambda: ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    head = (_lib.NR_BF16, 1024, U, p(users), N, p(table), table.stride(0), p(inv), None, None)
 
-    def topk():
-        rc = lib.nr_topk_users(_lib.NR_BF16, 1024, U, p(users), N, p(table), table.stride(0), p(inv), None, None, k,
-                               p(oi), p(os_), p(ws), ws.numel(), st())
-        assert rc == 0, lib.nr_last_error()
+    def entry(name, flt, *tail):
+        fn = getattr(lib, name if flt is None else name + "_filtered")
+        fptr = () if flt is None else tuple(p(t) for t in flt)
 
-    def rank():
-        rc = lib.nr_rank_targets(_lib.NR_BF16, 1024, U, p(users), N, p(table), table.stride(0), p(inv), None, None, U,
-                                 p(tgt), p(toff), p(rk), p(ws), ws.numel(), st())
-        assert rc == 0, lib.nr_last_error()
+        def call():
+            rc = fn(*head, *fptr, *tail, p(ws), ws.numel(), st())
+            assert rc == 0, lib.nr_last_error()
+        return call
 
-    return topk, rank, (oi, os_, rk)
+    topk = lambda flt=None: entry("nr_topk_users", flt, k, p(oi), p(os_))
+    rank = lambda flt=None: entry("nr_rank_targets", flt, U, p(tgt), p(toff), p(rk))
+    return topk, rank, (oi, os_, rk), filtered
 
 
 def main():
@@ -138,10 +147,13 @@ def main():
                "allpass_rank": lambda: ops.rank_targets_filtered(users, table, inv, tgt, toff, news_time=order["c"],
                                                                  time_lo=a_lo, time_hi=a_hi, news_cat=cat, cat_mask=every,
                                                                  out=ro, workspace=rws)}
-        keep = None
+        allpass = (order["c"], a_lo, a_hi, cat, every)
+        parent = None
         if args.parent_lib is not None:
-            fns["parent_topk"], fns["parent_rank"], keep = parent_entries(args.parent_lib, users, table, inv, k, tgt, toff,
-                                                                         dev)
+            parent = parent_entries(args.parent_lib, users, table, inv, k, tgt, toff, dev)
+            fns["parent_topk"], fns["parent_rank"] = parent[0](), parent[1]()
+            if parent[3]:
+                fns["parent_allpass_topk"], fns["parent_allpass_rank"] = parent[0](allpass), parent[1](allpass)
         once = {}
         for frac, tag in ((0.5, "f50"), (0.1, "f10"), (0.01, "f1")):
             n_ok = max(1, int(round(frac * N)))
@@ -171,12 +183,28 @@ def main():
         for n, fn in once.items():  # the slow baselines: one warm-up, then the median of `rounds` single passes
             timed(fn, 1)
             case[n + "_ms"] = round(statistics.median(timed(fn, 1) for _ in range(args.rounds)), 3)
+        if parent is not None and parent[3]:  # both builds on one filter: the same bits
+            def same(flt):
+                names = ("news_time", "time_lo", "time_hi", "news_cat", "cat_mask")
+                kw = {} if flt is None else dict(zip(names, flt))
+                (ops.topk_users if flt is None else ops.topk_users_filtered)(users, table, inv, k, out=o, workspace=ws, **kw)
+                (ops.rank_targets if flt is None else ops.rank_targets_filtered)(users, table, inv, tgt, toff, out=ro,
+                                                                                 workspace=rws, **kw)
+                parent[0](flt)()
+                parent[1](flt)()
+                torch.cuda.synchronize()
+                return all(torch.equal(x, y) for x, y in zip((*o, ro), parent[2]))
+
+            f10s = (order["s"], *window(0, max(1, int(round(0.1 * N))) - 1), cat, every)
+            case["parent_equal"] = {"unfiltered": same(None), "allpass": same(allpass), "f10.s": same(f10s)}
+            case["over_parent"] = {n: round(case[n + "_ms"] / case[f"parent_{n.replace('unfiltered_', '')}_ms"], 4)
+                                   for n in ("unfiltered_topk", "unfiltered_rank", "allpass_topk", "allpass_rank")}
         case["allpass_over_unfiltered_topk"] = round(case["allpass_topk_ms"] / case["unfiltered_topk_ms"], 4)
         case["allpass_over_unfiltered_rank"] = round(case["allpass_rank_ms"] / case["unfiltered_rank_ms"], 4)
         case["f1.c_over_1pct_of_unfiltered"] = round(case["f1.c_topk_ms"] / (0.01 * case["unfiltered_topk_ms"]), 2)
         print(json.dumps(case), file=sys.stderr, flush=True)
         out["cases"].append(case)
-        del ws, rws, o, ro, keep, fns, once
+        del ws, rws, o, ro, parent, fns, once
         torch.cuda.empty_cache()
     line = json.dumps(out)
     print(line, flush=True)
