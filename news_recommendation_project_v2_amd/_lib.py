@@ -19,12 +19,12 @@ INCLUDE = Path(__file__).resolve().parent.parent / "include"
 # translation units of libnewsrec_hip.so, in link order (also the hash order)
 HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip", "encoder.hip", "train.hip",
                "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip", "contrastive.hip", "topk.hip",
-               "fullrank.hip", "rerank.hip", "explain.hip")
+               "fullrank.hip", "rerank.hip", "explain.hip", "sections.hip")
 # the headers they include (every object is rebuilt when one changes), hashed after the sources
 HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CSRC / "nr_score_tile.h",
                INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
                INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h",
-               INCLUDE / "newsrec_filter.h")
+               INCLUDE / "newsrec_filter.h", INCLUDE / "newsrec_sections.h")
 
 
 def hip_source_files() -> list:
@@ -182,6 +182,14 @@ FILTER_SIGNATURES = {
                                       _l, _p]),
 }
 
+# sectioned top-K retrieval (include/newsrec_sections.h), bound by load() like SIGNATURES
+NR_SECTIONS_MAX = 16
+SECTIONS_SIGNATURES = {
+    "nr_topk_sections_workspace_bytes": (_l, [_i, _l, _l, _l, _l]),
+    "nr_topk_sections": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _p, _p, _p, _l,
+                              _p]),
+}
+
 
 class ContrastiveSpec(ctypes.Structure):
     """struct nr_contrastive_spec (include/newsrec_contrastive.h)."""
@@ -240,7 +248,7 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(os.fspath(LIB_PATH))
     for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES,
                               **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES,
-                              **FILTER_SIGNATURES}.items():
+                              **FILTER_SIGNATURES, **SECTIONS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

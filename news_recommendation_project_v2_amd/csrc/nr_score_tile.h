@@ -20,6 +20,8 @@
 //                  around the kernel's own epilogue over a finished score tile (a heap, a count).
 //   ScanArgs       host side: what nr_topk_users* and nr_rank_targets* take alike, with its
 //                  validation, launch preparation and (dtype, filtered) -> <TI, FILT> dispatch.
+//   TopkLayout     host side: the workspace of a top-K and its stage 2 (topk.hip), which the
+//                  sectioned top-K (sections.hip) runs over S lists per user.
 #pragma once
 
 #include "nr_common.h"
@@ -542,6 +544,42 @@ static int with_scan_types(const ScanArgs& a, F&& f) {
   return nr::with_dtype(
       a.dtype, [&](auto ti) { return a.flt.any() ? f(ti, std::true_type{}) : f(ti, std::false_type{}); });
 }
+
+// ---- what the top-K entries (topk.hip, sections.hip) share behind their stage 1
+struct alignas(8) Pair {
+  float s;
+  int32_t r;
+};
+
+// The workspace of a top-K that keeps K (score, row) pairs per user and chunk.
+struct TopkLayout {
+  int64_t nchunks, ub, cnt, uidx, coff, part, total;
+};
+static inline TopkLayout topk_layout(int dtype, int64_t U, int64_t N, int64_t K) {
+  TopkLayout L{};
+  L.nchunks = chunks_of(N);
+  int64_t o = 0;
+  auto take = [&](int64_t bytes) {
+    const int64_t at = o;
+    o += align256(bytes);
+    return at;
+  };
+  L.ub = take(dtype == NR_BF16 ? U * D * 2 : 0);
+  L.cnt = take(U * 4);
+  L.uidx = take(U * 4);
+  L.coff = take((U + 1) * 8);
+  L.part = take(U * L.nchunks * K * (int64_t)sizeof(Pair));
+  L.total = o;
+  return L;
+}
+
+// Stage 2 (topk.hip) over a.U users of S lists each: stage 1 left list (u, s)'s rank-sorted
+// runs of k pairs at part[((u S + s) nruns + run) k].  Merge per list, the evaluation path's
+// scores of a user's S k survivors, a rank sort per list: top_idx / top_scores [U][S][k].
+// cnt ([U] int32) is used when S == 1; with more lists per user a list's length is counted
+// from its runs again, so the workspace is topk_layout(dtype, U, N, S k) for every S.
+int topk_stage2_launch(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,
+                       int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores);
 
 }  // namespace tk
 }  // namespace nr

@@ -13,7 +13,8 @@
 //   stage 2  one wave per user: a K-round merge of the chunk lists' heads (ties by row),
 //            the survivors' rows (0 in place of a missing one: never row -1) to top_idx;
 //            the evaluation path's scoring kernel over them (score_users_dispatch) into
-//            top_scores; a rank sort of each row's <= 64 (score, row) pairs.
+//            top_scores; a rank sort of each row's <= 64 (score, row) pairs.  The sectioned
+//            top-K (sections.hip) runs the same three kernels over S lists per user.
 //
 // Every comparison is on the strict total order (score descending, row ascending), so no
 // result depends on the order in which lanes or workgroups ran.
@@ -29,11 +30,6 @@ namespace nr {
 namespace tk {
 
 constexpr int KMAX = NR_TOPK_MAX;
-
-struct alignas(8) Pair {
-  float s;
-  int32_t r;
-};
 
 __global__ __launch_bounds__(256) void topk_bf16_users_kernel(int64_t n8, const float* __restrict__ x,
                                                               __bf16* __restrict__ y) {
@@ -176,15 +172,18 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
   }
 }
 
-// One wave per user: K rounds over the heads of its chunk lists (each sorted).  Lane l
-// keeps the best head among chunks l, l + 64, ... and re-reads them only after it won.
-__global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int K, int nchunks, const Pair* __restrict__ part,
-                                                         int32_t* __restrict__ top_idx, int32_t* __restrict__ cnt_out,
-                                                         int32_t* __restrict__ uidx, int64_t* __restrict__ coff) {
+// One wave per list (S lists per user, row u = user * S + list; S = 1: one per user): K rounds
+// over the heads of its chunk lists (each sorted).  Lane l keeps the best head among chunks
+// l, l + 64, ... and re-reads them only after it won.  The scoring pass behind it takes a
+// user's S K rows as one list: uidx / coff are per user.  cnt_out may be null (topk_sort_kernel).
+__global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int S, int K, int nchunks,
+                                                         const Pair* __restrict__ part, int32_t* __restrict__ top_idx,
+                                                         int32_t* __restrict__ cnt_out, int32_t* __restrict__ uidx,
+                                                         int64_t* __restrict__ coff) {
   __shared__ uint8_t head[4][kMaxChunks];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t u = (int64_t)blockIdx.x * 4 + wave;
-  if (u >= U) return;  // wave-uniform; no block-wide barrier below
+  if (u >= U * S) return;  // wave-uniform; no block-wide barrier below
   const Pair* p = part + u * nchunks * K;
   for (int c = lane; c < nchunks; c += 64) head[wave][c] = 0;
   const float NINF = -__builtin_inff();
@@ -238,24 +237,44 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int K, int n
   }
   if (lane < K) top_idx[u * K + lane] = lane < cnt ? mine : 0;  // never row -1 to the scoring gather
   if (lane == 0) {
-    cnt_out[u] = cnt;
-    uidx[u] = (int32_t)u;
-    coff[u] = u * K;
-    if (u == U - 1) coff[U] = U * K;
+    if (cnt_out) cnt_out[u] = cnt;
+    if (u % S == 0) {
+      const int64_t user = u / S;
+      uidx[user] = (int32_t)user;
+      coff[user] = u * K;
+      if (user == U - 1) coff[U] = U * S * K;
+    }
   }
 }
 
-// One wave per user: order its <= 64 (evaluation score, row) pairs, pad the tail.
-__global__ __launch_bounds__(256) void topk_sort_kernel(int64_t U, int K, const int32_t* __restrict__ cnt_in,
+// One wave per list (R of them): order its <= 64 (evaluation score, row) pairs, pad the tail.
+// The list's length is the merge's count, or, where that was not kept (cnt_in null), counted
+// again: the rows of its runs, at most K.  L >= K: the lanes compared against -- lanes K and up
+// hold (-inf, INT32_MAX) pads, which beat nothing and are never written (a pad in lane
+// j < K still ranks j), so a short list does not pay for 64 rounds.
+template <int L>
+__global__ __launch_bounds__(256) void topk_sort_kernel(int64_t R, int K, const int32_t* __restrict__ cnt_in,
+                                                        int nchunks, const Pair* __restrict__ part,
                                                         int32_t* __restrict__ top_idx, float* __restrict__ top_scores) {
   const int lane = threadIdx.x & 63;
   const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (u >= U) return;
-  const bool valid = lane < cnt_in[u];
+  if (u >= R) return;
+  int n;
+  if (cnt_in) {
+    n = cnt_in[u];
+  } else {
+    const Pair* p = part + u * nchunks * K;
+    n = 0;
+    for (int i = lane; i < nchunks * K; i += 64) n += p[i].r >= 0 ? 1 : 0;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) n += __shfl_xor(n, m, 64);
+    n = min(n, K);
+  }
+  const bool valid = lane < n;
   const float s = valid ? top_scores[u * K + lane] : -__builtin_inff();
   const int32_t r = valid ? top_idx[u * K + lane] : INT32_MAX;
   int rank = 0;
-  for (int l = 0; l < 64; ++l) {
+  for (int l = 0; l < L; ++l) {
     const float os = __shfl(s, l, 64);
     const int32_t orow = __shfl(r, l, 64);
     rank += (better(os, orow, s, r) || (os == s && orow == r && l < lane)) ? 1 : 0;
@@ -267,27 +286,6 @@ __global__ __launch_bounds__(256) void topk_sort_kernel(int64_t U, int K, const 
   }
 }
 
-struct Layout {
-  int64_t nchunks, ub, cnt, uidx, coff, part, total;
-};
-static Layout layout(int dtype, int64_t U, int64_t N, int64_t K) {
-  Layout L{};
-  L.nchunks = chunks_of(N);
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    const int64_t at = o;
-    o += align256(bytes);
-    return at;
-  };
-  L.ub = take(dtype == NR_BF16 ? U * D * 2 : 0);
-  L.cnt = take(U * 4);
-  L.uidx = take(U * 4);
-  L.coff = take((U + 1) * 8);
-  L.part = take(U * L.nchunks * K * (int64_t)sizeof(Pair));
-  L.total = o;
-  return L;
-}
-
 }  // namespace tk
 }  // namespace nr
 
@@ -295,11 +293,35 @@ extern "C" int64_t nr_topk_chunk_rows(void) { return nr::tk::kChunk; }
 
 extern "C" int64_t nr_topk_workspace_bytes(int dtype, int64_t U, int64_t N, int64_t K) {
   if (!nr::tk::scan_shape_ok(dtype, U, N) || K < 1 || K > nr::tk::KMAX) return -1;
-  return nr::tk::layout(dtype, U, N, K).total;
+  return nr::tk::topk_layout(dtype, U, N, K).total;
 }
 
 namespace nr {
 namespace tk {
+
+int topk_stage2_launch(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,
+                       int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores) {
+  hipStream_t st = (hipStream_t)a.stream;
+  const int64_t R = a.U * S;
+  const dim3 gw((unsigned)((R + 3) / 4));
+  if (S != 1) cnt = nullptr;
+  hipLaunchKernelGGL(topk_merge_kernel, gw, dim3(256), 0, st, a.U, (int)S, (int)k, nruns, part, top_idx, cnt, uidx,
+                     coff);
+  NR_CHECK_LAUNCH(fn);
+  const int rc = nr::score_users_dispatch(a.dtype, a.users, uidx, a.cand_table, a.cand_ld, a.cand_inv_norm, top_idx,
+                                          coff, a.U, top_scores, st);
+  if (rc) return rc;
+  const int rc2 = nr::with_int<8, 16, 32, 64>(
+      k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64, [&] { return nr::unvalidated_code("top-K list length", (int)k); },
+      [&](auto lanes) {
+        hipLaunchKernelGGL(topk_sort_kernel<decltype(lanes)::value>, gw, dim3(256), 0, st, R, (int)k,
+                           (const int32_t*)cnt, nruns, part, top_idx, top_scores);
+        return NR_OK;
+      });
+  if (rc2) return rc2;
+  NR_CHECK_LAUNCH(fn);
+  return NR_OK;
+}
 
 // nr_topk_users and nr_topk_users_filtered: one validation, one launch sequence.  A filter with
 // both pairs null runs the unfiltered stage 1.
@@ -311,7 +333,7 @@ static int topk_run(const char* fn, const ScanArgs& a, int64_t K, int32_t* top_i
   };
   if (const int rc = check_scan(fn, a, k_ok, no_check)) return rc;
   NR_CHECK_ARG(top_idx && top_scores && ws, "%s: null pointer", fn);
-  const Layout L = layout(a.dtype, a.U, a.N, K);
+  const TopkLayout L = topk_layout(a.dtype, a.U, a.N, K);
   NR_CHECK_ARG(ws_bytes >= L.total, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes,
                (long long)L.total);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
@@ -335,16 +357,7 @@ static int topk_run(const char* fn, const ScanArgs& a, int64_t K, int32_t* top_i
   });
   if (rc1) return rc1;
   NR_CHECK_LAUNCH(fn);
-  const dim3 gw((unsigned)((U + 3) / 4));
-  hipLaunchKernelGGL(topk_merge_kernel, gw, dim3(256), 0, st, U, (int)K, (int)sl.g1.y, (const Pair*)part, top_idx, cnt,
-                     uidx, coff);
-  NR_CHECK_LAUNCH(fn);
-  const int rc = nr::score_users_dispatch(a.dtype, a.users, uidx, a.cand_table, a.cand_ld, a.cand_inv_norm, top_idx,
-                                          coff, U, top_scores, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(topk_sort_kernel, gw, dim3(256), 0, st, U, (int)K, (const int32_t*)cnt, top_idx, top_scores);
-  NR_CHECK_LAUNCH(fn);
-  return NR_OK;
+  return topk_stage2_launch(fn, a, 1, K, (int)sl.g1.y, part, cnt, uidx, coff, top_idx, top_scores);
 }
 
 }  // namespace tk

@@ -143,7 +143,7 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
                               exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
                               dtype=None, diversify: Optional[float] = None, pool: Optional[int] = None,
                               news_time=None, news_category=None, time_window=None, categories=None,
-                              explain: Optional[int] = None) -> dict:
+                              sections=None, explain: Optional[int] = None) -> dict:
     """The k news of the WHOLE table that the model recommends per impression:
     ``{"news_index": int32 [I, k], "scores": float32 [I, k]}`` on the host, score
     descending, ties by ascending news row, ``(-1, -inf)`` where fewer than k news are
@@ -177,7 +177,24 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     = (lo, hi) keeps the news with lo <= news_time <= hi, ``news_category`` [N] ids (0 .. 63)
     with ``categories`` = a 64-bit mask keeps the news whose category's bit is set; window
     and mask are scalars or one value per impression.  Every mode above then draws from the
-    eligible news only."""
+    eligible news only.
+
+    ``sections`` = a sequence of disjoint sections, each a 64-bit category mask or an iterable
+    of category ids (0 .. 63), builds a front page (PoolScoreEngine.recommend_sections,
+    include/newsrec_sections.h): ``news_index`` and ``scores`` are then [I, S, k], the k best
+    eligible news of each section from one walk over the table, and ``k`` means per section
+    (S <= 16, S * k <= 64).  It needs ``news_category`` and composes with ``time_window``;
+    with ``categories``, ``diversify`` or ``explain`` it is refused."""
+    if sections is not None:
+        if categories is not None or diversify is not None or explain is not None or pool is not None:
+            raise ValueError("get_top_k_recommendations: sections cannot be combined with categories, diversify or "
+                             "explain")
+        from .engine import section_masks
+        section_masks(sections)  # a bad item is refused before any device work
+        if news_category is None:
+            raise ValueError("get_top_k_recommendations: sections needs news_category")
+        if time_window is not None and news_time is None:
+            raise ValueError("get_top_k_recommendations: time_window needs news_time")
     if diversify is None and pool is not None:
         raise ValueError("get_top_k_recommendations: pool needs diversify")
     if explain is not None and not 1 <= int(explain) <= 8:
@@ -187,6 +204,10 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
                   dtype=dtype)
     n = len(history_len_list)
     eng.load_impressions(history_rev_index, history_len_list, np.zeros(0, np.int32), np.zeros(n, np.int32))
+    if sections is not None:
+        eng.set_catalogue(news_time=news_time, news_cat=news_category)
+        idx, scores = eng.recommend_sections(k, sections, exclude_history=exclude_history, time_window=time_window)
+        return {"news_index": _host(idx), "scores": _host(scores)}
     flt = {}
     if time_window is not None or categories is not None:
         eng.set_catalogue(news_time=news_time, news_cat=news_category)

@@ -78,6 +78,28 @@ def _upload(x, dev: torch.device, dtype: Optional[torch.dtype] = None) -> torch.
     return (t if dtype is None or t.dtype == dtype else t.to(dtype)).contiguous()
 
 
+def section_masks(sections) -> list:
+    """recommend_sections' ``sections`` as 64-bit masks (Python ints): an item is either a
+    mask (an integer: the same 64 bits as a Python int, int64 or uint64) or an iterable of
+    category ids 0 .. 63."""
+    if isinstance(sections, (str, bytes)) or not hasattr(sections, "__iter__"):
+        raise ValueError("sections must be a sequence of category masks or of category-id lists")
+    masks = []
+    for item in sections:
+        if isinstance(item, (int, np.integer)) and not isinstance(item, bool):
+            masks.append(int(item) & 0xFFFFFFFFFFFFFFFF)
+            continue
+        if isinstance(item, (str, bytes)) or not hasattr(item, "__iter__"):
+            raise ValueError(f"a section must be a 64-bit mask or an iterable of category ids, got {item!r}")
+        m = 0
+        for c in item:
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < 64:
+                raise ValueError(f"a section's category ids must be integers in 0 .. 63, got {c!r}")
+            m |= 1 << int(c)
+        masks.append(m)
+    return masks
+
+
 class _Queries:
     """The distinct (history, time window, category mask) tuples of the loaded impressions
     under a catalogue filter: retrieval and ranks run once per query."""
@@ -377,6 +399,52 @@ class PoolScoreEngine:
         idx, scores = self._recommend_distinct(k, exclude_history, user_block, q)
         sel = self._expansion(q)
         if sel is not None and idx.shape[0]:
+            return idx[sel], scores[sel]
+        return idx, scores
+
+    def recommend_sections(self, k: int, sections, exclude_history: bool = True, user_block: Optional[int] = None,
+                           time_window=None):
+        """A front page per impression: the k best eligible news of each of S sections, from
+        ONE walk over the table (ops.topk_sections): (idx int32 [I, S, k], scores f32
+        [I, S, k]).  ``sections`` is a sequence whose items are a 64-bit category mask or an
+        iterable of category ids (0 .. 63); the sections are disjoint, at most 16, and
+        S * k <= 64.  Section s equals recommend(k, categories=mask_s, time_window=...) bit
+        for bit.  Needs set_catalogue(news_cat=...), with ``time_window`` also news_time.
+        Users are pooled once per distinct history and the table is searched once per
+        distinct (history, lo, hi); the results do not depend on ``user_block``."""
+        masks = section_masks(sections)
+        k, n_sec = int(k), len(masks)
+        if not 1 <= n_sec <= 16 or k < 1 or n_sec * k > 64:
+            raise ValueError(f"recommend_sections: {n_sec} sections of k = {k} (1 .. 16 sections, k >= 1, "
+                             "sections * k <= 64)")
+        for i in range(n_sec):
+            for j in range(i):
+                if masks[i] & masks[j]:
+                    raise ValueError(f"recommend_sections: sections {j} and {i} share a category (sections are "
+                                     "disjoint)")
+        if self.news_cat is None:
+            raise ValueError("sections needs set_catalogue(news_cat=...)")
+        if self.news_cat.numel() != self.cand_table.shape[0]:
+            raise ValueError("the catalogue attributes must have one entry per news")
+        q = self._queries(time_window, None)
+        self.hist_table = self.transform(out=self.hist_table)
+        self.inv_norms()
+        hidx, hoff = self._distinct_hist()
+        n_rows = hoff.numel() - 1 if q is None else q.n
+        idx = torch.empty((n_rows, n_sec, k), dtype=torch.int32, device=self.device)
+        scores = torch.empty((n_rows, n_sec, k), dtype=torch.float32, device=self.device)
+        if n_rows == 0:
+            return idx, scores
+        users = self._pooled_users(hidx, hoff)
+        blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
+        need = ops.topk_sections_workspace_bytes(self.dtype, blk, self.cand_table.shape[0], n_sec, k)
+        self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, self.device)
+        for a, b, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history):
+            ops.topk_sections(rows, self.cand_table, self.cand_inv, k, masks, self.news_cat,
+                              news_time=flt.get("news_time"), time_lo=flt.get("time_lo"), time_hi=flt.get("time_hi"),
+                              excl_idx=eidx, excl_off=eoff, out=(idx[a:b], scores[a:b]), workspace=self._topk_ws)
+        sel = self._expansion(q)
+        if sel is not None:
             return idx[sel], scores[sel]
         return idx, scores
 

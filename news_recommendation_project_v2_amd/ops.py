@@ -424,6 +424,64 @@ def topk_users_filtered(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_
                       workspace=workspace, _filter=(news_time, time_lo, time_hi, news_cat, cat_mask))
 
 
+def section_masks(sections) -> list:
+    """``sections`` (a sequence of 64-bit masks: Python ints, int64 or uint64) as a list of
+    Python ints in [0, 2^64): the same 64 bits whichever way they came."""
+    if isinstance(sections, torch.Tensor):
+        sections = sections.reshape(-1).tolist()
+    return [int(v) & 0xFFFFFFFFFFFFFFFF for v in sections]
+
+
+def topk_sections_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, n_sections: int, k: int) -> int:
+    """nr_topk_sections_workspace_bytes (include/newsrec_sections.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_topk_sections_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, n_sections, k))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"topk_sections: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, S = {n_sections}, "
+            f"k = {k}; S in [1, {_lib.NR_SECTIONS_MAX}], k >= 1, S * k <= {_lib.NR_TOPK_MAX}, N <= 2^22)")
+    return need
+
+
+def topk_sections(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int, sections,
+                  news_cat: torch.Tensor, news_time: Optional[torch.Tensor] = None,
+                  time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
+                  excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None, out=None,
+                  workspace: Optional[torch.Tensor] = None):
+    """The k best eligible rows of each of S sections per user row, from one walk over the
+    table (nr_topk_sections): returns (idx int32 [U, S, k], scores f32 [U, S, k]).
+    ``sections`` is a sequence of S disjoint 64-bit category masks (Python ints, int64 or
+    uint64), the same for every user; ``news_cat`` uint8 [N].  Section s of the result
+    equals topk_users_filtered(k, cat_mask = sections[s]) with the same time window and
+    exclusion lists, bit for bit."""
+    dev = _dev(users, cand_table, cand_inv_norm, news_cat, news_time, time_lo, time_hi, excl_idx, excl_off, workspace,
+               *(out or ()))
+    n_users, dim, n_news, ld, dt, excl_idx = _check_scan("topk_sections", users, cand_table, cand_inv_norm, excl_idx,
+                                                         excl_off)
+    if (news_cat is None or news_cat.dtype != torch.uint8 or news_cat.dim() != 1 or news_cat.numel() != n_news
+            or not news_cat.is_contiguous()):
+        raise _lib.NewsRecHIPError(f"topk_sections: news_cat must be contiguous torch.uint8 [{n_news}]")
+    masks = section_masks(sections)
+    n_sec, k = len(masks), int(k)
+    tptr = _check_filter("topk_sections", n_users, n_news, news_time, time_lo, time_hi, None, None)[:3]
+    tptr.append(_ptr(news_cat))
+    need = topk_sections_workspace_bytes(cand_table.dtype, n_users, n_news, n_sec, k)
+    shape = (n_users, n_sec, k)
+    if out is None:
+        idx = torch.empty(shape, dtype=torch.int32, device=dev)
+        scores = torch.empty(shape, dtype=torch.float32, device=dev)
+    else:
+        idx, scores = out
+        if (idx.dtype != torch.int32 or scores.dtype != torch.float32 or tuple(idx.shape) != shape
+                or tuple(scores.shape) != shape or not idx.is_contiguous() or not scores.is_contiguous()):
+            raise _lib.NewsRecHIPError(f"topk_sections: out must be contiguous (int32, f32) of shape {shape}")
+    ws = grow_workspace(workspace, need, dev)
+    sec = (ctypes.c_uint64 * n_sec)(*masks)  # read on the host, before the call returns
+    _lib.call("nr_topk_sections", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm),
+              _ptr(excl_idx), _ptr(excl_off), *tptr, ctypes.cast(sec, ctypes.c_void_p), n_sec, k, _ptr(idx),
+              _ptr(scores), _ptr(ws), ws.numel(), _stream(dev))
+    return idx, scores
+
+
 def rank_targets_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, n_targets: int) -> int:
     """nr_rank_targets_workspace_bytes (include/newsrec_fullrank.h); raises on a shape the entry refuses."""
     need = int(_lib.load().nr_rank_targets_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, n_targets))

@@ -9,6 +9,7 @@ has no counterpart -- it only scores the candidates an impression lists).
     python scripts/recommend.py --synthetic --diversify 0.7 [--pool 64]
     python scripts/recommend.py --synthetic --explain 3
     python scripts/recommend.py --synthetic --evaluate --as-of [--fresh 48] [--categories 0,3,7]
+    python scripts/recommend.py --synthetic --sections "0,1;2;3,4,5" -k 4 [--as-of [--fresh 24]]
 
 Prints one JSON line per run and writes {out-dir}/recommendations.npy: an int32
 [I, K] array of rows of the split's news list (-1 where fewer than K are eligible).
@@ -37,6 +38,14 @@ rank -1 and count as misses).  --categories A,B,... keeps the news of those cate
 (names of data-dir/categories.json; ids with --synthetic).  The JSON line gains
 mean_eligible_news, the mean size of the catalogue an impression sees: it is nearly empty
 at the start of a split, which the metrics of the first impressions reflect.
+--sections "A,B;C;D" builds a front page: sections separated by ';', each a list of categories
+named as for --categories, disjoint, at most 16, and -k news PER SECTION (sections x k <= 64),
+all from one walk over the table.  recommendations.npy is then int32 [I, S, K], and
+{out-dir}/recommendations_sections.npz holds the page: news_index int32 and scores float32
+[I, S, K], sections (the S names as given) and news_category uint8 [N] (the category of each
+row of the news list).  The JSON line gains section_fill, per section the share of its slots
+that hold a news.  It composes with --as-of
+and --fresh and is refused with --categories, --diversify, --explain and --evaluate.
 """
 from __future__ import annotations
 
@@ -60,9 +69,22 @@ from news_recommendation_project_v2_amd.modeling_utils import FinalAttention  # 
 from news_recommendation_project_v2_amd.pipeline import Pipeline  # noqa: E402
 
 
+def category_ids(want, args, what: str) -> list:
+    """Category names (ids with --synthetic) to ids 0 .. 63."""
+    if args.synthetic:
+        ids = [int(c) for c in want]
+    else:
+        names = json.loads((args.data_dir / "categories.json").read_text())
+        ids = [int(names[c]) for c in want]
+    if any(not 0 <= c < 64 for c in ids):
+        raise SystemExit(f"{what}: only category ids 0 .. 63 can be asked for")
+    return ids
+
+
 def catalogue_filter(args, out, ctx) -> dict:
-    """get_top_k_recommendations' filter arguments for --as-of / --fresh / --categories ({} without them)."""
-    if not args.as_of and args.categories is None:
+    """get_top_k_recommendations' filter arguments for --as-of / --fresh / --categories /
+    --sections ({} without them)."""
+    if not args.as_of and args.categories is None and args.sections is None:
         return {}
     from news_recommendation_project_v2_amd import synthetic
     from news_recommendation_project_v2_amd.data_utils import catalogue_first_seen, read_behavior_times
@@ -83,28 +105,28 @@ def catalogue_filter(args, out, ctx) -> dict:
         lo = (when.astype(np.int64) - int(round(args.fresh * 3600)) if args.fresh is not None
               else np.full(n_imp, np.iinfo(np.int32).min, np.int64))
         flt["time_window"] = (np.maximum(lo, np.iinfo(np.int32).min).astype(np.int32), when.astype(np.int32))
-    if args.categories is not None:
-        want = [c.strip() for c in args.categories.split(",") if c.strip()]
-        if args.synthetic:
-            ids = [int(c) for c in want]
-        else:
-            names = json.loads((args.data_dir / "categories.json").read_text())
-            ids = [int(names[c]) for c in want]
+    if args.categories is not None or args.sections is not None:
+        if not args.synthetic:
             per_news = ctx.get("news_category", {})
             news_cat = np.array([per_news.get(n, 255) for n in news_list], dtype=np.float64)
             news_cat = np.where(np.isfinite(news_cat) & (news_cat >= 0) & (news_cat < 64), news_cat, 255).astype(np.uint8)
-        if any(not 0 <= c < 64 for c in ids):
-            raise SystemExit("--categories: only category ids 0 .. 63 can be asked for")
         flt["news_category"] = np.asarray(news_cat, dtype=np.uint8)
+    if args.categories is not None:
+        ids = category_ids([c.strip() for c in args.categories.split(",") if c.strip()], args, "--categories")
         flt["categories"] = np.array([sum(1 << c for c in set(ids))], dtype=np.uint64)
+    if args.sections is not None:
+        flt["sections"] = [category_ids([c.strip() for c in sec.split(",") if c.strip()], args, "--sections")
+                           for sec in args.sections.split(";")]
     return flt
 
 
 def mean_eligible(flt: dict) -> float:
     """Mean number of news inside an impression's window and mask (the exclusion of its own history aside)."""
     ok = np.ones(len(flt["news_time"] if "news_time" in flt else flt["news_category"]), dtype=bool)
-    if "categories" in flt:
-        wanted = np.array([(int(flt["categories"][0]) >> c) & 1 for c in range(64)], dtype=bool)
+    if "sections" in flt or "categories" in flt:
+        bits = (sum(1 << c for sec in flt["sections"] for c in sec) if "sections" in flt
+                else int(flt["categories"][0]))
+        wanted = np.array([(bits >> c) & 1 for c in range(64)], dtype=bool)
         ok &= (flt["news_category"] < 64) & wanted[np.minimum(flt["news_category"], 63)]
         if "news_time" not in flt:
             return float(ok.sum())
@@ -142,7 +164,15 @@ def main():
                     help="with --as-of: only the news first seen in the last HOURS before the impression")
     ap.add_argument("--categories", default=None, metavar="A,B,...",
                     help="only news of these categories (names; ids with --synthetic)")
+    ap.add_argument("--sections", default=None, metavar="A,B;C;...",
+                    help="a front page: -k news for each of these sections of categories (names; ids with "
+                         "--synthetic), from one walk over the table")
     args = ap.parse_args()
+    if args.sections is not None:
+        for flag, on in (("--categories", args.categories is not None), ("--diversify", args.diversify is not None),
+                         ("--explain", args.explain is not None), ("--evaluate", args.evaluate)):
+            if on:
+                ap.error(f"--sections cannot be combined with {flag}")
     if args.pool is not None and args.diversify is None:
         ap.error("--pool needs --diversify")
     if args.fresh is not None and not args.as_of:
@@ -189,8 +219,15 @@ def main():
     line = {"split": args.split, "pooler": args.pooler, "dtype": args.dtype, "k": args.k,
             "exclude_history": not args.keep_history, "impressions": int(idx.shape[0]),
             "news": int(out["news_embeddings"].shape[0]), "filled": float(have.mean()) if idx.size else 1.0,
-            "mean_top1_score": float(scores[:, 0][have[:, 0]].mean()) if have[:, :1].any() else None,
+            "mean_top1_score": float(scores[..., 0][have[..., 0]].mean()) if have[..., :1].any() else None,
             "ms": round(ms, 1), "out": str(path)}
+    if args.sections is not None:
+        names = [sec.strip() for sec in args.sections.split(";")]
+        sec_path = args.out_dir / "recommendations_sections.npz"
+        np.savez(sec_path, news_index=idx, scores=scores, sections=np.array(names),
+                 news_category=flt["news_category"])
+        line.update(sections=names, sections_out=str(sec_path),
+                    section_fill=[float(have[:, s].mean()) if have[:, s].size else 1.0 for s in range(len(names))])
     if flt:
         line.update(as_of=args.as_of, fresh_hours=args.fresh, categories=args.categories,
                     mean_eligible_news=mean_eligible(flt))
