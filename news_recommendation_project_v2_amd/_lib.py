@@ -24,7 +24,7 @@ HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip
 HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CSRC / "nr_score_tile.h",
                INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
                INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h",
-               INCLUDE / "newsrec_filter.h", INCLUDE / "newsrec_sections.h")
+               INCLUDE / "newsrec_filter.h", INCLUDE / "newsrec_sections.h", INCLUDE / "newsrec_prior.h")
 
 
 def hip_source_files() -> list:
@@ -190,6 +190,21 @@ SECTIONS_SIGNATURES = {
                               _p]),
 }
 
+# the rank-one prior of retrieval, ranks and sections (include/newsrec_prior.h), bound by load() like
+# SIGNATURES: the filtered / sectioned entries' arguments with news_prior and user_gain behind the
+# mask pointer and top_keys behind top_scores
+PRIOR_SIGNATURES = {
+    "nr_topk_users_prior_workspace_bytes": (_l, [_i, _l, _l, _l]),
+    "nr_topk_users_prior": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p,
+                                 _p, _l, _p]),
+    "nr_rank_targets_prior_workspace_bytes": (_l, [_i, _l, _l, _l]),
+    "nr_rank_targets_prior": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p,
+                                   _p, _p, _l, _p]),
+    "nr_topk_sections_prior_workspace_bytes": (_l, [_i, _l, _l, _l, _l]),
+    "nr_topk_sections_prior": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _p,
+                                    _p, _p, _p, _l, _p]),
+}
+
 
 class ContrastiveSpec(ctypes.Structure):
     """struct nr_contrastive_spec (include/newsrec_contrastive.h)."""
@@ -248,7 +263,7 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(os.fspath(LIB_PATH))
     for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES,
                               **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES,
-                              **FILTER_SIGNATURES, **SECTIONS_SIGNATURES}.items():
+                              **FILTER_SIGNATURES, **SECTIONS_SIGNATURES, **PRIOR_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

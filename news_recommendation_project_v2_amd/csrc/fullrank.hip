@@ -33,6 +33,7 @@
 
 #include "../../include/newsrec_filter.h"
 #include "../../include/newsrec_fullrank.h"
+#include "../../include/newsrec_prior.h"
 
 namespace nr {
 namespace tk {
@@ -42,8 +43,10 @@ constexpr int TCAP = 32;  // targets of a user whose thresholds and counters sta
 __device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // FILT (here and in rank_count_kernel): the catalogue filter of include/newsrec_filter.h; the
-// unfiltered instantiations hold none of it.
-template <typename TI, bool FILT>
+// unfiltered instantiations hold none of it.  PRIOR (here and in rank_count_kernel): the
+// rank-one prior of include/newsrec_prior.h; thresholds and counted scores are then selection
+// keys from the same ScoreTile chain, the gathered rows' priors staged next to their cand_inv.
+template <typename TI, bool FILT, bool PRIOR>
 __global__ __launch_bounds__(256) void rank_thresholds_kernel(int64_t U, int64_t N, int64_t Tn,
                                                               const TI* __restrict__ users,
                                                               const TI* __restrict__ tab, int64_t ldt,
@@ -52,11 +55,14 @@ __global__ __launch_bounds__(256) void rank_thresholds_kernel(int64_t U, int64_t
                                                               const int64_t* __restrict__ excl_off, FilterArgs flt,
                                                               const int32_t* __restrict__ tgt_idx,
                                                               const int64_t* __restrict__ tgt_off,
-                                                              float* __restrict__ tsel, int32_t* __restrict__ rank) {
+                                                              float* __restrict__ tsel, int32_t* __restrict__ rank,
+                                                              PriorArgs pri) {
   __shared__ __attribute__((aligned(16))) uint32_t smem[4 * TILE_WORDS];  // ring [2][news | users]; score tile
   __shared__ __attribute__((aligned(16))) float cinv_s[TS];
   __shared__ int32_t grow_s[2][TS];  // table rows behind the current and the next tile's news rows
   __shared__ int toff_s[TS + 1];     // the block's target offsets, minus the first
+  __shared__ __attribute__((aligned(16))) float prior_s[PRIOR ? TS : 4];  // the gathered rows' priors
+  __shared__ float gsel_s[PRIOR ? TS : 1];                                //   and the block's scaled gains
   const float* T = reinterpret_cast<const float*>(smem);
 
   const int tid = threadIdx.x;
@@ -68,8 +74,11 @@ __global__ __launch_bounds__(256) void rank_thresholds_kernel(int64_t U, int64_t
   const int ntiles = (int)((tb1 - tb0 + TS - 1) / TS);
   if (ntiles == 0) return;  // block-uniform: none of these users has a target
   if (tid <= nu) toff_s[tid] = (int)(clamp64(tgt_off[m0 + tid], tb0, tb1) - tb0);
+  if constexpr (PRIOR) {
+    if (tid < TS) gsel_s[tid] = tid < nu ? pri.gsel[m0 + tid] : 0.f;
+  }
 
-  ScoreTile<TI> st(smem, cinv_s, users, m0, U);
+  ScoreTile<TI, PRIOR> st(smem, cinv_s, users, m0, U, prior_s, gsel_s);
   auto fill_rows = [&](int tile, int buf) __attribute__((always_inline)) {
     if (tid < TS) {
       const int64_t j = tb0 + (int64_t)tile * TS + tid;
@@ -90,6 +99,9 @@ __global__ __launch_bounds__(256) void rank_thresholds_kernel(int64_t U, int64_t
     // it is read again after this tile's first barrier)
     if (tile + 1 < ntiles) fill_rows(tile + 1, buf ^ 1);
     if (tid < TS) cinv_s[tid] = cinv[grow_s[buf][tid]];
+    if constexpr (PRIOR) {
+      if (tid < TS) prior_s[tid] = pri.news_prior[grow_s[buf][tid]];
+    }
     st.scores(tab, ldt, rows_of(buf), tile + 1 < ntiles, rows_of(buf ^ 1), TS);
     const int64_t j = tb0 + (int64_t)tile * TS + tid;
     if (tid < TS && j < tb1) {
@@ -143,7 +155,7 @@ __device__ __forceinline__ int count_better(const int (&k)[64], int K, int32_t t
   return c;
 }
 
-template <typename TI, bool FILT>
+template <typename TI, bool FILT, bool PRIOR>
 __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, int64_t Tn,
                                                          const TI* __restrict__ users, const TI* __restrict__ tab,
                                                          int64_t ldt, const float* __restrict__ cinv,
@@ -152,7 +164,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
                                                          const int32_t* __restrict__ tgt_idx,
                                                          const int64_t* __restrict__ tgt_off,
                                                          const float* __restrict__ tsel, int64_t span_rows,
-                                                         int32_t* __restrict__ rank) {
+                                                         int32_t* __restrict__ rank, PriorArgs pri) {
   __shared__ __attribute__((aligned(16))) uint32_t smem[4 * TILE_WORDS];  // ring [2][news | users]; score tile
   __shared__ __attribute__((aligned(16))) float cinv_s[TS];
   __shared__ uint16_t ex_s[XCAP * TS];
@@ -162,10 +174,12 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
   __shared__ int tc_s[TCAP * TS];      //   and counters (both threads of a user add to one)
   __shared__ __attribute__((aligned(16))) int32_t ft_s[FILT ? ATTR_TIME_WORDS : 4];  // the tile's news times
   __shared__ uint32_t fc_s[FILT ? ATTR_CAT_WORDS : 1];                                //   and categories
+  __shared__ __attribute__((aligned(16))) float prior_s[PRIOR ? TS : 4];  // the tile's priors
+  __shared__ float gsel_s[PRIOR ? TS : 1];                                //   and the block's scaled gains
 
   const float NINF = -__builtin_inff();
-  ChunkWalk<TI, FILT> w(smem, cinv_s, ex_s, ov_mask, ft_s, fc_s, U, N, users, tab, ldt, cinv, excl_idx, excl_off, flt,
-                        span_rows);
+  ChunkWalk<TI, FILT, PRIOR> w(smem, cinv_s, ex_s, ov_mask, ft_s, fc_s, U, N, users, tab, ldt, cinv, excl_idx,
+                               excl_off, flt, span_rows, prior_s, gsel_s, pri);
   // threads 2u and 2u + 1 serve user u of the block: 64 scores of a tile each
   const int su = w.su, sh = w.sh;
   int64_t t0 = 0, t1 = 0;  // the user's targets (clamped into [0, T])
@@ -242,12 +256,13 @@ __global__ __launch_bounds__(256) void rank_count_kernel(int64_t U, int64_t N, i
 }
 
 struct RankLayout {
-  int64_t tsel, total;  // (the NR_BF16 users sit at offset 0)
+  int64_t tsel, gsel, total;  // (the NR_BF16 users sit at offset 0; with a prior, U scaled gains at the end)
 };
-static RankLayout rank_layout(int dtype, int64_t U, int64_t T) {
+static RankLayout rank_layout(int dtype, int64_t U, int64_t T, bool prior = false) {
   RankLayout L{};
   L.tsel = align256(dtype == NR_BF16 ? U * D * 2 : 0);
-  L.total = L.tsel + align256(T * 4);
+  L.gsel = L.tsel + align256(T * 4);
+  L.total = L.gsel + align256(prior ? U * 4 : 0);
   return L;
 }
 
@@ -262,17 +277,18 @@ extern "C" int64_t nr_rank_targets_workspace_bytes(int dtype, int64_t U, int64_t
 namespace nr {
 namespace tk {
 
-// nr_rank_targets and nr_rank_targets_filtered: one validation, one launch sequence.  A filter
-// with both pairs null runs the unfiltered kernels.
+// nr_rank_targets, nr_rank_targets_filtered and nr_rank_targets_prior: one validation, one launch
+// sequence.  A filter with both pairs null runs the unfiltered kernels, a null prior the kernels
+// without one.  keyed: the prior entry (its workspace holds the scaled gains).
 static int rank_run(const char* fn, const ScanArgs& a, int64_t T, const int32_t* tgt_idx, const int64_t* tgt_off,
-                    int32_t* rank, void* ws, int64_t ws_bytes) {
+                    int32_t* rank, void* ws, int64_t ws_bytes, bool keyed = false) {
   auto t_ok = [&] {
     NR_CHECK_ARG(T >= 0 && T < (1ll << 31), "%s: T = %lld outside [0, 2^31)", fn, (long long)T);
     return NR_OK;
   };
   if (const int rc = check_scan(fn, a, no_check, t_ok)) return rc;
   NR_CHECK_ARG(tgt_off && ws && (T == 0 || (tgt_idx && rank)), "%s: null pointer", fn);
-  const RankLayout L = rank_layout(a.dtype, a.U, T);
+  const RankLayout L = rank_layout(a.dtype, a.U, T, keyed);
   NR_CHECK_ARG(ws_bytes >= L.total, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes,
                (long long)L.total);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
@@ -286,17 +302,19 @@ static int rank_run(const char* fn, const ScanArgs& a, int64_t T, const int32_t*
     return NR_ERR_HIP;
   }
   ScanLaunch sl;
-  if (const int rc = scan_prepare(fn, a, ws, sl)) return rc;
-  return with_scan_types(a, [&](auto ti, auto filt) {
+  float* gsel = (float*)((char*)ws + L.gsel);
+  if (const int rc = scan_prepare(fn, a, ws, sl, gsel)) return rc;
+  const PriorArgs pri{a.news_prior, gsel};
+  return with_scan_types(a, [&](auto ti, auto filt, auto prior) {
     using TI = typename decltype(ti)::type;
-    constexpr bool F = decltype(filt)::value;
-    hipLaunchKernelGGL((rank_thresholds_kernel<TI, F>), sl.g0, dim3(256), 0, st, a.U, a.N, T, (const TI*)sl.urows,
+    constexpr bool F = decltype(filt)::value, P = decltype(prior)::value;
+    hipLaunchKernelGGL((rank_thresholds_kernel<TI, F, P>), sl.g0, dim3(256), 0, st, a.U, a.N, T, (const TI*)sl.urows,
                        (const TI*)a.cand_table, a.cand_ld, a.cand_inv_norm, a.excl_idx, a.excl_off, a.flt, tgt_idx,
-                       tgt_off, tsel, rank);
+                       tgt_off, tsel, rank, pri);
     NR_CHECK_LAUNCH(fn);
-    hipLaunchKernelGGL((rank_count_kernel<TI, F>), sl.g1, dim3(256), 0, st, a.U, a.N, T, (const TI*)sl.urows,
+    hipLaunchKernelGGL((rank_count_kernel<TI, F, P>), sl.g1, dim3(256), 0, st, a.U, a.N, T, (const TI*)sl.urows,
                        (const TI*)a.cand_table, a.cand_ld, a.cand_inv_norm, a.excl_idx, a.excl_off, a.flt, tgt_idx,
-                       tgt_off, (const float*)tsel, sl.span_rows, rank);
+                       tgt_off, (const float*)tsel, sl.span_rows, rank, pri);
     NR_CHECK_LAUNCH(fn);
     return NR_OK;
   });
@@ -325,4 +343,22 @@ extern "C" int nr_rank_targets_filtered(int dtype, int64_t dim, int64_t U, const
                           {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off,
                            {news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask}, stream},
                           T, tgt_idx, tgt_off, rank, ws, ws_bytes);
+}
+
+extern "C" int64_t nr_rank_targets_prior_workspace_bytes(int dtype, int64_t U, int64_t N, int64_t T) {
+  if (!nr::tk::scan_shape_ok(dtype, U, N) || T < 0 || T >= (1ll << 31)) return -1;
+  return nr::tk::rank_layout(dtype, U, T, true).total;
+}
+
+extern "C" int nr_rank_targets_prior(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                                     const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
+                                     const int32_t* excl_idx, const int64_t* excl_off, const int32_t* news_time,
+                                     const int32_t* q_time_lo, const int32_t* q_time_hi, const uint8_t* news_cat,
+                                     const uint64_t* q_cat_mask, const float* news_prior, const float* user_gain,
+                                     int64_t T, const int32_t* tgt_idx, const int64_t* tgt_off, int32_t* rank, void* ws,
+                                     int64_t ws_bytes, void* stream) {
+  return nr::tk::rank_run("nr_rank_targets_prior",
+                          {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off,
+                           {news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask}, stream, news_prior, user_gain},
+                          T, tgt_idx, tgt_off, rank, ws, ws_bytes, true);
 }

@@ -16,6 +16,9 @@
 //                  to -inf in every score tile by the whole workgroup instead.
 //   FilterOf<FILT> the catalogue filter (include/newsrec_filter.h): Eligible in the filtered
 //                  instantiations, a predicate on the finished score tile, never on the product.
+//   PRIOR          the rank-one prior (include/newsrec_prior.h): the PRIOR instantiations of
+//                  ScoreTile add gsel[user] * prior[news] where the tile is scaled, from two
+//                  small LDS arrays, so every epilogue sees selection KEYS in the score tile.
 //   ChunkWalk      a workgroup's walk over its run of chunks with the three above: everything
 //                  around the kernel's own epilogue over a finished score tile (a heap, a count).
 //   ScanArgs       host side: what nr_topk_users* and nr_rank_targets* take alike, with its
@@ -49,6 +52,8 @@ __device__ __forceinline__ bool better(float s, int32_t r, float s2, int32_t r2)
 
 // NR_BF16: users f32 -> bf16 rows (round to nearest even), U * D / 8 groups of 8 (topk.hip)
 int bf16_users_launch(int64_t U, const float* users, __bf16* out, hipStream_t st, const char* fn);
+// the prior's scaled gains, gsel[u] = gain[u] * max(|users[u]|, 1e-8): one wave per user (topk.hip)
+int prior_gains_launch(int64_t U, const float* users, const float* gain, float* gsel, hipStream_t st, const char* fn);
 
 // How many chunks one workgroup walks in sequence: chunks only run side by side while the
 // user blocks alone do not fill the device.
@@ -62,13 +67,34 @@ static inline int64_t chunk_span(int64_t U, int64_t nchunks) {
 template <typename TI> struct Acc { typedef f32x16 type[2][2]; };  // [news 32-block][user 32-block]
 template <> struct Acc<__bf16> { typedef f32x4 type[4][4]; };      // [news 16-block][user 16-block]
 
-template <typename TI>
+// The two operations of a key (include/newsrec_prior.h), each rounded on its own: never
+// contracted into an fma, whatever the translation unit's default, so a host can recompute
+// the bits with two f32 operations.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// The prior as the kernels take it: news_prior [N] and gsel [U], the scaled gains that the
+// pre-pass left in the workspace.  The PRIOR = false instantiations never read it.
+struct PriorArgs {
+  const float* news_prior = nullptr;
+  const float* gsel = nullptr;
+};
+
+template <typename TI, bool PRIOR = false>
 struct ScoreTile {
   static constexpr int BK = 128 / (int)sizeof(TI);
   static constexpr int NKT = (int)D / BK;  // K tiles per product (even: a tile starts on ring stage 0)
 
   uint32_t* smem;  // ring [2][news | users], 4 * TILE_WORDS words, 16-byte aligned; the score tile aliases it
   float* cinv_s;   // [TS] cand_inv of the tile's news rows, 16-byte aligned (the caller fills it before scores())
+  float* prior_s;  // PRIOR: [TS] the priors of the tile's news rows, 16-byte aligned (filled where cinv_s is)
+  float* gsel_s;   // PRIOR: [TS] the scaled gains of the block's users (filled once, before the first scores())
   int tid, lane, wm, wn;  // wm: news half, wn: user half
   // global -> register staging map: 4 chunks of 16 B per operand per thread; rows past U
   // are clamped for the loads (their scores are never selected)
@@ -77,8 +103,9 @@ struct ScoreTile {
   u32x4 rn[4], ru[4];
   typename Acc<TI>::type acc;
 
-  __device__ __forceinline__ ScoreTile(uint32_t* smem_, float* cinv_s_, const TI* users, int64_t m0, int64_t U)
-      : smem(smem_), cinv_s(cinv_s_) {
+  __device__ __forceinline__ ScoreTile(uint32_t* smem_, float* cinv_s_, const TI* users, int64_t m0, int64_t U,
+                                       float* prior_s_ = nullptr, float* gsel_s_ = nullptr)
+      : smem(smem_), cinv_s(cinv_s_), prior_s(prior_s_), gsel_s(gsel_s_) {
     tid = threadIdx.x;
     lane = tid & 63;
     const int wave = tid >> 6;
@@ -159,10 +186,20 @@ struct ScoreTile {
     const float NINF = -__builtin_inff();
     const float4 ci = *reinterpret_cast<const float4*>(cinv_s + nl);
     float4 v;
-    v.x = nl + 0 < nvalid ? a0 * ci.x : NINF;
-    v.y = nl + 1 < nvalid ? a1 * ci.y : NINF;
-    v.z = nl + 2 < nvalid ? a2 * ci.z : NINF;
-    v.w = nl + 3 < nvalid ? a3 * ci.w : NINF;
+    if constexpr (PRIOR) {
+      // sel + gsel * prior; the scaled score inside it has the PRIOR = false bits
+      const float4 pr = *reinterpret_cast<const float4*>(prior_s + nl);
+      const float g = gsel_s[ul];
+      v.x = nl + 0 < nvalid ? add_rn(mul_rn(a0, ci.x), mul_rn(g, pr.x)) : NINF;
+      v.y = nl + 1 < nvalid ? add_rn(mul_rn(a1, ci.y), mul_rn(g, pr.y)) : NINF;
+      v.z = nl + 2 < nvalid ? add_rn(mul_rn(a2, ci.z), mul_rn(g, pr.z)) : NINF;
+      v.w = nl + 3 < nvalid ? add_rn(mul_rn(a3, ci.w), mul_rn(g, pr.w)) : NINF;
+    } else {
+      v.x = nl + 0 < nvalid ? a0 * ci.x : NINF;
+      v.y = nl + 1 < nvalid ? a1 * ci.y : NINF;
+      v.z = nl + 2 < nvalid ? a2 * ci.z : NINF;
+      v.w = nl + 3 < nvalid ? a3 * ci.w : NINF;
+    }
     *reinterpret_cast<float4*>(tile() + ul * TLD + nl) = v;
   }
 
@@ -410,25 +447,28 @@ template <bool FILT> using FilterOf = std::conditional_t<FILT, Eligible, NoFilte
 // [m0, m0 + TS).  The kernel declares the __shared__ arrays and hands them in; run() calls
 // epilogue(n0, T) once per finished score tile T of rows [n0, n0 + TS) and closes the tile with
 // the barrier behind which the next tile's operands overwrite T.  Threads 2 su and 2 su + 1
-// (sh = 0, 1) serve user su of the block, which exists if `live`.
-template <typename TI, bool FILT>
+// (sh = 0, 1) serve user su of the block, which exists if `live`.  PRIOR: T holds selection
+// keys; the block's scaled gains are staged once, a tile's priors where its cand_inv is.
+template <typename TI, bool FILT, bool PRIOR = false>
 struct ChunkWalk {
-  int64_t N, m0, c0, ldt;
+  int64_t U, N, m0, c0, ldt;
   int ntiles, su, sh;
   bool live;
   const TI* tab;
   const float* cinv;
-  ScoreTile<TI> st;
+  PriorArgs pri;
+  ScoreTile<TI, PRIOR> st;
   Excluded ex;
   FilterOf<FILT> el;
 
   __device__ __forceinline__ ChunkWalk(uint32_t* smem, float* cinv_s, uint16_t* ex_s, uint32_t* ov_mask, int32_t* ft_s,
-                                       uint32_t* fc_s, int64_t U, int64_t N_, const TI* users, const TI* tab_,
+                                       uint32_t* fc_s, int64_t U_, int64_t N_, const TI* users, const TI* tab_,
                                        int64_t ldt_, const float* cinv_, const int32_t* excl_idx,
-                                       const int64_t* excl_off, const FilterArgs& flt, int64_t span_rows)
-      : N(N_), m0((int64_t)blockIdx.x * TS), c0((int64_t)blockIdx.y * span_rows), ldt(ldt_),
+                                       const int64_t* excl_off, const FilterArgs& flt, int64_t span_rows,
+                                       float* prior_s = nullptr, float* gsel_s = nullptr, PriorArgs pri_ = {})
+      : U(U_), N(N_), m0((int64_t)blockIdx.x * TS), c0((int64_t)blockIdx.y * span_rows), ldt(ldt_),
         ntiles((int)((min(N_, c0 + span_rows) - c0 + TS - 1) / TS)), su(threadIdx.x >> 1), sh(threadIdx.x & 1),
-        live(m0 + su < U), tab(tab_), cinv(cinv_), st(smem, cinv_s, users, m0, U),
+        live(m0 + su < U_), tab(tab_), cinv(cinv_), pri(pri_), st(smem, cinv_s, users, m0, U_, prior_s, gsel_s),
         ex(ex_s, ov_mask, excl_idx, excl_off, m0, live, c0), el(ft_s, fc_s, flt, m0, live) {}
 
   template <typename Epilogue>
@@ -439,11 +479,17 @@ struct ChunkWalk {
       return [n0, last = N - 1](int r) __attribute__((always_inline)) { return min(n0 + r, last); };
     };
     st.gload(tab, ldt, rows_from(c0), 0);
+    if constexpr (PRIOR) {  // (read behind the first tile's barriers)
+      if (tid < TS) st.gsel_s[tid] = m0 + tid < U ? pri.gsel[m0 + tid] : 0.f;
+    }
     for (int tile = 0; tile < ntiles; ++tile) {
       const int64_t n0 = c0 + (int64_t)tile * TS;
       if (tile == 0 || n0 == ex.cb + kChunk) ex.chunk_start(n0);
       const int nvalid = (int)min((int64_t)TS, N - n0);
       if (tid < TS) st.cinv_s[tid] = tid < nvalid ? cinv[n0 + tid] : 0.f;
+      if constexpr (PRIOR) {
+        if (tid < TS) st.prior_s[tid] = tid < nvalid ? pri.news_prior[n0 + tid] : 0.f;
+      }
       if constexpr (FILT) el.stage(n0, N);
       st.scores(tab, ldt, rows_from(n0), tile + 1 < ntiles, rows_from(n0 + TS), nvalid);
       ex.knock_out_overflow(st.tile(), m0, n0);
@@ -466,6 +512,9 @@ struct ScanArgs {
   const int64_t* excl_off;
   FilterArgs flt;
   void* stream;
+  const float* news_prior = nullptr;  // the rank-one prior (include/newsrec_prior.h): [N] and
+  const float* user_gain = nullptr;   //   [U], both or neither
+  bool prior() const { return news_prior != nullptr; }
 };
 
 static inline int64_t chunks_of(int64_t N) { return (N + kChunk - 1) / kChunk; }
@@ -501,19 +550,23 @@ static int check_scan(const char* fn, const ScanArgs& a, AfterDtype after_dtype,
   NR_CHECK_ARG((f.news_time == nullptr) == (f.q_lo == nullptr) && (f.news_time == nullptr) == (f.q_hi == nullptr),
                "%s: news_time, q_time_lo and q_time_hi go together", fn);
   NR_CHECK_ARG((f.news_cat == nullptr) == (f.q_mask == nullptr), "%s: news_cat and q_cat_mask go together", fn);
+  NR_CHECK_ARG((a.news_prior == nullptr) == (a.user_gain == nullptr), "%s: news_prior and user_gain go together", fn);
   NR_CHECK_ARG(a.users && a.cand_table && a.cand_inv_norm, "%s: null pointer", fn);
   return NR_OK;
 }
 
-// NR_CHECK_DEVICE over a scan's pointers, the feature's own (`outs`) between the scan's and the filter's
+// NR_CHECK_DEVICE over a scan's pointers, the feature's own (`outs`) between the scan's and the
+// filter's; the prior's come last
 static inline int check_scan_device(const char* fn, const ScanArgs& a, const char* out_names,
                                     std::initializer_list<const void*> outs) {
   if (const int rc = nr::check_device_ptrs(fn, "users, cand_table, cand_inv_norm, excl_idx, excl_off",
                                            {a.users, a.cand_table, a.cand_inv_norm, a.excl_idx, a.excl_off}))
     return rc;
   if (const int rc = nr::check_device_ptrs(fn, out_names, outs)) return rc;
-  return nr::check_device_ptrs(fn, "news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask",
-                               {a.flt.news_time, a.flt.q_lo, a.flt.q_hi, a.flt.news_cat, a.flt.q_mask});
+  if (const int rc = nr::check_device_ptrs(fn, "news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask",
+                                           {a.flt.news_time, a.flt.q_lo, a.flt.q_hi, a.flt.news_cat, a.flt.q_mask}))
+    return rc;
+  return nr::check_device_ptrs(fn, "news_prior, user_gain", {a.news_prior, a.user_gain});
 }
 
 // What a scan launches with: the users operand (NR_BF16: converted into `ub`, U * D * 2 bytes of
@@ -525,7 +578,10 @@ struct ScanLaunch {
   dim3 g0, g1;
   int64_t span_rows;  // news rows per workgroup of g1
 };
-static inline int scan_prepare(const char* fn, const ScanArgs& a, void* ub, ScanLaunch& L) {
+static inline int scan_prepare(const char* fn, const ScanArgs& a, void* ub, ScanLaunch& L, float* gsel = nullptr) {
+  // the prior's pre-pass: gsel [a.U] of the workspace
+  if (a.prior())
+    if (const int rc = prior_gains_launch(a.U, a.users, a.user_gain, gsel, (hipStream_t)a.stream, fn)) return rc;
   const int64_t nchunks = chunks_of(a.N), span = chunk_span(a.U, nchunks);
   L.g0 = dim3((unsigned)((a.U + TS - 1) / TS));
   L.g1 = dim3(L.g0.x, (unsigned)((nchunks + span - 1) / span));
@@ -538,11 +594,14 @@ static inline int scan_prepare(const char* fn, const ScanArgs& a, void* ub, Scan
   return NR_OK;
 }
 
-// f(TypeTag<TI>, std::bool_constant<FILT>) for the scan's dtype and whether it carries a filter
+// f(TypeTag<TI>, std::bool_constant<FILT>, std::bool_constant<PRIOR>) for the scan's dtype and
+// whether it carries a filter and a prior
 template <typename F>
 static int with_scan_types(const ScanArgs& a, F&& f) {
-  return nr::with_dtype(
-      a.dtype, [&](auto ti) { return a.flt.any() ? f(ti, std::true_type{}) : f(ti, std::false_type{}); });
+  return nr::with_dtype(a.dtype, [&](auto ti) {
+    auto with_prior = [&](auto filt) { return a.prior() ? f(ti, filt, std::true_type{}) : f(ti, filt, std::false_type{}); };
+    return a.flt.any() ? with_prior(std::true_type{}) : with_prior(std::false_type{});
+  });
 }
 
 // ---- what the top-K entries (topk.hip, sections.hip) share behind their stage 1
@@ -551,11 +610,12 @@ struct alignas(8) Pair {
   int32_t r;
 };
 
-// The workspace of a top-K that keeps K (score, row) pairs per user and chunk.
+// The workspace of a top-K that keeps K (score, row) pairs per user and chunk; with a prior,
+// the U scaled gains behind the base layout.
 struct TopkLayout {
-  int64_t nchunks, ub, cnt, uidx, coff, part, total;
+  int64_t nchunks, ub, cnt, uidx, coff, part, gsel, total;
 };
-static inline TopkLayout topk_layout(int dtype, int64_t U, int64_t N, int64_t K) {
+static inline TopkLayout topk_layout(int dtype, int64_t U, int64_t N, int64_t K, bool prior = false) {
   TopkLayout L{};
   L.nchunks = chunks_of(N);
   int64_t o = 0;
@@ -569,6 +629,7 @@ static inline TopkLayout topk_layout(int dtype, int64_t U, int64_t N, int64_t K)
   L.uidx = take(U * 4);
   L.coff = take((U + 1) * 8);
   L.part = take(U * L.nchunks * K * (int64_t)sizeof(Pair));
+  L.gsel = take(prior ? U * 4 : 0);
   L.total = o;
   return L;
 }
@@ -578,8 +639,11 @@ static inline TopkLayout topk_layout(int dtype, int64_t U, int64_t N, int64_t K)
 // scores of a user's S k survivors, a rank sort per list: top_idx / top_scores [U][S][k].
 // cnt ([U] int32) is used when S == 1; with more lists per user a list's length is counted
 // from its runs again, so the workspace is topk_layout(dtype, U, N, S k) for every S.
+// top_keys (null: none wanted) [U][S][k]: with a prior in `a` the rank sort orders by
+// fl(score + fl(gain * prior)) and writes these keys; without one they are the scores.
 int topk_stage2_launch(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,
-                       int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores);
+                       int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores,
+                       float* top_keys = nullptr);
 
 }  // namespace tk
 }  // namespace nr

@@ -17,6 +17,7 @@
 // keeps with K = k and the mask sec_mask[s]: the contract is an equality of bits.
 #include "nr_score_tile.h"
 
+#include "../../include/newsrec_prior.h"
 #include "../../include/newsrec_sections.h"
 
 namespace nr {
@@ -71,15 +72,17 @@ __device__ __forceinline__ void heap_keep(float* hs, int32_t* hr, int& n, int ca
 }
 
 // flt carries the time window only (its category pair is null: Eligible then stages category
-// 0 against the full mask); the categories act through the section bytes.
-template <typename TI>
+// 0 against the full mask); the categories act through the section bytes.  PRIOR: the rank-one
+// prior of include/newsrec_prior.h; the score tile, heaps and thresholds then hold selection keys.
+template <typename TI, bool PRIOR>
 __global__ __launch_bounds__(256) void sections_stage1_kernel(int64_t U, int64_t N, const TI* __restrict__ users,
                                                               const TI* __restrict__ tab, int64_t ldt,
                                                               const float* __restrict__ cinv,
                                                               const int32_t* __restrict__ excl_idx,
                                                               const int64_t* __restrict__ excl_off, FilterArgs flt,
                                                               const uint8_t* __restrict__ news_cat, SecMap map, int S,
-                                                              int k, int64_t span_rows, Pair* __restrict__ part) {
+                                                              int k, int64_t span_rows, Pair* __restrict__ part,
+                                                              PriorArgs pri) {
   __shared__ __attribute__((aligned(16))) uint32_t smem[4 * TILE_WORDS];  // ring [2][news | users]; score tile
   __shared__ float ls[SLOTS * TS];  // the users' heaps, [slot][user]
   __shared__ int32_t li[SLOTS * TS];
@@ -92,6 +95,8 @@ __global__ __launch_bounds__(256) void sections_stage1_kernel(int64_t U, int64_t
   __shared__ uint32_t fc_s[ATTR_CAT_WORDS];                               //   (Eligible's category bytes: zeros here)
   __shared__ uint32_t sec_s[TS / 4];  // the tile's section bytes, one per column
   __shared__ uint32_t map_s[16];
+  __shared__ __attribute__((aligned(16))) float prior_s[PRIOR ? TS : 4];  // the tile's priors
+  __shared__ float gsel_s[PRIOR ? TS : 1];                                //   and the block's scaled gains
 
   const int tid = threadIdx.x;
   const float NINF = -__builtin_inff();
@@ -100,8 +105,8 @@ __global__ __launch_bounds__(256) void sections_stage1_kernel(int64_t U, int64_t
     cnt_s[i] = 0;
   }
   if (tid < 16) map_s[tid] = map.w[tid];
-  ChunkWalk<TI, true> w(smem, cinv_s, ex_s, ov_mask, ft_s, fc_s, U, N, users, tab, ldt, cinv, excl_idx, excl_off, flt,
-                        span_rows);
+  ChunkWalk<TI, true, PRIOR> w(smem, cinv_s, ex_s, ov_mask, ft_s, fc_s, U, N, users, tab, ldt, cinv, excl_idx,
+                               excl_off, flt, span_rows, prior_s, gsel_s, pri);
   const int su = w.su, sh = w.sh;
   const int64_t m0 = w.m0;
   const bool windowed = flt.news_time != nullptr;
@@ -195,17 +200,21 @@ extern "C" int64_t nr_topk_sections_workspace_bytes(int dtype, int64_t U, int64_
   return nr::tk::topk_layout(dtype, U, N, S * k).total;
 }
 
-extern "C" int nr_topk_sections(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
-                                const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
-                                const int32_t* excl_idx, const int64_t* excl_off, const int32_t* news_time,
-                                const int32_t* q_time_lo, const int32_t* q_time_hi, const uint8_t* news_cat,
-                                const uint64_t* sec_mask, int64_t S, int64_t k, int32_t* top_idx, float* top_scores,
-                                void* ws, int64_t ws_bytes, void* stream) {
-  using namespace nr::tk;
-  const char* fn = "nr_topk_sections";
+namespace nr {
+namespace tk {
+
+// nr_topk_sections and nr_topk_sections_prior: one validation, one launch sequence.  A null
+// prior runs the stage 1 without one.  keyed: the prior entry, whose top_keys is required.
+static int sections_run(const char* fn, int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                        const void* cand_table, int64_t cand_ld, const float* cand_inv_norm, const int32_t* excl_idx,
+                        const int64_t* excl_off, const int32_t* news_time, const int32_t* q_time_lo,
+                        const int32_t* q_time_hi, const uint8_t* news_cat, const uint64_t* sec_mask,
+                        const float* news_prior, const float* user_gain, int64_t S, int64_t k, int32_t* top_idx,
+                        float* top_scores, float* top_keys, bool keyed, void* ws, int64_t ws_bytes, void* stream) {
   // the time window travels as the scan's filter; the categories act through the section map
-  const ScanArgs a{dtype, dim,      U,        users, N, cand_table, cand_ld, cand_inv_norm,
-                   excl_idx, excl_off, {news_time, q_time_lo, q_time_hi, nullptr, nullptr}, stream};
+  const ScanArgs a{dtype,    dim,      U, users, N, cand_table, cand_ld, cand_inv_norm,
+                   excl_idx, excl_off, {news_time, q_time_lo, q_time_hi, nullptr, nullptr}, stream, news_prior,
+                   user_gain};
   auto sk_ok = [&] {
     NR_CHECK_ARG(S >= 1 && S <= SMAX, "%s: S = %lld outside [1, %d]", fn, (long long)S, SMAX);
     NR_CHECK_ARG(k >= 1, "%s: k = %lld < 1", fn, (long long)k);
@@ -228,28 +237,66 @@ extern "C" int nr_topk_sections(int dtype, int64_t dim, int64_t U, const float* 
                    (long long)s, c);
       map.w[c >> 2] = (map.w[c >> 2] & ~(255u << (8 * (c & 3)))) | ((uint32_t)s << (8 * (c & 3)));
     }
-  NR_CHECK_ARG(top_idx && top_scores && ws, "%s: null pointer", fn);
-  const TopkLayout L = topk_layout(dtype, U, N, S * k);
+  NR_CHECK_ARG(top_idx && top_scores && ws && (top_keys || !keyed), "%s: null pointer", fn);
+  const TopkLayout L = topk_layout(dtype, U, N, S * k, keyed);
   NR_CHECK_ARG(ws_bytes >= L.total, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes,
                (long long)L.total);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
-  if (const int rc = check_scan_device(fn, a, "news_cat, top_idx, top_scores, ws", {news_cat, top_idx, top_scores, ws}))
+  if (const int rc = keyed ? check_scan_device(fn, a, "news_cat, top_idx, top_scores, top_keys, ws",
+                                               {news_cat, top_idx, top_scores, top_keys, ws})
+                           : check_scan_device(fn, a, "news_cat, top_idx, top_scores, ws",
+                                               {news_cat, top_idx, top_scores, ws}))
     return rc;
 
   hipStream_t st = (hipStream_t)stream;
   char* w = (char*)ws;
   Pair* part = (Pair*)(w + L.part);
+  float* gsel = (float*)(w + L.gsel);
   ScanLaunch sl;
-  if (const int rc = scan_prepare(fn, a, w + L.ub, sl)) return rc;
+  if (const int rc = scan_prepare(fn, a, w + L.ub, sl, gsel)) return rc;
   const int rc1 = nr::with_dtype(dtype, [&](auto ti) {
     using TI = typename decltype(ti)::type;
-    hipLaunchKernelGGL((sections_stage1_kernel<TI>), sl.g1, dim3(256), 0, st, U, N, (const TI*)sl.urows,
-                       (const TI*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, a.flt, news_cat, map, (int)S,
-                       (int)k, sl.span_rows, part);
-    return NR_OK;
+    auto launch = [&](auto prior) {
+      hipLaunchKernelGGL((sections_stage1_kernel<TI, decltype(prior)::value>), sl.g1, dim3(256), 0, st, U, N,
+                         (const TI*)sl.urows, (const TI*)cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off, a.flt,
+                         news_cat, map, (int)S, (int)k, sl.span_rows, part, PriorArgs{news_prior, gsel});
+      return NR_OK;
+    };
+    return a.prior() ? launch(std::true_type{}) : launch(std::false_type{});
   });
   if (rc1) return rc1;
   NR_CHECK_LAUNCH(fn);
   return topk_stage2_launch(fn, a, S, k, (int)sl.g1.y, part, (int32_t*)(w + L.cnt), (int32_t*)(w + L.uidx),
-                            (int64_t*)(w + L.coff), top_idx, top_scores);
+                            (int64_t*)(w + L.coff), top_idx, top_scores, top_keys);
+}
+
+}  // namespace tk
+}  // namespace nr
+
+extern "C" int nr_topk_sections(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                                const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
+                                const int32_t* excl_idx, const int64_t* excl_off, const int32_t* news_time,
+                                const int32_t* q_time_lo, const int32_t* q_time_hi, const uint8_t* news_cat,
+                                const uint64_t* sec_mask, int64_t S, int64_t k, int32_t* top_idx, float* top_scores,
+                                void* ws, int64_t ws_bytes, void* stream) {
+  return nr::tk::sections_run("nr_topk_sections", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx,
+                              excl_off, news_time, q_time_lo, q_time_hi, news_cat, sec_mask, nullptr, nullptr, S, k,
+                              top_idx, top_scores, nullptr, false, ws, ws_bytes, stream);
+}
+
+extern "C" int64_t nr_topk_sections_prior_workspace_bytes(int dtype, int64_t U, int64_t N, int64_t S, int64_t k) {
+  if (!nr::tk::scan_shape_ok(dtype, U, N) || !nr::tk::sections_shape_ok(U, S, k)) return -1;
+  return nr::tk::topk_layout(dtype, U, N, S * k, true).total;
+}
+
+extern "C" int nr_topk_sections_prior(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                                      const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
+                                      const int32_t* excl_idx, const int64_t* excl_off, const int32_t* news_time,
+                                      const int32_t* q_time_lo, const int32_t* q_time_hi, const uint8_t* news_cat,
+                                      const uint64_t* sec_mask, const float* news_prior, const float* user_gain,
+                                      int64_t S, int64_t k, int32_t* top_idx, float* top_scores, float* top_keys,
+                                      void* ws, int64_t ws_bytes, void* stream) {
+  return nr::tk::sections_run("nr_topk_sections_prior", dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm,
+                              excl_idx, excl_off, news_time, q_time_lo, q_time_hi, news_cat, sec_mask, news_prior,
+                              user_gain, S, k, top_idx, top_scores, top_keys, true, ws, ws_bytes, stream);
 }

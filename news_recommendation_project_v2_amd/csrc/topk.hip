@@ -24,6 +24,7 @@
 #include "nr_score_tile.h"
 
 #include "../../include/newsrec_filter.h"
+#include "../../include/newsrec_prior.h"
 #include "../../include/newsrec_topk.h"
 
 namespace nr {
@@ -49,17 +50,49 @@ int bf16_users_launch(int64_t U, const float* users, __bf16* out, hipStream_t st
   return NR_OK;
 }
 
+// gsel[u] = gain[u] * max(|users[u]|, 1e-8) (include/newsrec_prior.h): one wave per user.  Lane l
+// adds the squares of elements 4 l + 256 i + (0 .. 3) in that order, the lanes' sums meet in a
+// butterfly: a fixed order, so the bits depend on the user row and its gain alone.
+__global__ __launch_bounds__(256) void prior_gains_kernel(int64_t U, const float* __restrict__ users,
+                                                          const float* __restrict__ gain, float* __restrict__ gsel) {
+  const int lane = threadIdx.x & 63;
+  const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= U) return;  // wave-uniform
+  const float4* row = reinterpret_cast<const float4*>(users + u * D) + lane;
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < (int)D / 256; ++i) {
+    const float4 v = row[64 * i];
+    ss += v.x * v.x;
+    ss += v.y * v.y;
+    ss += v.z * v.z;
+    ss += v.w * v.w;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+  if (lane == 0) gsel[u] = mul_rn(gain[u], fmaxf(sqrtf(ss), 1e-8f));
+}
+
+int prior_gains_launch(int64_t U, const float* users, const float* gain, float* gsel, hipStream_t st, const char* fn) {
+  hipLaunchKernelGGL(prior_gains_kernel, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, st, U, users, gain, gsel);
+  NR_CHECK_LAUNCH(fn);
+  return NR_OK;
+}
+
 // FILT: the catalogue filter (include/newsrec_filter.h).  The predicate is ANDed into the scan's
 // masks, so an ineligible row never reaches the serial drain: while fewer than K rows are kept
 // every finite score passes the scan, and a selective filter would otherwise feed the heap loop
 // all of them.  The unfiltered instantiation holds none of it.
-template <typename TI, bool FILT>
+// PRIOR: the rank-one prior (include/newsrec_prior.h).  The score tile then holds selection
+// keys, and the scan, the heap and the partials below keep keys where they say scores.
+template <typename TI, bool FILT, bool PRIOR>
 __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, const TI* __restrict__ users,
                                                           const TI* __restrict__ tab, int64_t ldt,
                                                           const float* __restrict__ cinv,
                                                           const int32_t* __restrict__ excl_idx,
                                                           const int64_t* __restrict__ excl_off, FilterArgs flt,
-                                                          int K, int64_t span_rows, Pair* __restrict__ part) {
+                                                          int K, int64_t span_rows, Pair* __restrict__ part,
+                                                          PriorArgs pri) {
   __shared__ __attribute__((aligned(16))) uint32_t smem[4 * TILE_WORDS];  // ring [2][news | users]; score tile
   __shared__ float ls[KMAX * TS];  // the users' sorted lists, [rank][user]
   __shared__ int32_t li[KMAX * TS];
@@ -69,12 +102,14 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
   __shared__ uint32_t ov_mask[TS / 32];
   __shared__ __attribute__((aligned(16))) int32_t ft_s[FILT ? ATTR_TIME_WORDS : 4];  // the tile's news times
   __shared__ uint32_t fc_s[FILT ? ATTR_CAT_WORDS : 1];                                //   and categories
+  __shared__ __attribute__((aligned(16))) float prior_s[PRIOR ? TS : 4];  // the tile's priors
+  __shared__ float gsel_s[PRIOR ? TS : 1];                                //   and the block's scaled gains
 
   const int tid = threadIdx.x, lane = tid & 63;
   const float NINF = -__builtin_inff();
   // this workgroup's news rows: span_rows = a whole number of chunks, one running list over them
-  ChunkWalk<TI, FILT> w(smem, cinv_s, ex_s, ov_mask, ft_s, fc_s, U, N, users, tab, ldt, cinv, excl_idx, excl_off, flt,
-                        span_rows);
+  ChunkWalk<TI, FILT, PRIOR> w(smem, cinv_s, ex_s, ov_mask, ft_s, fc_s, U, N, users, tab, ldt, cinv, excl_idx,
+                               excl_off, flt, span_rows, prior_s, gsel_s, pri);
   // selection state: threads 2u and 2u + 1 serve user u of the block; 2u owns its list
   const int su = w.su, sh = w.sh;
   const int64_t m0 = w.m0;
@@ -252,10 +287,19 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int S, int K
 // again: the rows of its runs, at most K.  L >= K: the lanes compared against -- lanes K and up
 // hold (-inf, INT32_MAX) pads, which beat nothing and are never written (a pad in lane
 // j < K still ranks j), so a short list does not pay for 64 rounds.
-template <int L>
+// PRIOR (include/newsrec_prior.h): the order is by the key fl(score + fl(gain[user] * prior[row])),
+// list u belonging to user u / S, and the keys go to top_keys beside the untouched scores.
+struct SortPrior {
+  const float* news_prior;
+  const float* user_gain;
+  float* top_keys;
+  int S;
+};
+template <int L, bool PRIOR>
 __global__ __launch_bounds__(256) void topk_sort_kernel(int64_t R, int K, const int32_t* __restrict__ cnt_in,
                                                         int nchunks, const Pair* __restrict__ part,
-                                                        int32_t* __restrict__ top_idx, float* __restrict__ top_scores) {
+                                                        int32_t* __restrict__ top_idx, float* __restrict__ top_scores,
+                                                        SortPrior sp) {
   const int lane = threadIdx.x & 63;
   const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (u >= R) return;
@@ -273,16 +317,21 @@ __global__ __launch_bounds__(256) void topk_sort_kernel(int64_t R, int K, const 
   const bool valid = lane < n;
   const float s = valid ? top_scores[u * K + lane] : -__builtin_inff();
   const int32_t r = valid ? top_idx[u * K + lane] : INT32_MAX;
+  float key = s;  // what the list is ordered by
+  if constexpr (PRIOR) {
+    if (valid) key = add_rn(s, mul_rn(sp.user_gain[u / sp.S], sp.news_prior[r]));
+  }
   int rank = 0;
   for (int l = 0; l < L; ++l) {
-    const float os = __shfl(s, l, 64);
+    const float os = __shfl(key, l, 64);
     const int32_t orow = __shfl(r, l, 64);
-    rank += (better(os, orow, s, r) || (os == s && orow == r && l < lane)) ? 1 : 0;
+    rank += (better(os, orow, key, r) || (os == key && orow == r && l < lane)) ? 1 : 0;
   }
   // (the shuffles above consumed every lane's loads: the row is rewritten in place)
   if (rank < K) {
     top_idx[u * K + rank] = valid ? r : -1;
     top_scores[u * K + rank] = s;
+    if constexpr (PRIOR) sp.top_keys[u * K + rank] = key;
   }
 }
 
@@ -300,7 +349,8 @@ namespace nr {
 namespace tk {
 
 int topk_stage2_launch(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,
-                       int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores) {
+                       int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores,
+                       float* top_keys) {
   hipStream_t st = (hipStream_t)a.stream;
   const int64_t R = a.U * S;
   const dim3 gw((unsigned)((R + 3) / 4));
@@ -314,30 +364,46 @@ int topk_stage2_launch(const char* fn, const ScanArgs& a, int64_t S, int64_t k, 
   const int rc2 = nr::with_int<8, 16, 32, 64>(
       k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64, [&] { return nr::unvalidated_code("top-K list length", (int)k); },
       [&](auto lanes) {
-        hipLaunchKernelGGL(topk_sort_kernel<decltype(lanes)::value>, gw, dim3(256), 0, st, R, (int)k,
-                           (const int32_t*)cnt, nruns, part, top_idx, top_scores);
+        constexpr int L = decltype(lanes)::value;
+        const SortPrior sp{a.news_prior, a.user_gain, top_keys, (int)S};
+        if (a.prior())
+          hipLaunchKernelGGL((topk_sort_kernel<L, true>), gw, dim3(256), 0, st, R, (int)k, (const int32_t*)cnt, nruns,
+                             part, top_idx, top_scores, sp);
+        else
+          hipLaunchKernelGGL((topk_sort_kernel<L, false>), gw, dim3(256), 0, st, R, (int)k, (const int32_t*)cnt, nruns,
+                             part, top_idx, top_scores, sp);
         return NR_OK;
       });
   if (rc2) return rc2;
   NR_CHECK_LAUNCH(fn);
+  // without a prior the keys are the scores
+  if (top_keys && !a.prior() &&
+      hipMemcpyAsync(top_keys, top_scores, (size_t)(R * k) * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    nr::set_error("%s: hipMemcpyAsync failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    return NR_ERR_HIP;
+  }
   return NR_OK;
 }
 
-// nr_topk_users and nr_topk_users_filtered: one validation, one launch sequence.  A filter with
-// both pairs null runs the unfiltered stage 1.
+// nr_topk_users, nr_topk_users_filtered and nr_topk_users_prior: one validation, one launch
+// sequence.  A filter with both pairs null runs the unfiltered stage 1, a null prior the
+// stage 1 without one.  keyed: the prior entry, whose top_keys is required.
 static int topk_run(const char* fn, const ScanArgs& a, int64_t K, int32_t* top_idx, float* top_scores, void* ws,
-                    int64_t ws_bytes) {
+                    int64_t ws_bytes, bool keyed = false, float* top_keys = nullptr) {
   auto k_ok = [&] {
     NR_CHECK_ARG(K >= 1 && K <= KMAX, "%s: K = %lld outside [1, %d]", fn, (long long)K, KMAX);
     return NR_OK;
   };
   if (const int rc = check_scan(fn, a, k_ok, no_check)) return rc;
-  NR_CHECK_ARG(top_idx && top_scores && ws, "%s: null pointer", fn);
-  const TopkLayout L = topk_layout(a.dtype, a.U, a.N, K);
+  NR_CHECK_ARG(top_idx && top_scores && ws && (top_keys || !keyed), "%s: null pointer", fn);
+  const TopkLayout L = topk_layout(a.dtype, a.U, a.N, K, keyed);
   NR_CHECK_ARG(ws_bytes >= L.total, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes,
                (long long)L.total);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
-  if (const int rc = check_scan_device(fn, a, "top_idx, top_scores, ws", {top_idx, top_scores, ws})) return rc;
+  if (const int rc = keyed ? check_scan_device(fn, a, "top_idx, top_scores, top_keys, ws",
+                                               {top_idx, top_scores, top_keys, ws})
+                           : check_scan_device(fn, a, "top_idx, top_scores, ws", {top_idx, top_scores, ws}))
+    return rc;
 
   hipStream_t st = (hipStream_t)a.stream;
   const int64_t U = a.U;
@@ -347,17 +413,18 @@ static int topk_run(const char* fn, const ScanArgs& a, int64_t K, int32_t* top_i
   int64_t* coff = (int64_t*)(w + L.coff);
   Pair* part = (Pair*)(w + L.part);
   ScanLaunch sl;
-  if (const int rc = scan_prepare(fn, a, w + L.ub, sl)) return rc;
-  const int rc1 = with_scan_types(a, [&](auto ti, auto filt) {
+  float* gsel = (float*)(w + L.gsel);
+  if (const int rc = scan_prepare(fn, a, w + L.ub, sl, gsel)) return rc;
+  const int rc1 = with_scan_types(a, [&](auto ti, auto filt, auto prior) {
     using TI = typename decltype(ti)::type;
-    hipLaunchKernelGGL((topk_stage1_kernel<TI, decltype(filt)::value>), sl.g1, dim3(256), 0, st, U, a.N,
-                       (const TI*)sl.urows, (const TI*)a.cand_table, a.cand_ld, a.cand_inv_norm, a.excl_idx, a.excl_off,
-                       a.flt, (int)K, sl.span_rows, part);
+    hipLaunchKernelGGL((topk_stage1_kernel<TI, decltype(filt)::value, decltype(prior)::value>), sl.g1, dim3(256), 0, st,
+                       U, a.N, (const TI*)sl.urows, (const TI*)a.cand_table, a.cand_ld, a.cand_inv_norm, a.excl_idx,
+                       a.excl_off, a.flt, (int)K, sl.span_rows, part, PriorArgs{a.news_prior, gsel});
     return NR_OK;
   });
   if (rc1) return rc1;
   NR_CHECK_LAUNCH(fn);
-  return topk_stage2_launch(fn, a, 1, K, (int)sl.g1.y, part, cnt, uidx, coff, top_idx, top_scores);
+  return topk_stage2_launch(fn, a, 1, K, (int)sl.g1.y, part, cnt, uidx, coff, top_idx, top_scores, top_keys);
 }
 
 }  // namespace tk
@@ -382,4 +449,22 @@ extern "C" int nr_topk_users_filtered(int dtype, int64_t dim, int64_t U, const f
                           {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off,
                            {news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask}, stream},
                           K, top_idx, top_scores, ws, ws_bytes);
+}
+
+extern "C" int64_t nr_topk_users_prior_workspace_bytes(int dtype, int64_t U, int64_t N, int64_t K) {
+  if (!nr::tk::scan_shape_ok(dtype, U, N) || K < 1 || K > nr::tk::KMAX) return -1;
+  return nr::tk::topk_layout(dtype, U, N, K, true).total;
+}
+
+extern "C" int nr_topk_users_prior(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                                   const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
+                                   const int32_t* excl_idx, const int64_t* excl_off, const int32_t* news_time,
+                                   const int32_t* q_time_lo, const int32_t* q_time_hi, const uint8_t* news_cat,
+                                   const uint64_t* q_cat_mask, const float* news_prior, const float* user_gain,
+                                   int64_t K, int32_t* top_idx, float* top_scores, float* top_keys, void* ws,
+                                   int64_t ws_bytes, void* stream) {
+  return nr::tk::topk_run("nr_topk_users_prior",
+                          {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off,
+                           {news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask}, stream, news_prior, user_gain},
+                          K, top_idx, top_scores, ws, ws_bytes, true, top_keys);
 }

@@ -138,12 +138,26 @@ def get_final_second_attention_score(history_rev_index: np.ndarray, history_len_
     return {"scores": scores, "grouped_scores": grouped}
 
 
+def _check_prior_args(what: str, prior, prior_gain, n_news: int, n_imp: int, reranked: bool) -> None:
+    """The prior arguments of the retrieval helpers, refused before any device work."""
+    from .engine import check_gain, check_prior
+    if prior is not None:
+        check_prior(prior, n_news)
+    if prior_gain is None:
+        return
+    if prior is None:
+        raise ValueError(f"{what}: prior_gain needs prior")
+    check_gain(prior_gain, n_imp)
+    if reranked:
+        raise ValueError(f"{what}: prior_gain cannot be combined with diversify or explain")
+
+
 def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: np.ndarray,
                               news_embeddings: torch.Tensor, attention_model: torch.nn.Module, k: int,
                               exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
                               dtype=None, diversify: Optional[float] = None, pool: Optional[int] = None,
                               news_time=None, news_category=None, time_window=None, categories=None,
-                              sections=None, explain: Optional[int] = None) -> dict:
+                              sections=None, prior=None, prior_gain=None, explain: Optional[int] = None) -> dict:
     """The k news of the WHOLE table that the model recommends per impression:
     ``{"news_index": int32 [I, k], "scores": float32 [I, k]}`` on the host, score
     descending, ties by ascending news row, ``(-1, -inf)`` where fewer than k news are
@@ -184,7 +198,17 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     include/newsrec_sections.h): ``news_index`` and ``scores`` are then [I, S, k], the k best
     eligible news of each section from one walk over the table, and ``k`` means per section
     (S <= 16, S * k <= 64).  It needs ``news_category`` and composes with ``time_window``;
-    with ``categories``, ``diversify`` or ``explain`` it is refused."""
+    with ``categories``, ``diversify`` or ``explain`` it is refused.
+
+    ``prior`` f32 [N] (finite; e.g. data_utils.history_popularity) with ``prior_gain`` = g, a
+    finite scalar or one value per impression, selects and orders the news by ``score + g *
+    prior`` (PoolScoreEngine.recommend's ``prior_gain``, include/newsrec_prior.h): g = 0 changes
+    nothing, an impression with an empty history gets the news with the largest prior.  The
+    ``scores`` stay the cosines and the result gains ``"keys"`` float32, shaped like them: what
+    the lists are ordered by.  It composes with the catalogue filters and ``sections``; with
+    ``diversify`` or ``explain`` it is refused."""
+    _check_prior_args("get_top_k_recommendations", prior, prior_gain, news_embeddings.shape[0],
+                      len(history_len_list), diversify is not None or explain is not None or pool is not None)
     if sections is not None:
         if categories is not None or diversify is not None or explain is not None or pool is not None:
             raise ValueError("get_top_k_recommendations: sections cannot be combined with categories, diversify or "
@@ -205,13 +229,21 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     n = len(history_len_list)
     eng.load_impressions(history_rev_index, history_len_list, np.zeros(0, np.int32), np.zeros(n, np.int32))
     if sections is not None:
-        eng.set_catalogue(news_time=news_time, news_cat=news_category)
+        eng.set_catalogue(news_time=news_time, news_cat=news_category, news_prior=prior)
+        if prior_gain is not None:
+            idx, scores, keys = eng.recommend_sections(k, sections, exclude_history=exclude_history,
+                                                       time_window=time_window, prior_gain=prior_gain, want_keys=True)
+            return {"news_index": _host(idx), "scores": _host(scores), "keys": _host(keys)}
         idx, scores = eng.recommend_sections(k, sections, exclude_history=exclude_history, time_window=time_window)
         return {"news_index": _host(idx), "scores": _host(scores)}
     flt = {}
-    if time_window is not None or categories is not None:
-        eng.set_catalogue(news_time=news_time, news_cat=news_category)
+    if time_window is not None or categories is not None or prior_gain is not None:
+        eng.set_catalogue(news_time=news_time, news_cat=news_category, news_prior=prior)
         flt = {"time_window": time_window, "categories": categories}
+    if prior_gain is not None:
+        idx, scores, keys = eng.recommend(k, exclude_history=exclude_history, prior_gain=prior_gain, want_keys=True,
+                                          **flt)
+        return {"news_index": _host(idx), "scores": _host(scores), "keys": _host(keys)}
     why = {}
     if explain is not None:
         explained = eng.recommend_explained_filtered if flt else eng.recommend_explained
@@ -235,7 +267,7 @@ def get_full_table_ranks(history_rev_index: np.ndarray, history_len_list: np.nda
                          target_len_list: np.ndarray, news_embeddings: torch.Tensor, attention_model: torch.nn.Module,
                          exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
                          dtype=None, news_time=None, news_category=None, time_window=None,
-                         categories=None) -> dict:
+                         categories=None, prior=None, prior_gain=None) -> dict:
     """Where the given news stand among ALL news of the table for each impression's
     user: ``{"ranks": int32 [T]}`` on the host, in the order of ``target_index``
     (``target_len_list[i]`` rows of ``news_embeddings`` for impression i, e.g. its
@@ -252,16 +284,20 @@ def get_full_table_ranks(history_rev_index: np.ndarray, history_len_list: np.nda
     users x table MFMA product of the top-K path with a counting epilogue,
     include/newsrec_fullrank.h).  ``news_time`` / ``news_category`` / ``time_window`` /
     ``categories`` are get_top_k_recommendations' catalogue filters: only the eligible news
-    are counted, and a target its impression's filter leaves out gets -1."""
+    are counted, and a target its impression's filter leaves out gets -1.  ``prior`` /
+    ``prior_gain`` are get_top_k_recommendations' too: the ranks are then taken on ``score + g *
+    prior``, and the targets with rank < k are the rows it returns under the same arguments."""
+    _check_prior_args("get_full_table_ranks", prior, prior_gain, news_embeddings.shape[0], len(history_len_list),
+                      False)
     eng = _engine(attention_model, news_embeddings, query_news_embeddings if isinstance(query_news_embeddings,
                                                                                         torch.Tensor) else None,
                   dtype=dtype)
     n = len(history_len_list)
     eng.load_impressions(history_rev_index, history_len_list, np.zeros(0, np.int32), np.zeros(n, np.int32))
     flt = {}
-    if time_window is not None or categories is not None:
-        eng.set_catalogue(news_time=news_time, news_cat=news_category)
-        flt = {"time_window": time_window, "categories": categories}
+    if time_window is not None or categories is not None or prior_gain is not None:
+        eng.set_catalogue(news_time=news_time, news_cat=news_category, news_prior=prior)
+        flt = {"time_window": time_window, "categories": categories, "prior_gain": prior_gain}
     return {"ranks": _host(eng.rank_targets(target_index, target_len_list, exclude_history=exclude_history, **flt))}
 
 

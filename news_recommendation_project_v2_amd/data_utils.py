@@ -276,6 +276,32 @@ def catalogue_first_seen(impression_time: np.ndarray, hist_idx: np.ndarray, hist
     return first
 
 
+def history_popularity(hist_idx: np.ndarray, hist_len: np.ndarray, n_news: int) -> np.ndarray:
+    """float32 [n_news] in [0, 1]: log1p of the number of DISTINCT histories a news occurs in,
+    divided by its maximum (all zeros when no history holds a news) -- the ``news_prior`` of
+    PoolScoreEngine.set_catalogue for a popularity prior.  MIND repeats a user's history on
+    every impression of that user, so identical histories count once, and so does a news
+    that a history holds twice.  It is built from past clicks only: an evaluation against
+    the impressions' labels does not see them."""
+    idx = np.asarray(hist_idx, dtype=np.int64)
+    lens = np.asarray(hist_len, dtype=np.int64)
+    if len(lens) and int(lens.min()) < 0:
+        raise ValueError("history lengths must be >= 0")
+    if int(lens.sum()) != len(idx):
+        raise ValueError(f"lengths sum to {int(lens.sum())} but {len(idx)} indices were given")
+    n_news = int(n_news)
+    if len(idx) and (idx.min() < 0 or idx.max() >= n_news):
+        raise IndexError(f"news index outside the {n_news} news")
+    count = np.zeros(n_news, dtype=np.int64)
+    if len(idx):
+        group, _ = distinct_segments(idx, lens)
+        pairs = np.unique(np.repeat(group, lens) * n_news + idx)  # one per (distinct history, news)
+        count = np.bincount(pairs % n_news, minlength=n_news)
+    pop = np.log1p(count.astype(np.float64))
+    top = pop.max() if n_news else 0.0
+    return (pop / top if top > 0 else pop).astype(np.float32)
+
+
 MIND_TIME_FORMAT = "%m/%d/%Y %I:%M:%S %p"  # the Time column of behaviors.tsv: 11/15/2019 8:55:22 AM
 
 

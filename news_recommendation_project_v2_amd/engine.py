@@ -100,11 +100,42 @@ def section_masks(sections) -> list:
     return masks
 
 
-class _Queries:
-    """The distinct (history, time window, category mask) tuples of the loaded impressions
-    under a catalogue filter: retrieval and ranks run once per query."""
+def check_prior(news_prior, n_news: Optional[int]) -> np.ndarray:
+    """set_catalogue's ``news_prior`` as contiguous f32 [N]: one finite value per news."""
+    a = np.asarray(news_prior)
+    if a.ndim != 1 or (n_news is not None and len(a) != n_news):
+        raise ValueError("news_prior must have one entry per news" + ("" if n_news is None else f" ({n_news})"))
+    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("news_prior must be numbers")
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if not np.isfinite(a).all():
+        raise ValueError("news_prior must be finite")
+    return a
 
-    def __init__(self, user: np.ndarray, sel: np.ndarray, lo, hi, mask, dev):
+
+def check_gain(prior_gain, n_imp: int) -> np.ndarray:
+    """``prior_gain`` (a scalar or one value per impression) as finite f32 [n_imp]."""
+    try:
+        g = np.asarray(prior_gain, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("prior_gain must be a number or one number per impression") from None
+    if g.ndim > 1 or (g.ndim == 1 and len(g) != n_imp):
+        raise ValueError(f"prior_gain must be a scalar or have one value per impression ({n_imp})")
+    if not np.isfinite(g).all():
+        raise ValueError("prior_gain must be finite")
+    return np.ascontiguousarray(np.broadcast_to(g, (n_imp,))) + np.float32(0)  # (-0 and +0 are one gain)
+
+
+def _no_prior(what: str, prior_gain) -> None:
+    if prior_gain is not None:
+        raise ValueError(f"{what}: prior_gain cannot be combined with diversify or explain")
+
+
+class _Queries:
+    """The distinct (history, time window, category mask, prior gain) tuples of the loaded
+    impressions under a catalogue filter or a prior: retrieval and ranks run once per query."""
+
+    def __init__(self, user: np.ndarray, sel: np.ndarray, lo, hi, mask, dev, gain=None):
         self.n = len(user)
         self.user_host, self.sel_host = user, sel
         self.user = _upload(user.astype(np.int64), dev)  # the query's pooled user row
@@ -112,6 +143,7 @@ class _Queries:
         self.lo = None if lo is None else _upload(lo, dev)
         self.hi = None if hi is None else _upload(hi, dev)
         self.mask = None if mask is None else _upload(mask, dev)
+        self.gain = None if gain is None else _upload(gain, dev)
 
 
 class PoolScoreEngine:
@@ -128,8 +160,9 @@ class PoolScoreEngine:
         self.hist_table = None
         self._ws = None
         self._users = None  # f32 [distinct histories, D], reused across steps
-        self.news_time = None  # int32 [N] / uint8 [N]: set_catalogue
+        self.news_time = None  # int32 [N] / uint8 [N] / f32 [N]: set_catalogue
         self.news_cat = None
+        self.news_prior = None
 
     # ------------------------------------------------------------ inputs
     def load_news(self, news_embeddings: torch.Tensor, query_news_embeddings: Optional[torch.Tensor] = None):
@@ -142,12 +175,15 @@ class PoolScoreEngine:
         self._check_rows()
         return self
 
-    def set_catalogue(self, news_time=None, news_cat=None):
+    def set_catalogue(self, news_time=None, news_cat=None, news_prior=None):
         """Per-news attributes for the catalogue filters of recommend, recommend_diverse,
         recommend_explained and rank_targets: ``news_time`` int32 [N] (any unit; e.g. the
         time a news was first seen) and ``news_cat`` [N] category ids (0 .. 63 can be asked
-        for; 64 .. 255 never match).  None drops an attribute."""
+        for; 64 .. 255 never match); and for ``prior_gain`` (recommend, recommend_sections,
+        rank_targets) ``news_prior`` f32 [N], finite: a popularity or recency value per news.
+        None drops an attribute."""
         n = None if self.cand_table is None else self.cand_table.shape[0]
+        prior = None if news_prior is None else check_prior(news_prior, n)
         up = {}
         for name, arr, dt in (("news_time", news_time, np.int32), ("news_cat", news_cat, np.uint8)):
             if arr is None:
@@ -161,16 +197,19 @@ class PoolScoreEngine:
                 raise ValueError(f"{name} must be integers in the range of {np.dtype(dt).name}")
             up[name] = _upload(np.ascontiguousarray(a, dtype=dt), self.device)
         self.news_time, self.news_cat = up["news_time"], up["news_cat"]
+        self.news_prior = None if prior is None else _upload(prior, self.device)
         return self
 
-    def _queries(self, time_window, categories) -> Optional[_Queries]:
-        """None without a filter argument (today's paths run), else the distinct queries.
-        ``time_window`` = (lo, hi), ``categories`` = a 64-bit mask; each a scalar or one
-        value per impression."""
-        if time_window is None and categories is None:
+    def _queries(self, time_window, categories, prior_gain=None) -> Optional[_Queries]:
+        """None without a filter or prior argument (today's paths run), else the distinct
+        queries.  ``time_window`` = (lo, hi), ``categories`` = a 64-bit mask, ``prior_gain`` = the
+        gain of the set news_prior; each a scalar or one value per impression."""
+        if time_window is None and categories is None and prior_gain is None:
             return None
+        if prior_gain is not None and getattr(self, "news_prior", None) is None:
+            raise ValueError("prior_gain needs set_catalogue(news_prior=...)")
         n = self.n_imp
-        lo = hi = mask = None
+        lo = hi = mask = gain = None
         keys = [self.user_idx.cpu().numpy().astype(np.int64) if self.user_idx is not None
                 else np.arange(n, dtype=np.int64)]
         if time_window is not None:
@@ -190,16 +229,21 @@ class PoolScoreEngine:
                          dtype=np.uint64).view(np.int64)
             mask = np.ascontiguousarray(np.broadcast_to(m, (n,)))
             keys.append(mask)
+        if prior_gain is not None:
+            gain = check_gain(prior_gain, n)
+            keys.append(gain.view(np.int32).astype(np.int64))
+            if self.news_prior.numel() != self.cand_table.shape[0]:
+                raise ValueError("the catalogue attributes must have one entry per news")
         if self.news_time is not None and self.news_time.numel() != self.cand_table.shape[0] or (
                 self.news_cat is not None and self.news_cat.numel() != self.cand_table.shape[0]):
             raise ValueError("the catalogue attributes must have one entry per news")
         if n == 0:
             e = np.zeros(0, np.int64)
-            return _Queries(e, e, lo, hi, mask, self.device)
+            return _Queries(e, e, lo, hi, mask, self.device, gain)
         _, first, sel = np.unique(np.stack(keys, axis=1), axis=0, return_index=True, return_inverse=True)
         sel = np.asarray(sel).reshape(-1)
         pick = lambda a: None if a is None else np.ascontiguousarray(a[first])
-        return _Queries(keys[0][first], sel, pick(lo), pick(hi), pick(mask), self.device)
+        return _Queries(keys[0][first], sel, pick(lo), pick(hi), pick(mask), self.device, pick(gain))
 
     def _query_block(self, q: _Queries, users, hidx, hoff, a: int, b: int, exclude_history: bool):
         """Queries [a, b): their pooled rows gathered (f32, so a block bounds them), their
@@ -218,6 +262,8 @@ class PoolScoreEngine:
                    time_lo=None if q.lo is None else q.lo[a:b], time_hi=None if q.hi is None else q.hi[a:b],
                    news_cat=self.news_cat if q.mask is not None else None,
                    cat_mask=None if q.mask is None else q.mask[a:b])
+        if q.gain is not None:  # the callers then run the prior entries
+            flt.update(news_prior=self.news_prior, user_gain=q.gain[a:b])
         return users[qu], eidx, eoff, flt
 
     def _distinct_hist(self):
@@ -351,26 +397,35 @@ class PoolScoreEngine:
         return self.pool_score(want_users=want_users, scores=scores)
 
     def _recommend_distinct(self, k: int, exclude_history: bool, user_block: Optional[int],
-                            q: Optional[_Queries] = None):
+                            q: Optional[_Queries] = None, want_keys: bool = False):
         """recommend's lists per DISTINCT history (the deduplicated CSR when
         load_impressions built it, else one per impression): (idx [n_u, k], scores [n_u, k]).
-        Under a catalogue filter ``q``: per distinct query, [q.n, k]."""
+        Under a catalogue filter or a prior ``q``: per distinct query, [q.n, k].  ``want_keys``
+        appends what the lists are ordered by (the scores themselves without a prior)."""
         self.hist_table = self.transform(out=self.hist_table)
         self.inv_norms()
         hidx, hoff = self._distinct_hist()
         n_rows = hoff.numel() - 1 if q is None else q.n
         idx = torch.empty((n_rows, k), dtype=torch.int32, device=self.device)
         scores = torch.empty((n_rows, k), dtype=torch.float32, device=self.device)
-        if n_rows == 0:
-            return idx, scores
-        users = self._pooled_users(hidx, hoff)  # pooled once per distinct history, searched once per distinct query
-        blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
-        need = ops.topk_workspace_bytes(self.dtype, blk, self.cand_table.shape[0], k)
-        self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, self.device)
-        for a, b, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history):
-            (ops.topk_users_filtered if flt else ops.topk_users)(
-                rows, self.cand_table, self.cand_inv, k, excl_idx=eidx, excl_off=eoff, out=(idx[a:b], scores[a:b]),
-                workspace=self._topk_ws, **flt)
+        prior = q is not None and q.gain is not None
+        keys = torch.empty((n_rows, k), dtype=torch.float32, device=self.device) if prior else None
+        if n_rows:
+            users = self._pooled_users(hidx, hoff)  # pooled once per distinct history, searched once per distinct query
+            blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
+            need = (ops.topk_users_prior_workspace_bytes if prior else ops.topk_workspace_bytes)(
+                self.dtype, blk, self.cand_table.shape[0], k)
+            self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, self.device)
+            for a, b, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history):
+                if prior:
+                    ops.topk_users_prior(rows, self.cand_table, self.cand_inv, k, excl_idx=eidx, excl_off=eoff,
+                                         out=(idx[a:b], scores[a:b], keys[a:b]), workspace=self._topk_ws, **flt)
+                    continue
+                (ops.topk_users_filtered if flt else ops.topk_users)(
+                    rows, self.cand_table, self.cand_inv, k, excl_idx=eidx, excl_off=eoff,
+                    out=(idx[a:b], scores[a:b]), workspace=self._topk_ws, **flt)
+        if want_keys:
+            return idx, scores, (keys if prior else scores.clone())
         return idx, scores
 
     def _expansion(self, q: Optional[_Queries]) -> Optional[torch.Tensor]:
@@ -380,7 +435,7 @@ class PoolScoreEngine:
         return None if self.user_idx is None else self.user_idx.long()
 
     def recommend(self, k: int, exclude_history: bool = True, user_block: Optional[int] = None,
-                  time_window=None, categories=None):
+                  time_window=None, categories=None, prior_gain=None, want_keys: bool = False):
         """The k best news of the WHOLE table per impression (ops.topk_users over the
         pooled users): (idx int32 [I, k], scores f32 [I, k]), score descending, ties by
         ascending row, (-1, -inf) where fewer than k rows are eligible; the scores are
@@ -394,16 +449,24 @@ class PoolScoreEngine:
         news_time <= hi (inclusive; lo > hi is empty), ``categories`` = a 64-bit mask keeps
         the news whose category's bit is set; each a scalar or one value per impression.
         Users are still pooled once per distinct history; the table is searched once per
-        distinct (history, lo, hi, mask).  Without either argument nothing changes."""
-        q = self._queries(time_window, categories)
-        idx, scores = self._recommend_distinct(k, exclude_history, user_block, q)
+        distinct (history, lo, hi, mask).  Without either argument nothing changes.
+
+        ``prior_gain`` = g (a finite scalar or one value per impression; needs
+        set_catalogue(news_prior=...)) selects and orders the news by ``score + g * news_prior``
+        (ops.topk_users_prior): a popularity or recency prior; g = 0 changes nothing for that
+        impression, and an empty history is ordered by the prior alone.  The gain is part of
+        the distinct query.  The returned scores stay the cosines; ``want_keys`` appends the
+        keys f32 [I, k] the lists are ordered by (the scores themselves without a gain).
+        Without ``prior_gain`` today's paths run."""
+        q = self._queries(time_window, categories, prior_gain)
+        out = self._recommend_distinct(k, exclude_history, user_block, q, want_keys=want_keys)
         sel = self._expansion(q)
-        if sel is not None and idx.shape[0]:
-            return idx[sel], scores[sel]
-        return idx, scores
+        if sel is not None and out[0].shape[0]:
+            return tuple(t[sel] for t in out)
+        return out
 
     def recommend_sections(self, k: int, sections, exclude_history: bool = True, user_block: Optional[int] = None,
-                           time_window=None):
+                           time_window=None, prior_gain=None, want_keys: bool = False):
         """A front page per impression: the k best eligible news of each of S sections, from
         ONE walk over the table (ops.topk_sections): (idx int32 [I, S, k], scores f32
         [I, S, k]).  ``sections`` is a sequence whose items are a 64-bit category mask or an
@@ -411,7 +474,9 @@ class PoolScoreEngine:
         S * k <= 64.  Section s equals recommend(k, categories=mask_s, time_window=...) bit
         for bit.  Needs set_catalogue(news_cat=...), with ``time_window`` also news_time.
         Users are pooled once per distinct history and the table is searched once per
-        distinct (history, lo, hi); the results do not depend on ``user_block``."""
+        distinct (history, lo, hi); the results do not depend on ``user_block``.  ``prior_gain`` /
+        ``want_keys`` are recommend's (ops.topk_sections_prior): section s then equals
+        recommend(k, categories=mask_s, prior_gain=...), keys included."""
         masks = section_masks(sections)
         k, n_sec = int(k), len(masks)
         if not 1 <= n_sec <= 16 or k < 1 or n_sec * k > 64:
@@ -426,31 +491,40 @@ class PoolScoreEngine:
             raise ValueError("sections needs set_catalogue(news_cat=...)")
         if self.news_cat.numel() != self.cand_table.shape[0]:
             raise ValueError("the catalogue attributes must have one entry per news")
-        q = self._queries(time_window, None)
+        q = self._queries(time_window, None, prior_gain)
         self.hist_table = self.transform(out=self.hist_table)
         self.inv_norms()
         hidx, hoff = self._distinct_hist()
         n_rows = hoff.numel() - 1 if q is None else q.n
         idx = torch.empty((n_rows, n_sec, k), dtype=torch.int32, device=self.device)
         scores = torch.empty((n_rows, n_sec, k), dtype=torch.float32, device=self.device)
-        if n_rows == 0:
-            return idx, scores
-        users = self._pooled_users(hidx, hoff)
-        blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
-        need = ops.topk_sections_workspace_bytes(self.dtype, blk, self.cand_table.shape[0], n_sec, k)
-        self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, self.device)
-        for a, b, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history):
-            ops.topk_sections(rows, self.cand_table, self.cand_inv, k, masks, self.news_cat,
-                              news_time=flt.get("news_time"), time_lo=flt.get("time_lo"), time_hi=flt.get("time_hi"),
-                              excl_idx=eidx, excl_off=eoff, out=(idx[a:b], scores[a:b]), workspace=self._topk_ws)
+        prior = q is not None and q.gain is not None
+        keys = torch.empty((n_rows, n_sec, k), dtype=torch.float32, device=self.device) if prior else None
+        if n_rows:
+            users = self._pooled_users(hidx, hoff)
+            blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
+            need = (ops.topk_sections_prior_workspace_bytes if prior else ops.topk_sections_workspace_bytes)(
+                self.dtype, blk, self.cand_table.shape[0], n_sec, k)
+            self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, self.device)
+            for a, b, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history):
+                win = dict(news_time=flt.get("news_time"), time_lo=flt.get("time_lo"), time_hi=flt.get("time_hi"))
+                if prior:
+                    ops.topk_sections_prior(rows, self.cand_table, self.cand_inv, k, masks, self.news_cat,
+                                            news_prior=flt["news_prior"], user_gain=flt["user_gain"], excl_idx=eidx,
+                                            excl_off=eoff, out=(idx[a:b], scores[a:b], keys[a:b]),
+                                            workspace=self._topk_ws, **win)
+                    continue
+                ops.topk_sections(rows, self.cand_table, self.cand_inv, k, masks, self.news_cat, excl_idx=eidx,
+                                  excl_off=eoff, out=(idx[a:b], scores[a:b]), workspace=self._topk_ws, **win)
+        out = (idx, scores) + (((keys if prior else scores.clone()),) if want_keys else ())
         sel = self._expansion(q)
-        if sel is not None:
-            return idx[sel], scores[sel]
-        return idx, scores
+        if sel is not None and n_rows:
+            return tuple(t[sel] for t in out)
+        return out
 
     def recommend_diverse(self, k: int, lam: float, pool: int = 64, exclude_history: bool = True,
                           user_block: Optional[int] = None, want_ild: bool = False, want_plain: bool = False,
-                          time_window=None, categories=None):
+                          time_window=None, categories=None, prior_gain=None):
         """recommend's lists re-ranked for diversity (ops.rerank_mmr, greedy MMR): the
         ``pool`` best news per distinct history are retrieved as recommend(pool) does,
         k of them are picked one at a time, each maximising lam * score - (1 - lam) *
@@ -461,7 +535,9 @@ class PoolScoreEngine:
         recommend(k)'s list and of the returned one; with ``want_plain`` also recommend(k)'s
         scores f32 [I, k] (the pool's first k), for comparing the relevance given up.
         lam = 1 returns recommend(k).  ``time_window`` / ``categories`` filter the retrieved pool
-        as in recommend; the re-ranking itself sees only that pool."""
+        as in recommend; the re-ranking itself sees only that pool.  ``prior_gain`` is refused:
+        MMR re-ranks by the scores alone."""
+        _no_prior("recommend_diverse", prior_gain)
         q = self._queries(time_window, categories)
         idx, scores, ild, pscores = self._diverse_distinct(k, lam, pool, exclude_history, user_block, want_ild, q)
         k = int(k)
@@ -490,7 +566,8 @@ class PoolScoreEngine:
                            out=(idx, scores, None, ild, None))
         return idx, scores, ild, pscores
 
-    def explain(self, idx: torch.Tensor, top: int = 3, want_sum: bool = False, want_matrix: bool = False):
+    def explain(self, idx: torch.Tensor, top: int = 3, want_sum: bool = False, want_matrix: bool = False,
+                prior_gain=None):
         """Why these news: the exact per-click attribution of the scores of one list per
         impression (ops.explain_scores over the loaded history CSR).  ``idx`` int32 [I, K]
         rows of the news table (K <= 64; an entry outside the table is a pad): recommend's
@@ -501,7 +578,9 @@ class PoolScoreEngine:
         history's length or for a pad); with ``want_sum`` also f32 [I, K], every click's
         contributions added up (pool_score's score of the pair); with ``want_matrix`` also
         f32 [len(hist_idx), K], all of them.  The pooler table and the inverse norms are
-        computed when a step has not left them."""
+        computed when a step has not left them.  ``prior_gain`` is refused: a prior is no click's
+        contribution."""
+        _no_prior("explain", prior_gain)
         idx = torch.as_tensor(idx).to(self.device)
         if idx.dim() != 2 or idx.shape[0] != self.n_imp:
             raise ValueError("Number of rows should be consistent")
@@ -532,11 +611,13 @@ class PoolScoreEngine:
 
     def recommend_explained_filtered(self, k: int, time_window=None, categories=None, top: int = 3,
                                      lam: Optional[float] = None, pool: int = 64, exclude_history: bool = True,
-                                     user_block: Optional[int] = None):
+                                     user_block: Optional[int] = None, prior_gain=None):
         """recommend_explained under recommend's catalogue filters ``time_window`` /
         ``categories``: the filtered lists are expanded to the impressions first and explained
         against each impression's own history.  Without a filter argument it is
-        recommend_explained itself."""
+        recommend_explained itself.  ``prior_gain`` is refused, as in explain (recommend_explained
+        does not take the argument at all)."""
+        _no_prior("recommend_explained", prior_gain)
         q = self._queries(time_window, categories)
         if lam is None:
             idx, scores = self._recommend_distinct(int(k), exclude_history, user_block, q)
@@ -564,7 +645,7 @@ class PoolScoreEngine:
         return idx, scores, why, val
 
     def rank_targets(self, tgt_idx, tgt_len, exclude_history: bool = True, user_block: Optional[int] = None,
-                     time_window=None, categories=None):
+                     time_window=None, categories=None, prior_gain=None):
         """Full-table ranks of given news per impression (ops.rank_targets over the pooled
         users): int32 [T] in the caller's target order, ``tgt_len[i]`` targets (rows of the
         news table, e.g. the clicked candidates) for impression i.  A rank is the number
@@ -575,16 +656,19 @@ class PoolScoreEngine:
         targets are grouped under their distinct user (a stable sort) and the ranks
         scattered back.  ``user_block`` bounds the workspace; the results depend on neither.
         ``time_window`` / ``categories`` (as in recommend) count only the eligible news, and a
-        target that its impression's filter leaves out gets -1."""
+        target that its impression's filter leaves out gets -1.  ``prior_gain`` (as in recommend)
+        ranks on ``score + g * news_prior`` (ops.rank_targets_prior): the targets with rank < k are
+        then recommend(k, prior_gain=...)'s rows."""
         tgt_idx = np.ascontiguousarray(tgt_idx, dtype=np.int32)
         tgt_len = np.asarray(tgt_len, dtype=np.int64)
         if len(tgt_len) != self.n_imp:
             raise ValueError("Number of rows should be consistent")
         _check_segments(tgt_idx, tgt_len, "target")
+        q = self._queries(time_window, categories, prior_gain)
         self.hist_table = self.transform(out=self.hist_table)
         self.inv_norms()
         hidx, hoff = self._distinct_hist()
-        q = self._queries(time_window, categories)
+        prior = q is not None and q.gain is not None
         n_u = hoff.numel() - 1
         n_t = len(tgt_idx)
         ranks = torch.empty(n_t, dtype=torch.int32, device=self.device)
@@ -604,14 +688,15 @@ class PoolScoreEngine:
         blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
         n_news = self.cand_table.shape[0]
         most = max(int(toff[min(u0 + blk, n_rows)] - toff[u0]) for u0 in range(0, n_rows, blk))
-        need = ops.rank_targets_workspace_bytes(self.dtype, blk, n_news, most)
+        need = (ops.rank_targets_prior_workspace_bytes if prior else ops.rank_targets_workspace_bytes)(
+            self.dtype, blk, n_news, most)
         self._rank_ws = ops.grow_workspace(getattr(self, "_rank_ws", None), max(need, 256), self.device)
         sorted_ranks = ranks if order is None else torch.empty_like(ranks)
         has_targets = lambda u0, u1: toff[u0] != toff[u1]
         for u0, u1, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history,
                                                           wanted=has_targets):
             a, b = int(toff[u0]), int(toff[u1])
-            (ops.rank_targets_filtered if flt else ops.rank_targets)(
+            (ops.rank_targets_prior if prior else ops.rank_targets_filtered if flt else ops.rank_targets)(
                 rows, self.cand_table, self.cand_inv, tidx_d[a:b], _upload(toff[u0:u1 + 1] - a, self.device),
                 excl_idx=eidx, excl_off=eoff, out=sorted_ranks[a:b], workspace=self._rank_ws, **flt)
         if order is not None:

@@ -382,17 +382,27 @@ def _check_filter(what: str, n_users: int, n_news: int, news_time, time_lo, time
 
 def topk_users(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int,
                excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
-               out=None, workspace: Optional[torch.Tensor] = None, _filter=None):
+               out=None, workspace: Optional[torch.Tensor] = None, _filter=None, _prior=None):
     """The k best rows of ``cand_table`` per user row (nr_topk_users): returns
     (idx int32 [U, k], scores f32 [U, k]), score descending, ties by ascending row,
     a short tail as (-1, -inf); the scores are score_users' bit for bit.  The CSR
     (excl_idx int32, excl_off int64 [U + 1]) lists rows a user must not get; its
     entries are range-checked here (one small sync).  ``out`` = (idx, scores) to
     write into."""
-    dev = _dev(users, cand_table, cand_inv_norm, excl_idx, excl_off, workspace, *(out or ()), *(_filter or ()))
+    dev = _dev(users, cand_table, cand_inv_norm, excl_idx, excl_off, workspace, *(out or ()), *(_filter or ()),
+               *(_prior or ()))
     n_users, dim, n_news, ld, dt, excl_idx = _check_scan("topk_users", users, cand_table, cand_inv_norm, excl_idx,
                                                          excl_off)
     k = int(k)
+    if _prior is not None:  # topk_users_prior: (idx, scores, keys)
+        pptr = _check_prior("topk_users_prior", n_users, n_news, *_prior)
+        fptr = _check_filter("topk_users_prior", n_users, n_news, *(_filter or (None,) * 5))
+        idx, scores, keys = _keyed_outputs("topk_users_prior", out, (n_users, k), dev)
+        ws = grow_workspace(workspace, topk_users_prior_workspace_bytes(cand_table.dtype, n_users, n_news, k), dev)
+        _lib.call("nr_topk_users_prior", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
+                  _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, *pptr, k, _ptr(idx), _ptr(scores),
+                  _ptr(keys), _ptr(ws), ws.numel(), _stream(dev))
+        return idx, scores, keys
     if out is None:
         idx = torch.empty((n_users, k), dtype=torch.int32, device=dev)
         scores = torch.empty((n_users, k), dtype=torch.float32, device=dev)
@@ -424,6 +434,58 @@ def topk_users_filtered(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_
                       workspace=workspace, _filter=(news_time, time_lo, time_hi, news_cat, cat_mask))
 
 
+def _check_prior(what: str, n_users: int, n_news: int, news_prior, user_gain) -> list:
+    """Host checks of a rank-one prior (include/newsrec_prior.h): the two pointers in the C
+    order.  Both or neither; f32 [N] and f32 [U].  (Finite values are the caller's promise,
+    as for the table: PoolScoreEngine checks what it is given on the host.)"""
+    if (news_prior is None) != (user_gain is None):
+        raise _lib.NewsRecHIPError(f"{what}: news_prior and user_gain go together")
+    for t, name, n in ((news_prior, "news_prior", n_news), (user_gain, "user_gain", n_users)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous()):
+            raise _lib.NewsRecHIPError(f"{what}: {name} must be contiguous {torch.float32} [{n}]")
+    return [_ptr(news_prior), _ptr(user_gain)]
+
+
+def _keyed_outputs(what: str, out, shape, dev):
+    """(idx int32, scores f32, keys f32) of ``shape``: the caller's ``out`` checked, or new ones."""
+    if out is None:
+        return (torch.empty(shape, dtype=torch.int32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev),
+                torch.empty(shape, dtype=torch.float32, device=dev))
+    if len(out) != 3 or any(t is None or t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+                            for t, dt in zip(out, (torch.int32, torch.float32, torch.float32))):
+        raise _lib.NewsRecHIPError(f"{what}: out must be contiguous (int32, f32, f32) of shape {tuple(shape)}")
+    return tuple(out)
+
+
+def topk_users_prior_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) -> int:
+    """nr_topk_users_prior_workspace_bytes (include/newsrec_prior.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_topk_users_prior_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, k))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"topk_users_prior: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, k = {k}; "
+            f"k in [1, {_lib.NR_TOPK_MAX}], N <= 2^22)")
+    return need
+
+
+def topk_users_prior(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int,
+                     news_prior: Optional[torch.Tensor] = None, user_gain: Optional[torch.Tensor] = None,
+                     news_time: Optional[torch.Tensor] = None, time_lo: Optional[torch.Tensor] = None,
+                     time_hi: Optional[torch.Tensor] = None, news_cat: Optional[torch.Tensor] = None,
+                     cat_mask: Optional[torch.Tensor] = None, excl_idx: Optional[torch.Tensor] = None,
+                     excl_off: Optional[torch.Tensor] = None, out=None, workspace: Optional[torch.Tensor] = None):
+    """topk_users_filtered with a rank-one prior (nr_topk_users_prior): news are selected and
+    ordered by ``cosine + user_gain[u] * news_prior[c]`` (f32 [N], f32 [U]).  Returns (idx
+    int32 [U, k], scores f32 [U, k], keys f32 [U, k]): the scores are still score_users' bit
+    for bit, ``keys = fl32(scores + fl32(gain * prior))`` is what the list is ordered by
+    (descending, ties by ascending row; a short tail is (-1, -inf, -inf)).  A user with gain
+    0 gets topk_users_filtered's list; a zero user is ordered by the prior alone.  Without
+    the pair the result is topk_users_filtered's bit for bit and keys == scores.  ``out`` =
+    (idx, scores, keys) to write into."""
+    return topk_users(users, cand_table, cand_inv_norm, k, excl_idx=excl_idx, excl_off=excl_off, out=out,
+                      workspace=workspace, _filter=(news_time, time_lo, time_hi, news_cat, cat_mask),
+                      _prior=(news_prior, user_gain))
+
+
 def section_masks(sections) -> list:
     """``sections`` (a sequence of 64-bit masks: Python ints, int64 or uint64) as a list of
     Python ints in [0, 2^64): the same 64 bits whichever way they came."""
@@ -446,7 +508,7 @@ def topk_sections(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: 
                   news_cat: torch.Tensor, news_time: Optional[torch.Tensor] = None,
                   time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
                   excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None, out=None,
-                  workspace: Optional[torch.Tensor] = None):
+                  workspace: Optional[torch.Tensor] = None, _prior=None):
     """The k best eligible rows of each of S sections per user row, from one walk over the
     table (nr_topk_sections): returns (idx int32 [U, S, k], scores f32 [U, S, k]).
     ``sections`` is a sequence of S disjoint 64-bit category masks (Python ints, int64 or
@@ -454,7 +516,7 @@ def topk_sections(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: 
     equals topk_users_filtered(k, cat_mask = sections[s]) with the same time window and
     exclusion lists, bit for bit."""
     dev = _dev(users, cand_table, cand_inv_norm, news_cat, news_time, time_lo, time_hi, excl_idx, excl_off, workspace,
-               *(out or ()))
+               *(out or ()), *(_prior or ()))
     n_users, dim, n_news, ld, dt, excl_idx = _check_scan("topk_sections", users, cand_table, cand_inv_norm, excl_idx,
                                                          excl_off)
     if (news_cat is None or news_cat.dtype != torch.uint8 or news_cat.dim() != 1 or news_cat.numel() != n_news
@@ -464,8 +526,18 @@ def topk_sections(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: 
     n_sec, k = len(masks), int(k)
     tptr = _check_filter("topk_sections", n_users, n_news, news_time, time_lo, time_hi, None, None)[:3]
     tptr.append(_ptr(news_cat))
-    need = topk_sections_workspace_bytes(cand_table.dtype, n_users, n_news, n_sec, k)
     shape = (n_users, n_sec, k)
+    sec = (ctypes.c_uint64 * n_sec)(*masks)  # read on the host, before the call returns
+    if _prior is not None:  # topk_sections_prior: (idx, scores, keys)
+        pptr = _check_prior("topk_sections_prior", n_users, n_news, *_prior)
+        need = topk_sections_prior_workspace_bytes(cand_table.dtype, n_users, n_news, n_sec, k)
+        idx, scores, keys = _keyed_outputs("topk_sections_prior", out, shape, dev)
+        ws = grow_workspace(workspace, need, dev)
+        _lib.call("nr_topk_sections_prior", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
+                  _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *tptr, ctypes.cast(sec, ctypes.c_void_p), *pptr,
+                  n_sec, k, _ptr(idx), _ptr(scores), _ptr(keys), _ptr(ws), ws.numel(), _stream(dev))
+        return idx, scores, keys
+    need = topk_sections_workspace_bytes(cand_table.dtype, n_users, n_news, n_sec, k)
     if out is None:
         idx = torch.empty(shape, dtype=torch.int32, device=dev)
         scores = torch.empty(shape, dtype=torch.float32, device=dev)
@@ -475,11 +547,35 @@ def topk_sections(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: 
                 or tuple(scores.shape) != shape or not idx.is_contiguous() or not scores.is_contiguous()):
             raise _lib.NewsRecHIPError(f"topk_sections: out must be contiguous (int32, f32) of shape {shape}")
     ws = grow_workspace(workspace, need, dev)
-    sec = (ctypes.c_uint64 * n_sec)(*masks)  # read on the host, before the call returns
     _lib.call("nr_topk_sections", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld, _ptr(cand_inv_norm),
               _ptr(excl_idx), _ptr(excl_off), *tptr, ctypes.cast(sec, ctypes.c_void_p), n_sec, k, _ptr(idx),
               _ptr(scores), _ptr(ws), ws.numel(), _stream(dev))
     return idx, scores
+
+
+def topk_sections_prior_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, n_sections: int, k: int) -> int:
+    """nr_topk_sections_prior_workspace_bytes (include/newsrec_prior.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_topk_sections_prior_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, n_sections, k))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"topk_sections_prior: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, S = {n_sections}, "
+            f"k = {k}; S in [1, {_lib.NR_SECTIONS_MAX}], k >= 1, S * k <= {_lib.NR_TOPK_MAX}, N <= 2^22)")
+    return need
+
+
+def topk_sections_prior(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int, sections,
+                        news_cat: torch.Tensor, news_prior: Optional[torch.Tensor] = None,
+                        user_gain: Optional[torch.Tensor] = None, news_time: Optional[torch.Tensor] = None,
+                        time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
+                        excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None, out=None,
+                        workspace: Optional[torch.Tensor] = None):
+    """topk_sections with topk_users_prior's rank-one prior (nr_topk_sections_prior): returns
+    (idx int32 [U, S, k], scores f32 [U, S, k], keys f32 [U, S, k]).  Section s equals
+    topk_users_prior(k, cat_mask = sections[s]) with the same prior, time window and
+    exclusion lists, bit for bit, keys included."""
+    return topk_sections(users, cand_table, cand_inv_norm, k, sections, news_cat, news_time=news_time,
+                         time_lo=time_lo, time_hi=time_hi, excl_idx=excl_idx, excl_off=excl_off, out=out,
+                         workspace=workspace, _prior=(news_prior, user_gain))
 
 
 def rank_targets_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, n_targets: int) -> int:
@@ -495,7 +591,7 @@ def rank_targets_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, 
 def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, tgt_idx: torch.Tensor,
                  tgt_off: torch.Tensor, excl_idx: Optional[torch.Tensor] = None,
                  excl_off: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                 workspace: Optional[torch.Tensor] = None, _filter=None) -> torch.Tensor:
+                 workspace: Optional[torch.Tensor] = None, _filter=None, _prior=None) -> torch.Tensor:
     """Full-table ranks of target rows (nr_rank_targets): for the targets
     tgt_idx[tgt_off[u]:tgt_off[u + 1]] (int32, int64 [U + 1]) of user row u, int32 [T]
     with the number of eligible rows of ``cand_table`` that beat the target in top-K's
@@ -505,7 +601,7 @@ def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: t
     topk_users takes it; its entries and the target offsets are checked here (one
     small sync).  ``out`` = int32 [T] to write into."""
     dev = _dev(users, cand_table, cand_inv_norm, tgt_idx, tgt_off, excl_idx, excl_off, workspace, out,
-               *(_filter or ()))
+               *(_filter or ()), *(_prior or ()))
     n_users, dim, n_news, ld, dt, excl_idx = _check_scan("rank_targets", users, cand_table, cand_inv_norm, excl_idx,
                                                          excl_off)
     _check_csr(tgt_idx, tgt_off, "tgt")
@@ -519,6 +615,16 @@ def rank_targets(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: t
         out = torch.empty(n_tgt, dtype=torch.int32, device=dev)
     elif out.dtype != torch.int32 or out.shape != (n_tgt,) or not out.is_contiguous():
         raise _lib.NewsRecHIPError(f"rank_targets: out must be contiguous int32 of shape {(n_tgt,)}")
+    if _prior is not None:  # rank_targets_prior
+        pptr = _check_prior("rank_targets_prior", n_users, n_news, *_prior)
+        fptr = _check_filter("rank_targets_prior", n_users, n_news, *(_filter or (None,) * 5))
+        ws = grow_workspace(workspace, rank_targets_prior_workspace_bytes(cand_table.dtype, n_users, n_news, n_tgt),
+                            dev)
+        if n_tgt:
+            _lib.call("nr_rank_targets_prior", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
+                      _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, *pptr, n_tgt, _ptr(tgt_idx),
+                      _ptr(tgt_off), _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
+        return out
     ws = grow_workspace(workspace, max(rank_targets_workspace_bytes(cand_table.dtype, n_users, n_news, n_tgt), 256), dev)
     fptr = [] if _filter is None else _check_filter("rank_targets_filtered", n_users, n_news, *_filter)
     if n_tgt == 0:
@@ -542,6 +648,31 @@ def rank_targets_filtered(users: torch.Tensor, cand_table: torch.Tensor, cand_in
     targets with rank < k are exactly the rows topk_users_filtered returns."""
     return rank_targets(users, cand_table, cand_inv_norm, tgt_idx, tgt_off, excl_idx=excl_idx, excl_off=excl_off,
                         out=out, workspace=workspace, _filter=(news_time, time_lo, time_hi, news_cat, cat_mask))
+
+
+def rank_targets_prior_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, n_targets: int) -> int:
+    """nr_rank_targets_prior_workspace_bytes (include/newsrec_prior.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_rank_targets_prior_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, n_targets))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"rank_targets_prior: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, T = {n_targets}; "
+            "U >= 1, 1 <= N <= 2^22, T < 2^31)")
+    return need
+
+
+def rank_targets_prior(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor,
+                       tgt_idx: torch.Tensor, tgt_off: torch.Tensor, news_prior: Optional[torch.Tensor] = None,
+                       user_gain: Optional[torch.Tensor] = None, news_time: Optional[torch.Tensor] = None,
+                       time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
+                       news_cat: Optional[torch.Tensor] = None, cat_mask: Optional[torch.Tensor] = None,
+                       excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rank_targets_filtered under topk_users_prior's rank-one prior (nr_rank_targets_prior): the
+    eligible rows are counted on the keys ``cosine + user_gain[u] * news_prior[c]``.  For
+    k <= 64 the targets with rank < k are exactly the rows topk_users_prior returns."""
+    return rank_targets(users, cand_table, cand_inv_norm, tgt_idx, tgt_off, excl_idx=excl_idx, excl_off=excl_off,
+                        out=out, workspace=workspace, _filter=(news_time, time_lo, time_hi, news_cat, cat_mask),
+                        _prior=(news_prior, user_gain))
 
 
 def rerank_mmr(cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, list_idx: torch.Tensor, list_rel: torch.Tensor,

@@ -117,6 +117,16 @@ def catalogue_attributes(n_news: int, n_imp: int, seed: int = 1234, n_categories
     return when, cats
 
 
+def catalogue_prior(n_news: int, seed: int = 1234) -> np.ndarray:
+    """A seeded per-news prior in [0, 1] for the rank-one prior of retrieval (float32
+    [n_news]): the long tail of a popularity count, log1p of a Zipf-like draw divided by its
+    maximum.  Like catalogue_attributes it has a generator stream of its own."""
+    rng = np.random.default_rng([int(seed), 0x9810121])
+    pop = np.log1p(np.floor(1.0 / np.maximum(rng.random(int(n_news)), 1e-6) - 1.0))
+    top = pop.max() if n_news else 0.0
+    return (pop / top if top > 0 else pop).astype(np.float32)
+
+
 def mind_shaped(name: str = "mind_large_dev", seed: int = 1234, **kw) -> Impressions:
     n_news, n_imp = SHAPES[name]
     return mind_impressions(n_news, n_imp, seed=seed, **kw)

@@ -10,6 +10,7 @@ has no counterpart -- it only scores the candidates an impression lists).
     python scripts/recommend.py --synthetic --explain 3
     python scripts/recommend.py --synthetic --evaluate --as-of [--fresh 48] [--categories 0,3,7]
     python scripts/recommend.py --synthetic --sections "0,1;2;3,4,5" -k 4 [--as-of [--fresh 24]]
+    python scripts/recommend.py --synthetic --prior popularity --prior-gain 0.2 [--prior-cold 1] [--evaluate]
 
 Prints one JSON line per run and writes {out-dir}/recommendations.npy: an int32
 [I, K] array of rows of the split's news list (-1 where fewer than K are eligible).
@@ -46,6 +47,15 @@ all from one walk over the table.  recommendations.npy is then int32 [I, S, K], 
 row of the news list).  The JSON line gains section_fill, per section the share of its slots
 that hold a news.  It composes with --as-of
 and --fresh and is refused with --categories, --diversify, --explain and --evaluate.
+--prior popularity|FILE.npy with --prior-gain G selects and orders the news by score + G * prior
+(include/newsrec_prior.h): "popularity" is data_utils.history_popularity of the split's
+histories (past clicks only: --evaluate does not see its own labels), FILE.npy a float array
+with one finite value per row of the news list.  --prior-cold G0 is the gain of the impressions
+with an empty history (default G), which are then ordered by the prior alone.
+{out-dir}/recommendations_keys.npy holds what the lists are ordered by, the scores stay the
+cosines, and the JSON line gains prior, prior_gain, prior_cold and mean_top1_key.  It works with
+--evaluate, --as-of, --fresh, --categories and --sections and is refused with --diversify and
+--explain.
 """
 from __future__ import annotations
 
@@ -120,6 +130,24 @@ def catalogue_filter(args, out, ctx) -> dict:
     return flt
 
 
+def prior_arguments(args, out) -> dict:
+    """get_top_k_recommendations' / get_full_table_ranks' prior arguments for --prior ({} without it)."""
+    if args.prior is None:
+        return {}
+    hist_len = np.asarray(out["history_len_list"], dtype=np.int64)
+    n_news = len(out["news_list"])
+    if args.prior == "popularity":
+        from news_recommendation_project_v2_amd.data_utils import history_popularity
+        prior = history_popularity(out["history_rev_ind_array"][0], hist_len, n_news)
+    else:
+        prior = np.load(args.prior)
+        if prior.ndim != 1 or len(prior) != n_news:
+            raise SystemExit(f"--prior: {args.prior} must hold one value per news ({n_news})")
+    cold = args.prior_gain if args.prior_cold is None else args.prior_cold
+    gain = np.where(hist_len > 0, np.float32(args.prior_gain), np.float32(cold)).astype(np.float32)
+    return {"prior": np.asarray(prior, dtype=np.float32), "prior_gain": gain}
+
+
 def mean_eligible(flt: dict) -> float:
     """Mean number of news inside an impression's window and mask (the exclusion of its own history aside)."""
     ok = np.ones(len(flt["news_time"] if "news_time" in flt else flt["news_category"]), dtype=bool)
@@ -167,7 +195,21 @@ def main():
     ap.add_argument("--sections", default=None, metavar="A,B;C;...",
                     help="a front page: -k news for each of these sections of categories (names; ids with "
                          "--synthetic), from one walk over the table")
+    ap.add_argument("--prior", default=None, metavar="popularity|FILE.npy",
+                    help="a per-news prior added to the score with --prior-gain: the popularity of the split's "
+                         "histories, or one float per row of the news list")
+    ap.add_argument("--prior-gain", type=float, default=None, metavar="G", help="order by score + G * prior")
+    ap.add_argument("--prior-cold", type=float, default=None, metavar="G0",
+                    help="the gain of impressions with an empty history (default G)")
     args = ap.parse_args()
+    if (args.prior is None) != (args.prior_gain is None):
+        ap.error("--prior and --prior-gain go together")
+    if args.prior_cold is not None and args.prior is None:
+        ap.error("--prior-cold needs --prior")
+    if args.prior is not None:
+        for flag, on in (("--diversify", args.diversify is not None), ("--explain", args.explain is not None)):
+            if on:
+                ap.error(f"--prior cannot be combined with {flag}")
     if args.sections is not None:
         for flag, on in (("--categories", args.categories is not None), ("--diversify", args.diversify is not None),
                          ("--explain", args.explain is not None), ("--evaluate", args.evaluate)):
@@ -202,6 +244,7 @@ def main():
     out, _ = Pipeline(f"recommend_{args.split}", [("init_transform", TransformData()),
                                                   ("load_embedding", loader)]).transform(ctx)
     flt = catalogue_filter(args, out, ctx)
+    pri = prior_arguments(args, out)
     t0 = time.perf_counter()
     rec = dmh.get_top_k_recommendations(out["history_rev_ind_array"][0], out["history_len_list"],
                                         out["news_embeddings"], model, args.k,
@@ -209,7 +252,7 @@ def main():
                                         dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
                                         **({} if args.diversify is None else
                                            {"diversify": args.diversify, "pool": args.pool}),
-                                        **({} if args.explain is None else {"explain": args.explain}), **flt)
+                                        **({} if args.explain is None else {"explain": args.explain}), **flt, **pri)
     ms = (time.perf_counter() - t0) * 1e3
     idx, scores = rec["news_index"], rec["scores"]
     args.out_dir.mkdir(parents=True, exist_ok=True)
@@ -231,6 +274,13 @@ def main():
     if flt:
         line.update(as_of=args.as_of, fresh_hours=args.fresh, categories=args.categories,
                     mean_eligible_news=mean_eligible(flt))
+    if pri:
+        keys_path = args.out_dir / "recommendations_keys.npy"
+        np.save(keys_path, rec["keys"])
+        line.update(prior=args.prior, prior_gain=args.prior_gain,
+                    prior_cold=args.prior_gain if args.prior_cold is None else args.prior_cold,
+                    mean_top1_key=float(rec["keys"][..., 0][have[..., 0]].mean()) if have[..., :1].any() else None,
+                    keys_out=str(keys_path))
     if args.diversify is not None:
         from news_recommendation_project_v2_amd.evaluation import diversity_metrics
         line.update(diversify=args.diversify, pool=args.pool or 64)
@@ -254,7 +304,7 @@ def main():
                                          np.asarray(out["impression_rev_ind_array"][0])[clicked], tgt_len,
                                          out["news_embeddings"], model, exclude_history=not args.keep_history,
                                          dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
-                                         **flt)["ranks"]
+                                         **flt, **pri)["ranks"]
         line["evaluate_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
         metrics = retrieval_metrics(ranks, tgt_len, ks=[int(k) for k in args.ks.split(",")])
         line["impressions_evaluated"] = metrics.pop("impressions")  # ("impressions" stays the number recommended for)
