@@ -19,12 +19,13 @@ INCLUDE = Path(__file__).resolve().parent.parent / "include"
 # translation units of libnewsrec_hip.so, in link order (also the hash order)
 HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip", "encoder.hip", "train.hip",
                "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip", "contrastive.hip", "topk.hip",
-               "fullrank.hip", "rerank.hip", "explain.hip", "sections.hip")
+               "fullrank.hip", "rerank.hip", "explain.hip", "sections.hip", "caps.hip")
 # the headers they include (every object is rebuilt when one changes), hashed after the sources
 HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CSRC / "nr_score_tile.h",
                INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
                INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h",
-               INCLUDE / "newsrec_filter.h", INCLUDE / "newsrec_sections.h", INCLUDE / "newsrec_prior.h")
+               INCLUDE / "newsrec_filter.h", INCLUDE / "newsrec_sections.h", INCLUDE / "newsrec_prior.h",
+               INCLUDE / "newsrec_caps.h")
 
 
 def hip_source_files() -> list:
@@ -205,6 +206,15 @@ PRIOR_SIGNATURES = {
                                     _p, _p, _p, _l, _p]),
 }
 
+# per-group caps of retrieval (include/newsrec_caps.h), bound by load() like SIGNATURES:
+# nr_topk_users_prior's arguments with news_group and cap behind user_gain
+NR_CAP_GROUPS_MAX = 1024
+CAPS_SIGNATURES = {
+    "nr_topk_users_capped_workspace_bytes": (_l, [_i, _l, _l, _l]),
+    "nr_topk_users_capped": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _p,
+                                  _p, _p, _p, _l, _p]),
+}
+
 
 class ContrastiveSpec(ctypes.Structure):
     """struct nr_contrastive_spec (include/newsrec_contrastive.h)."""
@@ -263,7 +273,8 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(os.fspath(LIB_PATH))
     for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES,
                               **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES,
-                              **FILTER_SIGNATURES, **SECTIONS_SIGNATURES, **PRIOR_SIGNATURES}.items():
+                              **FILTER_SIGNATURES, **SECTIONS_SIGNATURES, **PRIOR_SIGNATURES,
+                              **CAPS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

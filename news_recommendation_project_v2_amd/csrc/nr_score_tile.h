@@ -644,6 +644,11 @@ static inline TopkLayout topk_layout(int dtype, int64_t U, int64_t N, int64_t K,
 int topk_stage2_launch(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,
                        int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores,
                        float* top_keys = nullptr);
+// Its steps behind the merge (the re-score and the rank sort), for an entry with a merge of its
+// own (caps.hip): that merge has left what topk_merge_kernel leaves in top_idx, cnt, uidx, coff.
+int topk_stage2_finish(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,
+                       int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores,
+                       float* top_keys = nullptr);
 
 }  // namespace tk
 }  // namespace nr

@@ -358,6 +358,16 @@ int topk_stage2_launch(const char* fn, const ScanArgs& a, int64_t S, int64_t k, 
   hipLaunchKernelGGL(topk_merge_kernel, gw, dim3(256), 0, st, a.U, (int)S, (int)k, nruns, part, top_idx, cnt, uidx,
                      coff);
   NR_CHECK_LAUNCH(fn);
+  return topk_stage2_finish(fn, a, S, k, nruns, part, cnt, uidx, coff, top_idx, top_scores, top_keys);
+}
+
+int topk_stage2_finish(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,
+                       int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores,
+                       float* top_keys) {
+  hipStream_t st = (hipStream_t)a.stream;
+  const int64_t R = a.U * S;
+  const dim3 gw((unsigned)((R + 3) / 4));
+  if (S != 1) cnt = nullptr;
   const int rc = nr::score_users_dispatch(a.dtype, a.users, uidx, a.cand_table, a.cand_ld, a.cand_inv_norm, top_idx,
                                           coff, a.U, top_scores, st);
   if (rc) return rc;

@@ -157,7 +157,8 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
                               exclude_history: bool = True, query_news_embeddings: Optional[torch.Tensor] = None,
                               dtype=None, diversify: Optional[float] = None, pool: Optional[int] = None,
                               news_time=None, news_category=None, time_window=None, categories=None,
-                              sections=None, prior=None, prior_gain=None, explain: Optional[int] = None) -> dict:
+                              sections=None, prior=None, prior_gain=None, groups=None, group_cap=None,
+                              explain: Optional[int] = None) -> dict:
     """The k news of the WHOLE table that the model recommends per impression:
     ``{"news_index": int32 [I, k], "scores": float32 [I, k]}`` on the host, score
     descending, ties by ascending news row, ``(-1, -inf)`` where fewer than k news are
@@ -206,7 +207,25 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     nothing, an impression with an empty history gets the news with the largest prior.  The
     ``scores`` stay the cosines and the result gains ``"keys"`` float32, shaped like them: what
     the lists are ordered by.  It composes with the catalogue filters and ``sections``; with
-    ``diversify`` or ``explain`` it is refused."""
+    ``diversify`` or ``explain`` it is refused.
+
+    ``groups`` [N] integer labels in [0, 1024) (data_utils.dense_groups makes them from category
+    names, sub-categories, publishers ...) with ``group_cap`` = c in 1 .. 64 allows at most c
+    news of one group in a list (PoolScoreEngine.recommend's ``group_cap``,
+    include/newsrec_caps.h): the eligible news are walked best first and one is taken while
+    its group holds fewer than c, so a list may end in ``(-1, -inf)`` before k.  Both or
+    neither; it composes with the catalogue filters and the prior (the result then has
+    ``"keys"``), and is refused with ``sections``, ``diversify`` and ``explain``."""
+    if (groups is None) != (group_cap is None):
+        raise ValueError("get_top_k_recommendations: groups and group_cap go together")
+    if group_cap is not None:
+        if sections is not None or diversify is not None or explain is not None or pool is not None:
+            raise ValueError("get_top_k_recommendations: group_cap cannot be combined with sections, diversify or "
+                             "explain")
+        from .engine import check_groups
+        check_groups(groups, news_embeddings.shape[0])  # bad labels are refused before any device work
+        if isinstance(group_cap, bool) or not isinstance(group_cap, (int, np.integer)) or not 1 <= group_cap <= 64:
+            raise ValueError(f"get_top_k_recommendations: group_cap = {group_cap!r} must be an integer in 1 .. 64")
     _check_prior_args("get_top_k_recommendations", prior, prior_gain, news_embeddings.shape[0],
                       len(history_len_list), diversify is not None or explain is not None or pool is not None)
     if sections is not None:
@@ -237,9 +256,14 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
         idx, scores = eng.recommend_sections(k, sections, exclude_history=exclude_history, time_window=time_window)
         return {"news_index": _host(idx), "scores": _host(scores)}
     flt = {}
-    if time_window is not None or categories is not None or prior_gain is not None:
-        eng.set_catalogue(news_time=news_time, news_cat=news_category, news_prior=prior)
+    if time_window is not None or categories is not None or prior_gain is not None or group_cap is not None:
+        eng.set_catalogue(news_time=news_time, news_cat=news_category, news_prior=prior, news_group=groups)
         flt = {"time_window": time_window, "categories": categories}
+    if group_cap is not None:
+        idx, scores, keys = eng.recommend(k, exclude_history=exclude_history, prior_gain=prior_gain, want_keys=True,
+                                          group_cap=int(group_cap), **flt)
+        res = {"news_index": _host(idx), "scores": _host(scores)}
+        return {**res, "keys": _host(keys)} if prior_gain is not None else res
     if prior_gain is not None:
         idx, scores, keys = eng.recommend(k, exclude_history=exclude_history, prior_gain=prior_gain, want_keys=True,
                                           **flt)

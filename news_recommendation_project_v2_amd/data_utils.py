@@ -302,6 +302,33 @@ def history_popularity(hist_idx: np.ndarray, hist_len: np.ndarray, n_news: int) 
     return (pop / top if top > 0 else pop).astype(np.float32)
 
 
+GROUPS_MAX = 1024  # NR_CAP_GROUPS_MAX (include/newsrec_caps.h)
+
+
+def dense_groups(labels):
+    """(ids uint16 [N], names): any 1-D array of hashable labels -- category names,
+    sub-category names, publisher ids -- as dense group ids numbered by first appearance,
+    ``names[ids[i]] == labels[i]``: the ``news_group`` of PoolScoreEngine.set_catalogue and the
+    ``groups`` of get_top_k_recommendations.  More than 1024 distinct labels are refused (the
+    limit of the per-group caps, include/newsrec_caps.h)."""
+    arr = labels if isinstance(labels, np.ndarray) else np.asarray(list(labels), dtype=object)
+    if arr.ndim != 1:
+        raise ValueError("labels must be one-dimensional: one label per news")
+    seen: dict = {}
+    names = []
+    ids = np.empty(len(arr), dtype=np.uint16)
+    for i, lab in enumerate(arr.tolist()):
+        g = seen.get(lab)
+        if g is None:
+            g = len(names)
+            if g >= GROUPS_MAX:
+                raise ValueError(f"more than {GROUPS_MAX} distinct labels (entry {i}: {lab!r})")
+            seen[lab] = g
+            names.append(lab)
+        ids[i] = g
+    return ids, names
+
+
 MIND_TIME_FORMAT = "%m/%d/%Y %I:%M:%S %p"  # the Time column of behaviors.tsv: 11/15/2019 8:55:22 AM
 
 

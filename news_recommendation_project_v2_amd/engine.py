@@ -131,6 +131,28 @@ def _no_prior(what: str, prior_gain) -> None:
         raise ValueError(f"{what}: prior_gain cannot be combined with diversify or explain")
 
 
+def _no_cap(what: str, group_cap) -> None:
+    if group_cap is not None:
+        raise ValueError(f"{what}: group_cap is recommend's alone (no ranks, sections, MMR or explained lists "
+                         "under per-group caps)")
+
+
+def check_groups(news_group, n_news: Optional[int]) -> np.ndarray:
+    """set_catalogue's ``news_group`` as contiguous int16 [N]: one integer label in [0, 1024)
+    per news (the 16 bits the kernels read as uint16)."""
+    a = news_group.cpu().numpy() if isinstance(news_group, torch.Tensor) else np.asarray(news_group)
+    if a.ndim != 1 or (n_news is not None and len(a) != n_news):
+        raise ValueError("news_group must have one entry per news" + ("" if n_news is None else f" ({n_news})"))
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("news_group must be integer labels (data_utils.dense_groups makes them)")
+    if len(a) and (a.min() < 0 or a.max() >= GROUPS_MAX):
+        raise ValueError(f"news_group labels must lie in [0, {GROUPS_MAX})")
+    return np.ascontiguousarray(a, dtype=np.int16)
+
+
+GROUPS_MAX = 1024  # NR_CAP_GROUPS_MAX (include/newsrec_caps.h)
+
+
 class _Queries:
     """The distinct (history, time window, category mask, prior gain) tuples of the loaded
     impressions under a catalogue filter or a prior: retrieval and ranks run once per query."""
@@ -163,6 +185,7 @@ class PoolScoreEngine:
         self.news_time = None  # int32 [N] / uint8 [N] / f32 [N]: set_catalogue
         self.news_cat = None
         self.news_prior = None
+        self.news_group = None  # int16 [N]
 
     # ------------------------------------------------------------ inputs
     def load_news(self, news_embeddings: torch.Tensor, query_news_embeddings: Optional[torch.Tensor] = None):
@@ -175,15 +198,18 @@ class PoolScoreEngine:
         self._check_rows()
         return self
 
-    def set_catalogue(self, news_time=None, news_cat=None, news_prior=None):
+    def set_catalogue(self, news_time=None, news_cat=None, news_prior=None, news_group=None):
         """Per-news attributes for the catalogue filters of recommend, recommend_diverse,
         recommend_explained and rank_targets: ``news_time`` int32 [N] (any unit; e.g. the
         time a news was first seen) and ``news_cat`` [N] category ids (0 .. 63 can be asked
         for; 64 .. 255 never match); and for ``prior_gain`` (recommend, recommend_sections,
-        rank_targets) ``news_prior`` f32 [N], finite: a popularity or recency value per news.
+        rank_targets) ``news_prior`` f32 [N], finite: a popularity or recency value per news; and
+        for recommend's ``group_cap`` ``news_group`` [N], integer labels in [0, 1024) on the host
+        or the device (data_utils.dense_groups makes them from any labels).
         None drops an attribute."""
         n = None if self.cand_table is None else self.cand_table.shape[0]
         prior = None if news_prior is None else check_prior(news_prior, n)
+        groups = None if news_group is None else check_groups(news_group, n)
         up = {}
         for name, arr, dt in (("news_time", news_time, np.int32), ("news_cat", news_cat, np.uint8)):
             if arr is None:
@@ -198,6 +224,7 @@ class PoolScoreEngine:
             up[name] = _upload(np.ascontiguousarray(a, dtype=dt), self.device)
         self.news_time, self.news_cat = up["news_time"], up["news_cat"]
         self.news_prior = None if prior is None else _upload(prior, self.device)
+        self.news_group = None if groups is None else _upload(groups, self.device)
         return self
 
     def _queries(self, time_window, categories, prior_gain=None) -> Optional[_Queries]:
@@ -397,11 +424,20 @@ class PoolScoreEngine:
         return self.pool_score(want_users=want_users, scores=scores)
 
     def _recommend_distinct(self, k: int, exclude_history: bool, user_block: Optional[int],
-                            q: Optional[_Queries] = None, want_keys: bool = False):
+                            q: Optional[_Queries] = None, want_keys: bool = False, group_cap=None):
         """recommend's lists per DISTINCT history (the deduplicated CSR when
         load_impressions built it, else one per impression): (idx [n_u, k], scores [n_u, k]).
         Under a catalogue filter or a prior ``q``: per distinct query, [q.n, k].  ``want_keys``
-        appends what the lists are ordered by (the scores themselves without a prior)."""
+        appends what the lists are ordered by (the scores themselves without a prior).
+        ``group_cap``: at most that many news of one news_group per list (ops.topk_users_capped)."""
+        capped = group_cap is not None
+        if capped:
+            if isinstance(group_cap, bool) or not isinstance(group_cap, (int, np.integer)) or not 1 <= group_cap <= 64:
+                raise ValueError(f"group_cap = {group_cap!r} must be an integer in 1 .. 64")
+            if getattr(self, "news_group", None) is None:
+                raise ValueError("group_cap needs set_catalogue(news_group=...)")
+            if self.news_group.numel() != self.cand_table.shape[0]:
+                raise ValueError("the catalogue attributes must have one entry per news")
         self.hist_table = self.transform(out=self.hist_table)
         self.inv_norms()
         hidx, hoff = self._distinct_hist()
@@ -409,14 +445,19 @@ class PoolScoreEngine:
         idx = torch.empty((n_rows, k), dtype=torch.int32, device=self.device)
         scores = torch.empty((n_rows, k), dtype=torch.float32, device=self.device)
         prior = q is not None and q.gain is not None
-        keys = torch.empty((n_rows, k), dtype=torch.float32, device=self.device) if prior else None
+        keys = torch.empty((n_rows, k), dtype=torch.float32, device=self.device) if prior or capped else None
         if n_rows:
             users = self._pooled_users(hidx, hoff)  # pooled once per distinct history, searched once per distinct query
             blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
-            need = (ops.topk_users_prior_workspace_bytes if prior else ops.topk_workspace_bytes)(
+            need = (ops.topk_users_prior_workspace_bytes if prior or capped else ops.topk_workspace_bytes)(
                 self.dtype, blk, self.cand_table.shape[0], k)
             self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, self.device)
             for a, b, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history):
+                if capped:
+                    ops.topk_users_capped(rows, self.cand_table, self.cand_inv, k, self.news_group, int(group_cap),
+                                          excl_idx=eidx, excl_off=eoff, out=(idx[a:b], scores[a:b], keys[a:b]),
+                                          workspace=self._topk_ws, **flt)
+                    continue
                 if prior:
                     ops.topk_users_prior(rows, self.cand_table, self.cand_inv, k, excl_idx=eidx, excl_off=eoff,
                                          out=(idx[a:b], scores[a:b], keys[a:b]), workspace=self._topk_ws, **flt)
@@ -425,7 +466,7 @@ class PoolScoreEngine:
                     rows, self.cand_table, self.cand_inv, k, excl_idx=eidx, excl_off=eoff,
                     out=(idx[a:b], scores[a:b]), workspace=self._topk_ws, **flt)
         if want_keys:
-            return idx, scores, (keys if prior else scores.clone())
+            return idx, scores, (keys if prior or capped else scores.clone())
         return idx, scores
 
     def _expansion(self, q: Optional[_Queries]) -> Optional[torch.Tensor]:
@@ -435,7 +476,7 @@ class PoolScoreEngine:
         return None if self.user_idx is None else self.user_idx.long()
 
     def recommend(self, k: int, exclude_history: bool = True, user_block: Optional[int] = None,
-                  time_window=None, categories=None, prior_gain=None, want_keys: bool = False):
+                  time_window=None, categories=None, prior_gain=None, want_keys: bool = False, group_cap=None):
         """The k best news of the WHOLE table per impression (ops.topk_users over the
         pooled users): (idx int32 [I, k], scores f32 [I, k]), score descending, ties by
         ascending row, (-1, -inf) where fewer than k rows are eligible; the scores are
@@ -457,16 +498,22 @@ class PoolScoreEngine:
         impression, and an empty history is ordered by the prior alone.  The gain is part of
         the distinct query.  The returned scores stay the cosines; ``want_keys`` appends the
         keys f32 [I, k] the lists are ordered by (the scores themselves without a gain).
-        Without ``prior_gain`` today's paths run."""
+        Without ``prior_gain`` today's paths run.
+
+        ``group_cap`` = c (1 .. 64; needs set_catalogue(news_group=...)) allows at most c news
+        of one group in a list (ops.topk_users_capped): the eligible news are walked best first
+        and one is taken while its group holds fewer than c, until k are taken, so a list may
+        be shorter than k.  It composes with every argument above; c >= k changes nothing, and
+        without ``group_cap`` today's paths run."""
         q = self._queries(time_window, categories, prior_gain)
-        out = self._recommend_distinct(k, exclude_history, user_block, q, want_keys=want_keys)
+        out = self._recommend_distinct(k, exclude_history, user_block, q, want_keys=want_keys, group_cap=group_cap)
         sel = self._expansion(q)
         if sel is not None and out[0].shape[0]:
             return tuple(t[sel] for t in out)
         return out
 
     def recommend_sections(self, k: int, sections, exclude_history: bool = True, user_block: Optional[int] = None,
-                           time_window=None, prior_gain=None, want_keys: bool = False):
+                           time_window=None, prior_gain=None, want_keys: bool = False, group_cap=None):
         """A front page per impression: the k best eligible news of each of S sections, from
         ONE walk over the table (ops.topk_sections): (idx int32 [I, S, k], scores f32
         [I, S, k]).  ``sections`` is a sequence whose items are a 64-bit category mask or an
@@ -477,6 +524,7 @@ class PoolScoreEngine:
         distinct (history, lo, hi); the results do not depend on ``user_block``.  ``prior_gain`` /
         ``want_keys`` are recommend's (ops.topk_sections_prior): section s then equals
         recommend(k, categories=mask_s, prior_gain=...), keys included."""
+        _no_cap("recommend_sections", group_cap)
         masks = section_masks(sections)
         k, n_sec = int(k), len(masks)
         if not 1 <= n_sec <= 16 or k < 1 or n_sec * k > 64:
@@ -524,7 +572,7 @@ class PoolScoreEngine:
 
     def recommend_diverse(self, k: int, lam: float, pool: int = 64, exclude_history: bool = True,
                           user_block: Optional[int] = None, want_ild: bool = False, want_plain: bool = False,
-                          time_window=None, categories=None, prior_gain=None):
+                          time_window=None, categories=None, prior_gain=None, group_cap=None):
         """recommend's lists re-ranked for diversity (ops.rerank_mmr, greedy MMR): the
         ``pool`` best news per distinct history are retrieved as recommend(pool) does,
         k of them are picked one at a time, each maximising lam * score - (1 - lam) *
@@ -538,6 +586,7 @@ class PoolScoreEngine:
         as in recommend; the re-ranking itself sees only that pool.  ``prior_gain`` is refused:
         MMR re-ranks by the scores alone."""
         _no_prior("recommend_diverse", prior_gain)
+        _no_cap("recommend_diverse", group_cap)
         q = self._queries(time_window, categories)
         idx, scores, ild, pscores = self._diverse_distinct(k, lam, pool, exclude_history, user_block, want_ild, q)
         k = int(k)
@@ -611,13 +660,15 @@ class PoolScoreEngine:
 
     def recommend_explained_filtered(self, k: int, time_window=None, categories=None, top: int = 3,
                                      lam: Optional[float] = None, pool: int = 64, exclude_history: bool = True,
-                                     user_block: Optional[int] = None, prior_gain=None):
+                                     user_block: Optional[int] = None, prior_gain=None, group_cap=None):
         """recommend_explained under recommend's catalogue filters ``time_window`` /
         ``categories``: the filtered lists are expanded to the impressions first and explained
         against each impression's own history.  Without a filter argument it is
-        recommend_explained itself.  ``prior_gain`` is refused, as in explain (recommend_explained
-        does not take the argument at all)."""
+        recommend_explained itself.  ``prior_gain`` and ``group_cap`` are refused, the first as in
+        explain (recommend_explained does not take either argument at all); ``explain(idx)`` takes
+        any lists, recommend's capped ones included."""
         _no_prior("recommend_explained", prior_gain)
+        _no_cap("recommend_explained", group_cap)
         q = self._queries(time_window, categories)
         if lam is None:
             idx, scores = self._recommend_distinct(int(k), exclude_history, user_block, q)
@@ -645,7 +696,7 @@ class PoolScoreEngine:
         return idx, scores, why, val
 
     def rank_targets(self, tgt_idx, tgt_len, exclude_history: bool = True, user_block: Optional[int] = None,
-                     time_window=None, categories=None, prior_gain=None):
+                     time_window=None, categories=None, prior_gain=None, group_cap=None):
         """Full-table ranks of given news per impression (ops.rank_targets over the pooled
         users): int32 [T] in the caller's target order, ``tgt_len[i]`` targets (rows of the
         news table, e.g. the clicked candidates) for impression i.  A rank is the number
@@ -659,6 +710,7 @@ class PoolScoreEngine:
         target that its impression's filter leaves out gets -1.  ``prior_gain`` (as in recommend)
         ranks on ``score + g * news_prior`` (ops.rank_targets_prior): the targets with rank < k are
         then recommend(k, prior_gain=...)'s rows."""
+        _no_cap("rank_targets", group_cap)
         tgt_idx = np.ascontiguousarray(tgt_idx, dtype=np.int32)
         tgt_len = np.asarray(tgt_len, dtype=np.int64)
         if len(tgt_len) != self.n_imp:

@@ -291,6 +291,55 @@ def diversity_metrics(ild, idx=None, categories=None, rel_before=None, rel_after
     return out
 
 
+def group_cap_metrics(idx, groups, cap, scores_capped=None, scores_plain=None) -> dict:
+    """Summary of lists retrieved under per-group caps (data_model_helper.get_top_k_recommendations
+    with ``groups`` / ``group_cap``; the reference has no counterpart).  Host numpy in float64.
+
+    ``idx`` int [I, k]: the lists (-1 entries are pads and left out); ``groups`` int [N]: one
+    label per news row; ``cap``: the cap the lists were retrieved under.  Returns ``lists``;
+    ``max_group_count``, the largest number of news of one group in any list (<= cap when the
+    caps held; 0 without a list entry); ``at_cap_share``, the share of lists in which at least
+    one group reached the cap; ``distinct_groups``, the mean number of distinct groups per
+    list; and, when ``scores_capped`` and ``scores_plain`` [I, k] (the capped lists' scores and
+    the uncapped lists') are both given, ``score_given_up``: the mean over the lists of (mean
+    finite plain score - mean finite capped score)."""
+    ix = np.asarray(idx, dtype=np.int64)
+    grp = np.asarray(groups)
+    if ix.ndim != 2:
+        raise ValueError("idx must be [I, k]")
+    if grp.ndim != 1:
+        raise ValueError("groups must be [N]: one label per news row")
+    cap = int(cap)
+    if cap < 1:
+        raise ValueError(f"cap = {cap} < 1")
+    if ix.size and ix.max() >= len(grp):
+        raise IndexError(f"news row {int(ix.max())} has no group ({len(grp)} were given)")
+    if (scores_capped is None) != (scores_plain is None):
+        raise ValueError("scores_capped and scores_plain go together")
+    nan = float("nan")
+    largest, at_cap, distinct = 0, 0, []
+    for row in ix:
+        _, counts = np.unique(grp[row[row >= 0]], return_counts=True)
+        top = int(counts.max()) if len(counts) else 0
+        largest = max(largest, top)
+        at_cap += top >= cap
+        distinct.append(len(counts))
+    out = {"lists": int(ix.shape[0]), "max_group_count": largest,
+           "at_cap_share": at_cap / len(ix) if len(ix) else nan,
+           "distinct_groups": float(np.mean(distinct)) if distinct else nan}
+    if scores_capped is not None:
+        sc, sp = np.asarray(scores_capped, dtype=np.float64), np.asarray(scores_plain, dtype=np.float64)
+        if sc.shape != ix.shape or sp.ndim != 2 or sp.shape[0] != ix.shape[0]:
+            raise ValueError("scores_capped must be shaped like idx and scores_plain have one row per list")
+        gaps = []
+        for a, b in zip(sc, sp):
+            a, b = a[np.isfinite(a)], b[np.isfinite(b)]
+            if len(a) and len(b):
+                gaps.append(b.mean() - a.mean())
+        out["score_given_up"] = float(np.mean(gaps)) if gaps else nan
+    return out
+
+
 def explanation_metrics(why_share, scores) -> dict:
     """Summary of per-click explanations (data_model_helper.get_top_k_recommendations with
     ``explain``; the reference has no counterpart).  Host numpy in float64.

@@ -486,6 +486,63 @@ def topk_users_prior(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_nor
                       _prior=(news_prior, user_gain))
 
 
+def topk_users_capped_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) -> int:
+    """nr_topk_users_capped_workspace_bytes (include/newsrec_caps.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_topk_users_capped_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, k))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"topk_users_capped: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, k = {k}; "
+            f"k in [1, {_lib.NR_TOPK_MAX}], N <= 2^22)")
+    return need
+
+
+def _check_groups(what: str, n_news: int, news_group, cap) -> int:
+    """Host checks of per-group caps (include/newsrec_caps.h): ``news_group`` 16-bit integers
+    [N] (int16, or uint16 where torch has it: the same bits) with every label in [0,
+    NR_CAP_GROUPS_MAX) -- read back here, one small sync -- and ``cap`` in [1, NR_TOPK_MAX]."""
+    ok16 = (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
+    if (not isinstance(news_group, torch.Tensor) or news_group.dtype not in ok16 or news_group.dim() != 1
+            or news_group.numel() != n_news or not news_group.is_contiguous()):
+        raise _lib.NewsRecHIPError(f"{what}: news_group must be contiguous 16-bit integers [{n_news}]")
+    if isinstance(cap, bool) or int(cap) != cap or not 1 <= int(cap) <= _lib.NR_TOPK_MAX:
+        raise _lib.NewsRecHIPError(f"{what}: cap = {cap!r} outside [1, {_lib.NR_TOPK_MAX}]")
+    if n_news:
+        lo, hi = (int(v) for v in torch.aminmax(news_group.view(torch.int16)))
+        if lo < 0 or hi >= _lib.NR_CAP_GROUPS_MAX:
+            raise _lib.NewsRecHIPError(f"{what}: news_group labels must lie in [0, {_lib.NR_CAP_GROUPS_MAX})")
+    return int(cap)
+
+
+def topk_users_capped(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int,
+                      news_group: torch.Tensor, cap: int, news_prior: Optional[torch.Tensor] = None,
+                      user_gain: Optional[torch.Tensor] = None, news_time: Optional[torch.Tensor] = None,
+                      time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
+                      news_cat: Optional[torch.Tensor] = None, cat_mask: Optional[torch.Tensor] = None,
+                      excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None, out=None,
+                      workspace: Optional[torch.Tensor] = None):
+    """topk_users_prior with at most ``cap`` rows of one group per list (nr_topk_users_capped):
+    ``news_group`` [N] 16-bit labels in [0, 1024) (data_utils.dense_groups makes them), ``cap``
+    in [1, 64].  The list is the greedy one: eligible rows in the order (key descending, row
+    ascending), a row taken while its group holds fewer than ``cap``, until k are taken; it is
+    short, ending in (-1, -inf, -inf), when the caps leave fewer than k rows.  Returns (idx,
+    scores, keys) as topk_users_prior does; without a prior keys == scores.  ``cap >= k`` is
+    topk_users_prior bit for bit.  The filter, the prior and the exclusion CSR compose."""
+    what = "topk_users_capped"
+    dev = _dev(users, cand_table, cand_inv_norm, news_group, news_prior, user_gain, news_time, time_lo, time_hi,
+               news_cat, cat_mask, excl_idx, excl_off, workspace, *(out or ()))
+    n_users, dim, n_news, ld, dt, excl_idx = _check_scan(what, users, cand_table, cand_inv_norm, excl_idx, excl_off)
+    k = int(k)
+    cap = _check_groups(what, n_news, news_group, cap)
+    pptr = _check_prior(what, n_users, n_news, news_prior, user_gain)
+    fptr = _check_filter(what, n_users, n_news, news_time, time_lo, time_hi, news_cat, cat_mask)
+    ws = grow_workspace(workspace, topk_users_capped_workspace_bytes(cand_table.dtype, n_users, n_news, k), dev)
+    idx, scores, keys = _keyed_outputs(what, out, (n_users, k), dev)
+    _lib.call("nr_topk_users_capped", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
+              _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, *pptr, _ptr(news_group), cap, k, _ptr(idx),
+              _ptr(scores), _ptr(keys), _ptr(ws), ws.numel(), _stream(dev))
+    return idx, scores, keys
+
+
 def section_masks(sections) -> list:
     """``sections`` (a sequence of 64-bit masks: Python ints, int64 or uint64) as a list of
     Python ints in [0, 2^64): the same 64 bits whichever way they came."""

@@ -56,6 +56,14 @@ with an empty history (default G), which are then ordered by the prior alone.
 cosines, and the JSON line gains prior, prior_gain, prior_cold and mean_top1_key.  It works with
 --evaluate, --as-of, --fresh, --categories and --sections and is refused with --diversify and
 --explain.
+--cap C [--cap-by category|FILE.npy] allows at most C news of one group in a list
+(include/newsrec_caps.h): the eligible news are walked best first and one is taken while its
+group holds fewer than C, so a list can end before K.  The groups are the per-news categories
+that --categories uses (the default, --synthetic included) or FILE.npy, one label of any kind
+per row of the news list (at most 1024 distinct ones).  The JSON line gains cap, cap_by and
+evaluation.group_cap_metrics of the lists: max_group_count (<= C), at_cap_share and
+distinct_groups.  It composes with --as-of, --fresh, --categories and --prior*, and is refused
+with --sections, --diversify, --explain and --evaluate.
 """
 from __future__ import annotations
 
@@ -148,6 +156,30 @@ def prior_arguments(args, out) -> dict:
     return {"prior": np.asarray(prior, dtype=np.float32), "prior_gain": gain}
 
 
+def cap_arguments(args, out, ctx) -> dict:
+    """get_top_k_recommendations' ``groups`` / ``group_cap`` for --cap ({} without it)."""
+    if args.cap is None:
+        return {}
+    from news_recommendation_project_v2_amd.data_utils import dense_groups
+    news_list = list(out["news_list"])
+    if args.cap_by != "category":
+        labels = np.load(args.cap_by)
+        if labels.ndim != 1 or len(labels) != len(news_list):
+            raise SystemExit(f"--cap-by: {args.cap_by} must hold one label per news ({len(news_list)})")
+    elif args.synthetic:  # the categories of catalogue_filter
+        from news_recommendation_project_v2_amd import synthetic
+        rows = np.array([int(str(n)[1:]) for n in news_list], dtype=np.int64)
+        labels = synthetic.catalogue_attributes(int(rows.max()) + 1, len(out["history_len_list"]), seed=1234)[1][rows]
+    else:
+        per_news = ctx.get("news_category", {})
+        labels = np.array([per_news.get(n, 255) for n in news_list])
+    try:
+        ids, _ = dense_groups(labels)
+    except ValueError as e:
+        raise SystemExit(f"--cap-by: {e}")
+    return {"groups": ids, "group_cap": args.cap}
+
+
 def mean_eligible(flt: dict) -> float:
     """Mean number of news inside an impression's window and mask (the exclusion of its own history aside)."""
     ok = np.ones(len(flt["news_time"] if "news_time" in flt else flt["news_category"]), dtype=bool)
@@ -201,7 +233,20 @@ def main():
     ap.add_argument("--prior-gain", type=float, default=None, metavar="G", help="order by score + G * prior")
     ap.add_argument("--prior-cold", type=float, default=None, metavar="G0",
                     help="the gain of impressions with an empty history (default G)")
+    ap.add_argument("--cap", type=int, default=None, metavar="C", help="at most C news of one group in a list (1..64)")
+    ap.add_argument("--cap-by", default=None, metavar="category|FILE.npy",
+                    help="with --cap: the groups, the news' categories (default) or one label per row of the news list")
     args = ap.parse_args()
+    if args.cap_by is not None and args.cap is None:
+        ap.error("--cap-by needs --cap")
+    if args.cap is not None:
+        if not 1 <= args.cap <= 64:
+            ap.error("--cap must be in 1 .. 64")
+        args.cap_by = args.cap_by or "category"
+        for flag, on in (("--sections", args.sections is not None), ("--diversify", args.diversify is not None),
+                         ("--explain", args.explain is not None), ("--evaluate", args.evaluate)):
+            if on:
+                ap.error(f"--cap cannot be combined with {flag}")
     if (args.prior is None) != (args.prior_gain is None):
         ap.error("--prior and --prior-gain go together")
     if args.prior_cold is not None and args.prior is None:
@@ -245,6 +290,7 @@ def main():
                                                   ("load_embedding", loader)]).transform(ctx)
     flt = catalogue_filter(args, out, ctx)
     pri = prior_arguments(args, out)
+    caps = cap_arguments(args, out, ctx)
     t0 = time.perf_counter()
     rec = dmh.get_top_k_recommendations(out["history_rev_ind_array"][0], out["history_len_list"],
                                         out["news_embeddings"], model, args.k,
@@ -252,7 +298,7 @@ def main():
                                         dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
                                         **({} if args.diversify is None else
                                            {"diversify": args.diversify, "pool": args.pool}),
-                                        **({} if args.explain is None else {"explain": args.explain}), **flt, **pri)
+                                        **({} if args.explain is None else {"explain": args.explain}), **flt, **pri, **caps)
     ms = (time.perf_counter() - t0) * 1e3
     idx, scores = rec["news_index"], rec["scores"]
     args.out_dir.mkdir(parents=True, exist_ok=True)
@@ -281,6 +327,11 @@ def main():
                     prior_cold=args.prior_gain if args.prior_cold is None else args.prior_cold,
                     mean_top1_key=float(rec["keys"][..., 0][have[..., 0]].mean()) if have[..., :1].any() else None,
                     keys_out=str(keys_path))
+    if caps:
+        from news_recommendation_project_v2_amd.evaluation import group_cap_metrics
+        gm = group_cap_metrics(idx, caps["groups"], args.cap)
+        gm.pop("lists")
+        line.update(cap=args.cap, cap_by=args.cap_by, **gm)
     if args.diversify is not None:
         from news_recommendation_project_v2_amd.evaluation import diversity_metrics
         line.update(diversify=args.diversify, pool=args.pool or 64)
