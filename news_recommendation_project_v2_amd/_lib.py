@@ -25,7 +25,7 @@ HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CS
                INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
                INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h",
                INCLUDE / "newsrec_filter.h", INCLUDE / "newsrec_sections.h", INCLUDE / "newsrec_prior.h",
-               INCLUDE / "newsrec_caps.h")
+               INCLUDE / "newsrec_caps.h", INCLUDE / "newsrec_page.h")
 
 
 def hip_source_files() -> list:
@@ -215,6 +215,16 @@ CAPS_SIGNATURES = {
                                   _p, _p, _p, _l, _p]),
 }
 
+# cursors of retrieval (include/newsrec_page.h), bound by load() like SIGNATURES: nr_topk_users_prior's
+# arguments with after_key, after_row, next_key and next_row behind user_gain
+NR_DEEP_MAX = 1024  # the longest list PoolScoreEngine.recommend_deep pages to
+PAGE_SIGNATURES = {
+    "nr_topk_users_after_workspace_bytes": (_l, [_i, _l, _l, _l]),
+    "nr_topk_users_after": (_i, [_i, _l, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                 _l, _p, _p, _p, _p, _l, _p]),
+}
+
+
 
 class ContrastiveSpec(ctypes.Structure):
     """struct nr_contrastive_spec (include/newsrec_contrastive.h)."""
@@ -274,7 +284,7 @@ def load() -> ctypes.CDLL:
     for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES,
                               **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES,
                               **FILTER_SIGNATURES, **SECTIONS_SIGNATURES, **PRIOR_SIGNATURES,
-                              **CAPS_SIGNATURES}.items():
+                              **CAPS_SIGNATURES, **PAGE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

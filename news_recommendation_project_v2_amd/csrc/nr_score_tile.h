@@ -514,7 +514,10 @@ struct ScanArgs {
   void* stream;
   const float* news_prior = nullptr;  // the rank-one prior (include/newsrec_prior.h): [N] and
   const float* user_gain = nullptr;   //   [U], both or neither
+  const float* after_key = nullptr;    // the cursor (include/newsrec_page.h): [U] and [U], both or
+  const int32_t* after_row = nullptr;  //   neither; nr_topk_users_after alone sets it
   bool prior() const { return news_prior != nullptr; }
+  bool after() const { return after_key != nullptr; }
 };
 
 static inline int64_t chunks_of(int64_t N) { return (N + kChunk - 1) / kChunk; }
@@ -595,11 +598,20 @@ static inline int scan_prepare(const char* fn, const ScanArgs& a, void* ub, Scan
 }
 
 // f(TypeTag<TI>, std::bool_constant<FILT>, std::bool_constant<PRIOR>) for the scan's dtype and
-// whether it carries a filter and a prior
+// whether it carries a filter and a prior; an f that takes a fourth tag (topk.hip's stage 1)
+// gets std::bool_constant<AFTER> too: whether the scan carries a cursor
 template <typename F>
 static int with_scan_types(const ScanArgs& a, F&& f) {
   return nr::with_dtype(a.dtype, [&](auto ti) {
-    auto with_prior = [&](auto filt) { return a.prior() ? f(ti, filt, std::true_type{}) : f(ti, filt, std::false_type{}); };
+    auto with_after = [&](auto filt, auto prior) {
+      if constexpr (std::is_invocable_v<F&, decltype(ti), decltype(filt), decltype(prior), std::true_type>)
+        return a.after() ? f(ti, filt, prior, std::true_type{}) : f(ti, filt, prior, std::false_type{});
+      else
+        return f(ti, filt, prior);
+    };
+    auto with_prior = [&](auto filt) {
+      return a.prior() ? with_after(filt, std::true_type{}) : with_after(filt, std::false_type{});
+    };
     return a.flt.any() ? with_prior(std::true_type{}) : with_prior(std::false_type{});
   });
 }
@@ -641,9 +653,11 @@ static inline TopkLayout topk_layout(int dtype, int64_t U, int64_t N, int64_t K,
 // from its runs again, so the workspace is topk_layout(dtype, U, N, S k) for every S.
 // top_keys (null: none wanted) [U][S][k]: with a prior in `a` the rank sort orders by
 // fl(score + fl(gain * prior)) and writes these keys; without one they are the scores.
+// next_key / next_row (null: not wanted) [U S]: each list's last survivor in selection order,
+// the cursor of include/newsrec_page.h.
 int topk_stage2_launch(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,
                        int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores,
-                       float* top_keys = nullptr);
+                       float* top_keys = nullptr, float* next_key = nullptr, int32_t* next_row = nullptr);
 // Its steps behind the merge (the re-score and the rank sort), for an entry with a merge of its
 // own (caps.hip): that merge has left what topk_merge_kernel leaves in top_idx, cnt, uidx, coff.
 int topk_stage2_finish(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,

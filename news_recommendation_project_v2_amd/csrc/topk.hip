@@ -24,6 +24,7 @@
 #include "nr_score_tile.h"
 
 #include "../../include/newsrec_filter.h"
+#include "../../include/newsrec_page.h"
 #include "../../include/newsrec_prior.h"
 #include "../../include/newsrec_topk.h"
 
@@ -85,14 +86,23 @@ int prior_gains_launch(int64_t U, const float* users, const float* gain, float* 
 // all of them.  The unfiltered instantiation holds none of it.
 // PRIOR: the rank-one prior (include/newsrec_prior.h).  The score tile then holds selection
 // keys, and the scan, the heap and the partials below keep keys where they say scores.
-template <typename TI, bool FILT, bool PRIOR>
+// AFTER: the cursor (include/newsrec_page.h).  A row is kept only if it lies strictly behind
+// (cur_key, cur_row) in the order of better(): `v <= cur_key` is ANDed into the scan's masks ahead
+// of the filter, so the rows above the cursor never reach the serial drain, and the drain
+// settles the tie on the row.  Both threads of a user hold its cursor in two registers; no LDS.
+// The instantiations without a cursor hold none of it.
+struct AfterArgs {
+  const float* key = nullptr;
+  const int32_t* row = nullptr;
+};
+template <typename TI, bool FILT, bool PRIOR, bool AFTER>
 __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, const TI* __restrict__ users,
                                                           const TI* __restrict__ tab, int64_t ldt,
                                                           const float* __restrict__ cinv,
                                                           const int32_t* __restrict__ excl_idx,
                                                           const int64_t* __restrict__ excl_off, FilterArgs flt,
                                                           int K, int64_t span_rows, Pair* __restrict__ part,
-                                                          PriorArgs pri) {
+                                                          PriorArgs pri, AfterArgs aft) {
   __shared__ __attribute__((aligned(16))) uint32_t smem[4 * TILE_WORDS];  // ring [2][news | users]; score tile
   __shared__ float ls[KMAX * TS];  // the users' sorted lists, [rank][user]
   __shared__ int32_t li[KMAX * TS];
@@ -115,6 +125,14 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
   const int64_t m0 = w.m0;
   int cnt = 0;            // rows kept so far (a heap in LDS, the worst at slot 0)
   float thr = NINF;       // the worst's score once K are kept; -inf until then (every finite score passes)
+  float cur_key = __builtin_inff();  // AFTER: the user's cursor; (+inf, -1) is the start of the list
+  int32_t cur_row = -1;
+  if constexpr (AFTER) {
+    if (w.live) {
+      cur_key = aft.key[m0 + su];
+      cur_row = aft.row[m0 + su];
+    }
+  }
 
   w.run([&](int64_t n0, float* T) __attribute__((always_inline)) {
     // ---- scan against the running K-th best; what passes and is not excluded is kept (ascending row)
@@ -124,7 +142,10 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const float4 v = *reinterpret_cast<const float4*>(row + 4 * i);
-        const uint32_t b = (v.x > thr ? 1u : 0u) | (v.y > thr ? 2u : 0u) | (v.z > thr ? 4u : 0u) | (v.w > thr ? 8u : 0u);
+        uint32_t b = (v.x > thr ? 1u : 0u) | (v.y > thr ? 2u : 0u) | (v.z > thr ? 4u : 0u) | (v.w > thr ? 8u : 0u);
+        if constexpr (AFTER)  // (a NaN cursor passes nothing)
+          b &= (v.x <= cur_key ? 1u : 0u) | (v.y <= cur_key ? 2u : 0u) | (v.z <= cur_key ? 4u : 0u) |
+               (v.w <= cur_key ? 8u : 0u);
         if (i < 8) mlo |= b << (4 * i);
         else mhi |= b << (4 * (i - 8));
       }
@@ -141,6 +162,9 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
           const int32_t row = (int32_t)(n0 + col);
           // a later row never beats an equal score already kept, so the compare is strict
           if (!(s > thr) || w.ex.staged(row)) continue;  // (the threshold may have risen since the scan)
+          if constexpr (AFTER) {
+            if (s == cur_key && row <= cur_row) continue;  // at the cursor's key: only the rows behind its row
+          }
           // the list is a binary heap with the WORST kept entry (lowest score, then highest
           // row) at slot 0: log2 K steps per kept row
           int i;
@@ -211,10 +235,13 @@ __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, 
 // over the heads of its chunk lists (each sorted).  Lane l keeps the best head among chunks
 // l, l + 64, ... and re-reads them only after it won.  The scoring pass behind it takes a
 // user's S K rows as one list: uidx / coff are per user.  cnt_out may be null (topk_sort_kernel).
+// next_key / next_row (null: not wanted; include/newsrec_page.h): the last round's winner, the
+// list's last survivor in selection order, or the end cursor when fewer than K survived.
 __global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int S, int K, int nchunks,
                                                          const Pair* __restrict__ part, int32_t* __restrict__ top_idx,
                                                          int32_t* __restrict__ cnt_out, int32_t* __restrict__ uidx,
-                                                         int64_t* __restrict__ coff) {
+                                                         int64_t* __restrict__ coff, float* __restrict__ next_key,
+                                                         int32_t* __restrict__ next_row) {
   __shared__ uint8_t head[4][kMaxChunks];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t u = (int64_t)blockIdx.x * 4 + wave;
@@ -243,6 +270,8 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int S, int K
   refresh();
   int32_t mine = 0;  // lane j: the j-th survivor
   int cnt = 0;
+  float last_s = NINF;  // the latest winner (every lane holds the butterfly's result)
+  int32_t last_r = INT32_MAX;
   for (int j = 0; j < K; ++j) {
     float ws = bs;
     int32_t wr = br;
@@ -264,6 +293,8 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int S, int K
     wr = __shfl(wr, 0, 64);
     if (wr == INT32_MAX) break;  // every list is exhausted
     if (lane == j) mine = wr;
+    last_s = ws;
+    last_r = wr;
     ++cnt;
     if (lane == wl) {
       head[wave][bc] += 1;
@@ -273,6 +304,10 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int S, int K
   if (lane < K) top_idx[u * K + lane] = lane < cnt ? mine : 0;  // never row -1 to the scoring gather
   if (lane == 0) {
     if (cnt_out) cnt_out[u] = cnt;
+    if (next_key) {
+      next_key[u] = cnt == K ? last_s : NINF;
+      next_row[u] = cnt == K ? last_r : INT32_MAX;
+    }
     if (u % S == 0) {
       const int64_t user = u / S;
       uidx[user] = (int32_t)user;
@@ -288,7 +323,8 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int S, int K
 // hold (-inf, INT32_MAX) pads, which beat nothing and are never written (a pad in lane
 // j < K still ranks j), so a short list does not pay for 64 rounds.
 // PRIOR (include/newsrec_prior.h): the order is by the key fl(score + fl(gain[user] * prior[row])),
-// list u belonging to user u / S, and the keys go to top_keys beside the untouched scores.
+// list u belonging to user u / S, and the keys go to top_keys (null: not wanted, which
+// nr_topk_users_after alone allows) beside the untouched scores.
 struct SortPrior {
   const float* news_prior;
   const float* user_gain;
@@ -331,7 +367,9 @@ __global__ __launch_bounds__(256) void topk_sort_kernel(int64_t R, int K, const 
   if (rank < K) {
     top_idx[u * K + rank] = valid ? r : -1;
     top_scores[u * K + rank] = s;
-    if constexpr (PRIOR) sp.top_keys[u * K + rank] = key;
+    if constexpr (PRIOR) {
+      if (sp.top_keys) sp.top_keys[u * K + rank] = key;
+    }
   }
 }
 
@@ -350,13 +388,13 @@ namespace tk {
 
 int topk_stage2_launch(const char* fn, const ScanArgs& a, int64_t S, int64_t k, int nruns, const Pair* part,
                        int32_t* cnt, int32_t* uidx, int64_t* coff, int32_t* top_idx, float* top_scores,
-                       float* top_keys) {
+                       float* top_keys, float* next_key, int32_t* next_row) {
   hipStream_t st = (hipStream_t)a.stream;
   const int64_t R = a.U * S;
   const dim3 gw((unsigned)((R + 3) / 4));
   if (S != 1) cnt = nullptr;
   hipLaunchKernelGGL(topk_merge_kernel, gw, dim3(256), 0, st, a.U, (int)S, (int)k, nruns, part, top_idx, cnt, uidx,
-                     coff);
+                     coff, next_key, next_row);
   NR_CHECK_LAUNCH(fn);
   return topk_stage2_finish(fn, a, S, k, nruns, part, cnt, uidx, coff, top_idx, top_scores, top_keys);
 }
@@ -395,25 +433,38 @@ int topk_stage2_finish(const char* fn, const ScanArgs& a, int64_t S, int64_t k, 
   return NR_OK;
 }
 
-// nr_topk_users, nr_topk_users_filtered and nr_topk_users_prior: one validation, one launch
-// sequence.  A filter with both pairs null runs the unfiltered stage 1, a null prior the
-// stage 1 without one.  keyed: the prior entry, whose top_keys is required.
+// nr_topk_users, nr_topk_users_filtered, nr_topk_users_prior and nr_topk_users_after: one
+// validation, one launch sequence.  A filter with both pairs null runs the unfiltered stage 1, a
+// null prior the stage 1 without one, a null cursor the stage 1 without one.  keyed: the prior
+// entry, whose top_keys is required.  paged: the cursor entry (include/newsrec_page.h), with the
+// prior entry's workspace, a nullable top_keys and the next cursor's two arrays (`next`).
+struct NextCursor {
+  float* key = nullptr;
+  int32_t* row = nullptr;
+};
 static int topk_run(const char* fn, const ScanArgs& a, int64_t K, int32_t* top_idx, float* top_scores, void* ws,
-                    int64_t ws_bytes, bool keyed = false, float* top_keys = nullptr) {
+                    int64_t ws_bytes, bool keyed = false, float* top_keys = nullptr, bool paged = false,
+                    NextCursor next = {}) {
   auto k_ok = [&] {
     NR_CHECK_ARG(K >= 1 && K <= KMAX, "%s: K = %lld outside [1, %d]", fn, (long long)K, KMAX);
     return NR_OK;
   };
   if (const int rc = check_scan(fn, a, k_ok, no_check)) return rc;
+  NR_CHECK_ARG((a.after_key == nullptr) == (a.after_row == nullptr), "%s: after_key and after_row go together", fn);
+  NR_CHECK_ARG((next.key == nullptr) == (next.row == nullptr), "%s: next_key and next_row go together", fn);
   NR_CHECK_ARG(top_idx && top_scores && ws && (top_keys || !keyed), "%s: null pointer", fn);
-  const TopkLayout L = topk_layout(a.dtype, a.U, a.N, K, keyed);
+  const TopkLayout L = topk_layout(a.dtype, a.U, a.N, K, keyed || paged);
   NR_CHECK_ARG(ws_bytes >= L.total, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes,
                (long long)L.total);
   NR_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
-  if (const int rc = keyed ? check_scan_device(fn, a, "top_idx, top_scores, top_keys, ws",
-                                               {top_idx, top_scores, top_keys, ws})
-                           : check_scan_device(fn, a, "top_idx, top_scores, ws", {top_idx, top_scores, ws}))
+  if (const int rc = keyed || paged ? check_scan_device(fn, a, "top_idx, top_scores, top_keys, ws",
+                                                        {top_idx, top_scores, top_keys, ws})
+                                    : check_scan_device(fn, a, "top_idx, top_scores, ws", {top_idx, top_scores, ws}))
     return rc;
+  if (paged)
+    if (const int rc = nr::check_device_ptrs(fn, "after_key, after_row, next_key, next_row",
+                                             {a.after_key, a.after_row, next.key, next.row}))
+      return rc;
 
   hipStream_t st = (hipStream_t)a.stream;
   const int64_t U = a.U;
@@ -425,16 +476,18 @@ static int topk_run(const char* fn, const ScanArgs& a, int64_t K, int32_t* top_i
   ScanLaunch sl;
   float* gsel = (float*)(w + L.gsel);
   if (const int rc = scan_prepare(fn, a, w + L.ub, sl, gsel)) return rc;
-  const int rc1 = with_scan_types(a, [&](auto ti, auto filt, auto prior) {
+  const int rc1 = with_scan_types(a, [&](auto ti, auto filt, auto prior, auto after) {
     using TI = typename decltype(ti)::type;
-    hipLaunchKernelGGL((topk_stage1_kernel<TI, decltype(filt)::value, decltype(prior)::value>), sl.g1, dim3(256), 0, st,
-                       U, a.N, (const TI*)sl.urows, (const TI*)a.cand_table, a.cand_ld, a.cand_inv_norm, a.excl_idx,
-                       a.excl_off, a.flt, (int)K, sl.span_rows, part, PriorArgs{a.news_prior, gsel});
+    hipLaunchKernelGGL(
+        (topk_stage1_kernel<TI, decltype(filt)::value, decltype(prior)::value, decltype(after)::value>), sl.g1,
+        dim3(256), 0, st, U, a.N, (const TI*)sl.urows, (const TI*)a.cand_table, a.cand_ld, a.cand_inv_norm, a.excl_idx,
+        a.excl_off, a.flt, (int)K, sl.span_rows, part, PriorArgs{a.news_prior, gsel}, AfterArgs{a.after_key, a.after_row});
     return NR_OK;
   });
   if (rc1) return rc1;
   NR_CHECK_LAUNCH(fn);
-  return topk_stage2_launch(fn, a, 1, K, (int)sl.g1.y, part, cnt, uidx, coff, top_idx, top_scores, top_keys);
+  return topk_stage2_launch(fn, a, 1, K, (int)sl.g1.y, part, cnt, uidx, coff, top_idx, top_scores, top_keys, next.key,
+                            next.row);
 }
 
 }  // namespace tk
@@ -477,4 +530,23 @@ extern "C" int nr_topk_users_prior(int dtype, int64_t dim, int64_t U, const floa
                           {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off,
                            {news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask}, stream, news_prior, user_gain},
                           K, top_idx, top_scores, ws, ws_bytes, true, top_keys);
+}
+
+extern "C" int64_t nr_topk_users_after_workspace_bytes(int dtype, int64_t U, int64_t N, int64_t K) {
+  return nr_topk_users_prior_workspace_bytes(dtype, U, N, K);
+}
+
+extern "C" int nr_topk_users_after(int dtype, int64_t dim, int64_t U, const float* users, int64_t N,
+                                   const void* cand_table, int64_t cand_ld, const float* cand_inv_norm,
+                                   const int32_t* excl_idx, const int64_t* excl_off, const int32_t* news_time,
+                                   const int32_t* q_time_lo, const int32_t* q_time_hi, const uint8_t* news_cat,
+                                   const uint64_t* q_cat_mask, const float* news_prior, const float* user_gain,
+                                   const float* after_key, const int32_t* after_row, float* next_key,
+                                   int32_t* next_row, int64_t K, int32_t* top_idx, float* top_scores, float* top_keys,
+                                   void* ws, int64_t ws_bytes, void* stream) {
+  return nr::tk::topk_run("nr_topk_users_after",
+                          {dtype, dim, U, users, N, cand_table, cand_ld, cand_inv_norm, excl_idx, excl_off,
+                           {news_time, q_time_lo, q_time_hi, news_cat, q_cat_mask}, stream, news_prior, user_gain,
+                           after_key, after_row},
+                          K, top_idx, top_scores, ws, ws_bytes, false, top_keys, true, {next_key, next_row});
 }

@@ -158,7 +158,7 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
                               dtype=None, diversify: Optional[float] = None, pool: Optional[int] = None,
                               news_time=None, news_category=None, time_window=None, categories=None,
                               sections=None, prior=None, prior_gain=None, groups=None, group_cap=None,
-                              explain: Optional[int] = None) -> dict:
+                              page: Optional[int] = None, explain: Optional[int] = None) -> dict:
     """The k news of the WHOLE table that the model recommends per impression:
     ``{"news_index": int32 [I, k], "scores": float32 [I, k]}`` on the host, score
     descending, ties by ascending news row, ``(-1, -inf)`` where fewer than k news are
@@ -215,7 +215,24 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     include/newsrec_caps.h): the eligible news are walked best first and one is taken while
     its group holds fewer than c, so a list may end in ``(-1, -inf)`` before k.  Both or
     neither; it composes with the catalogue filters and the prior (the result then has
-    ``"keys"``), and is refused with ``sections``, ``diversify`` and ``explain``."""
+    ``"keys"``), and is refused with ``sections``, ``diversify`` and ``explain``.
+
+    ``page`` = P in 1 .. 64 lifts the limit on k from 64 to 1024 (PoolScoreEngine.recommend_deep,
+    include/newsrec_page.h): the list is fetched in ceil(k / P) cursor calls of P rows, each
+    continuing exactly where the one before ended, and returned ordered by score (by key
+    under a prior) descending, ties by ascending news row.  It composes with the catalogue
+    filters and the prior, and is refused with ``sections``, ``diversify``, ``explain`` and
+    ``group_cap``.  Without ``page`` nothing changes: k > 64 is refused."""
+    if page is not None:
+        if (sections is not None or diversify is not None or explain is not None or pool is not None
+                or group_cap is not None or groups is not None):
+            raise ValueError("get_top_k_recommendations: page cannot be combined with sections, diversify, explain "
+                             "or group_cap")
+        from .engine import check_deep
+        check_deep("get_top_k_recommendations", k, page)
+    elif sections is None and diversify is None and explain is None and pool is None and not 1 <= k <= 64:
+        from . import ops  # the entry's own refusal, ahead of any device work
+        ops.topk_workspace_bytes(torch.float32 if dtype is None else dtype, 1, news_embeddings.shape[0], k)
     if (groups is None) != (group_cap is None):
         raise ValueError("get_top_k_recommendations: groups and group_cap go together")
     if group_cap is not None:
@@ -259,6 +276,11 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     if time_window is not None or categories is not None or prior_gain is not None or group_cap is not None:
         eng.set_catalogue(news_time=news_time, news_cat=news_category, news_prior=prior, news_group=groups)
         flt = {"time_window": time_window, "categories": categories}
+    if page is not None:
+        idx, scores, keys = eng.recommend_deep(int(k), int(page), exclude_history=exclude_history,
+                                               prior_gain=prior_gain, want_keys=True, **flt)
+        res = {"news_index": _host(idx), "scores": _host(scores)}
+        return {**res, "keys": _host(keys)} if prior_gain is not None else res
     if group_cap is not None:
         idx, scores, keys = eng.recommend(k, exclude_history=exclude_history, prior_gain=prior_gain, want_keys=True,
                                           group_cap=int(group_cap), **flt)

@@ -151,13 +151,43 @@ def check_groups(news_group, n_news: Optional[int]) -> np.ndarray:
 
 
 GROUPS_MAX = 1024  # NR_CAP_GROUPS_MAX (include/newsrec_caps.h)
+DEEP_MAX = 1024    # _lib.NR_DEEP_MAX: the longest list recommend_deep pages to
+PAGE_MAX = 64      # _lib.NR_TOPK_MAX: the rows of one cursor call
+
+
+def _no_cursor(what: str, **given) -> None:
+    for name, v in given.items():
+        if v is not None and v is not False:
+            raise ValueError(f"{what}: {name} is recommend's alone (no cursors for sections, per-group caps, MMR or "
+                             "explained lists)")
+
+
+def check_cursor(after, n_imp: int):
+    """recommend's ``after`` as host arrays (key f32 [n_imp], row int32 [n_imp]): the pair a
+    previous call returned (device tensors are read back) or host arrays of the same kind."""
+    if not isinstance(after, (tuple, list)) or len(after) != 2:
+        raise ValueError("after must be the (key, row) pair a previous call returned")
+    key, row = (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in after)
+    if key.shape != (n_imp,) or row.shape != (n_imp,):
+        raise ValueError(f"after must hold one (key, row) per impression ({n_imp})")
+    if not np.issubdtype(key.dtype, np.floating) or not np.issubdtype(row.dtype, np.integer):
+        raise ValueError("after must be (float keys, integer rows)")
+    return np.ascontiguousarray(key, dtype=np.float32), np.ascontiguousarray(row, dtype=np.int32)
+
+
+def check_deep(what: str, k, page) -> None:
+    """The sizes of a paged list: 1 <= k <= DEEP_MAX rows in cursor calls of 1 <= page <= PAGE_MAX."""
+    for name, v, top in (("k", k, DEEP_MAX), ("page", page, PAGE_MAX)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= top:
+            raise ValueError(f"{what}: {name} = {v!r} must be an integer in 1 .. {top}")
 
 
 class _Queries:
-    """The distinct (history, time window, category mask, prior gain) tuples of the loaded
-    impressions under a catalogue filter or a prior: retrieval and ranks run once per query."""
+    """The distinct (history, time window, category mask, prior gain, cursor) tuples of the loaded
+    impressions under a catalogue filter, a prior or a cursor: retrieval and ranks run once per
+    query."""
 
-    def __init__(self, user: np.ndarray, sel: np.ndarray, lo, hi, mask, dev, gain=None):
+    def __init__(self, user: np.ndarray, sel: np.ndarray, lo, hi, mask, dev, gain=None, after=None):
         self.n = len(user)
         self.user_host, self.sel_host = user, sel
         self.user = _upload(user.astype(np.int64), dev)  # the query's pooled user row
@@ -166,6 +196,7 @@ class _Queries:
         self.hi = None if hi is None else _upload(hi, dev)
         self.mask = None if mask is None else _upload(mask, dev)
         self.gain = None if gain is None else _upload(gain, dev)
+        self.after = None if after is None else (_upload(after[0], dev), _upload(after[1], dev))
 
 
 class PoolScoreEngine:
@@ -227,11 +258,12 @@ class PoolScoreEngine:
         self.news_group = None if groups is None else _upload(groups, self.device)
         return self
 
-    def _queries(self, time_window, categories, prior_gain=None) -> Optional[_Queries]:
-        """None without a filter or prior argument (today's paths run), else the distinct
+    def _queries(self, time_window, categories, prior_gain=None, after=None) -> Optional[_Queries]:
+        """None without a filter, prior or cursor argument (today's paths run), else the distinct
         queries.  ``time_window`` = (lo, hi), ``categories`` = a 64-bit mask, ``prior_gain`` = the
-        gain of the set news_prior; each a scalar or one value per impression."""
-        if time_window is None and categories is None and prior_gain is None:
+        gain of the set news_prior; each a scalar or one value per impression.  ``after`` =
+        check_cursor's pair: an impression's cursor is part of its query, as its gain is."""
+        if time_window is None and categories is None and prior_gain is None and after is None:
             return None
         if prior_gain is not None and getattr(self, "news_prior", None) is None:
             raise ValueError("prior_gain needs set_catalogue(news_prior=...)")
@@ -261,16 +293,19 @@ class PoolScoreEngine:
             keys.append(gain.view(np.int32).astype(np.int64))
             if self.news_prior.numel() != self.cand_table.shape[0]:
                 raise ValueError("the catalogue attributes must have one entry per news")
+        if after is not None:  # the bits: NaN keys and -0 stay what they are
+            keys += [after[0].view(np.int32).astype(np.int64), after[1].astype(np.int64)]
         if self.news_time is not None and self.news_time.numel() != self.cand_table.shape[0] or (
                 self.news_cat is not None and self.news_cat.numel() != self.cand_table.shape[0]):
             raise ValueError("the catalogue attributes must have one entry per news")
         if n == 0:
             e = np.zeros(0, np.int64)
-            return _Queries(e, e, lo, hi, mask, self.device, gain)
+            return _Queries(e, e, lo, hi, mask, self.device, gain, after)
         _, first, sel = np.unique(np.stack(keys, axis=1), axis=0, return_index=True, return_inverse=True)
         sel = np.asarray(sel).reshape(-1)
         pick = lambda a: None if a is None else np.ascontiguousarray(a[first])
-        return _Queries(keys[0][first], sel, pick(lo), pick(hi), pick(mask), self.device, pick(gain))
+        return _Queries(keys[0][first], sel, pick(lo), pick(hi), pick(mask), self.device, pick(gain),
+                        None if after is None else (pick(after[0]), pick(after[1])))
 
     def _query_block(self, q: _Queries, users, hidx, hoff, a: int, b: int, exclude_history: bool):
         """Queries [a, b): their pooled rows gathered (f32, so a block bounds them), their
@@ -431,6 +466,8 @@ class PoolScoreEngine:
         appends what the lists are ordered by (the scores themselves without a prior).
         ``group_cap``: at most that many news of one news_group per list (ops.topk_users_capped)."""
         capped = group_cap is not None
+        if not 1 <= k <= PAGE_MAX:  # the entry's own refusal, ahead of the device work
+            ops.topk_workspace_bytes(self.dtype, 1, self.cand_table.shape[0], k)
         if capped:
             if isinstance(group_cap, bool) or not isinstance(group_cap, (int, np.integer)) or not 1 <= group_cap <= 64:
                 raise ValueError(f"group_cap = {group_cap!r} must be an integer in 1 .. 64")
@@ -475,8 +512,70 @@ class PoolScoreEngine:
             return q.sel
         return None if self.user_idx is None else self.user_idx.long()
 
+    def _paged_distinct(self, sizes, exclude_history: bool, user_block: Optional[int], q: Optional[_Queries] = None):
+        """Consecutive pages of ``sizes[p]`` rows (each 1 .. 64) per DISTINCT history, or with ``q``
+        per distinct query, by cursor calls (ops.topk_users_after) that start at the queries'
+        cursors (``q.after``; the start of the list without).  Returns (idx, scores, keys), each
+        [n_rows, sum(sizes)] with the pages side by side, and the cursor behind the last page
+        (key f32 [n_rows], row int32 [n_rows]).  The cursors stay on the device: nothing waits
+        for a page before the next one is enqueued."""
+        self.hist_table = self.transform(out=self.hist_table)
+        self.inv_norms()
+        hidx, hoff = self._distinct_hist()
+        n_rows = hoff.numel() - 1 if q is None else q.n
+        dev = self.device
+        pages = [tuple(torch.empty((n_rows, k), dtype=dt, device=dev)
+                       for dt in (torch.int32, torch.float32, torch.float32)) for k in sizes]
+        if q is not None and q.after is not None:
+            cur = (q.after[0].clone(), q.after[1].clone())
+        else:
+            cur = ops.start_cursor(n_rows, dev)
+        if n_rows:
+            users = self._pooled_users(hidx, hoff)
+            blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
+            need = ops.topk_users_after_workspace_bytes(self.dtype, blk, self.cand_table.shape[0], max(sizes))
+            self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, dev)
+            for a, b, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history):
+                at = (cur[0][a:b], cur[1][a:b])  # read by a call's first kernels, rewritten by its last
+                for p, k in enumerate(sizes):
+                    ops.topk_users_after(rows, self.cand_table, self.cand_inv, k, after=at, next_out=at, excl_idx=eidx,
+                                         excl_off=eoff, out=tuple(t[a:b] for t in pages[p]), workspace=self._topk_ws,
+                                         excl_checked=p > 0, **flt)
+        return tuple(torch.cat([pg[i] for pg in pages], dim=1) if len(pages) > 1 else pages[0][i]
+                     for i in range(3)) + (cur,)
+
+    def recommend_deep(self, k: int, page: int = 64, exclude_history: bool = True, user_block: Optional[int] = None,
+                       time_window=None, categories=None, prior_gain=None, want_keys: bool = False):
+        """recommend past 64 rows: the k best news (1 <= k <= 1024) per impression, fetched in
+        ceil(k / page) cursor calls of ``page`` rows (1 .. 64; the last call asks for the
+        remainder), each continuing where the one before ended (ops.topk_users_after): the
+        pages are consecutive, disjoint slices of the order the retrieval selects in, so together
+        they are the k best rows of that order, and no state grows with the depth.  The
+        concatenated list is then ordered by (key descending, row ascending) -- the key is the
+        score without ``prior_gain`` -- and returned as recommend returns it: (idx int32 [I, k],
+        scores f32 [I, k]) and with ``want_keys`` the keys, (-1, -inf) where fewer than k rows
+        are eligible.  The other arguments are recommend's (``group_cap`` is not taken).  For
+        k <= 64 with page = k it is recommend(k) bit for bit."""
+        check_deep("recommend_deep", k, page)
+        k, page = int(k), int(page)
+        q = self._queries(time_window, categories, prior_gain)
+        sizes = [page] * (k // page) + ([k % page] if k % page else [])
+        idx, scores, keys, _ = self._paged_distinct(sizes, exclude_history, user_block, q)
+        if len(sizes) > 1 and idx.shape[0]:
+            # (key descending, row ascending) by two stable sorts: rows first, then keys
+            by_row = torch.sort(idx, dim=1, stable=True).indices
+            by_key = torch.sort(keys.gather(1, by_row), dim=1, descending=True, stable=True).indices
+            order = by_row.gather(1, by_key)
+            idx, scores, keys = (t.gather(1, order) for t in (idx, scores, keys))
+        out = (idx, scores) + ((keys,) if want_keys else ())
+        sel = self._expansion(q)
+        if sel is not None and idx.shape[0]:
+            return tuple(t[sel] for t in out)
+        return out
+
     def recommend(self, k: int, exclude_history: bool = True, user_block: Optional[int] = None,
-                  time_window=None, categories=None, prior_gain=None, want_keys: bool = False, group_cap=None):
+                  time_window=None, categories=None, prior_gain=None, want_keys: bool = False, group_cap=None,
+                  after=None, want_cursor: bool = False):
         """The k best news of the WHOLE table per impression (ops.topk_users over the
         pooled users): (idx int32 [I, k], scores f32 [I, k]), score descending, ties by
         ascending row, (-1, -inf) where fewer than k rows are eligible; the scores are
@@ -504,7 +603,34 @@ class PoolScoreEngine:
         of one group in a list (ops.topk_users_capped): the eligible news are walked best first
         and one is taken while its group holds fewer than c, until k are taken, so a list may
         be shorter than k.  It composes with every argument above; c >= k changes nothing, and
-        without ``group_cap`` today's paths run."""
+        without ``group_cap`` today's paths run.
+
+        ``after`` = (key f32 [I], row int32 [I]), the pair a previous call returned with
+        ``want_cursor``, continues each impression's list behind that position
+        (ops.topk_users_after): the next k rows of the same ordering, disjoint from every page
+        before.  ``want_cursor`` appends the pair behind this call's last row to the result (the
+        end cursor (-inf, INT32_MAX) where fewer than k rows were left).  A cursor is opaque --
+        selection keys, not scores -- and valid only with the same history, table, dtype and
+        ``prior_gain``; ``time_window`` / ``categories`` / ``exclude_history`` may change between
+        pages.  It is part of the distinct query, as the gain is.  Inside a page the order is by
+        score (by key); across a boundary scores may be out of order by the selection band
+        (include/newsrec_page.h).  ``group_cap`` is refused with either; without both today's
+        paths run."""
+        if after is not None or want_cursor:
+            if group_cap is not None:
+                raise ValueError("recommend: after / want_cursor cannot be combined with group_cap (no cursors under "
+                                 "per-group caps)")
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= PAGE_MAX:
+                raise ValueError(f"recommend: k = {k!r} must be an integer in 1 .. {PAGE_MAX} with a cursor "
+                                 "(recommend_deep pages further)")
+            cur = None if after is None else check_cursor(after, self.n_imp)
+            q = self._queries(time_window, categories, prior_gain, after=cur)
+            idx, scores, keys, nxt = self._paged_distinct([int(k)], exclude_history, user_block, q)
+            sel = self._expansion(q)
+            out = (idx, scores) + ((keys,) if want_keys else ())
+            if sel is not None and idx.shape[0]:
+                out, nxt = tuple(t[sel] for t in out), (nxt[0][sel], nxt[1][sel])
+            return out + ((nxt,) if want_cursor else ())
         q = self._queries(time_window, categories, prior_gain)
         out = self._recommend_distinct(k, exclude_history, user_block, q, want_keys=want_keys, group_cap=group_cap)
         sel = self._expansion(q)
@@ -513,7 +639,7 @@ class PoolScoreEngine:
         return out
 
     def recommend_sections(self, k: int, sections, exclude_history: bool = True, user_block: Optional[int] = None,
-                           time_window=None, prior_gain=None, want_keys: bool = False, group_cap=None):
+                           time_window=None, prior_gain=None, want_keys: bool = False, group_cap=None, after=None):
         """A front page per impression: the k best eligible news of each of S sections, from
         ONE walk over the table (ops.topk_sections): (idx int32 [I, S, k], scores f32
         [I, S, k]).  ``sections`` is a sequence whose items are a 64-bit category mask or an
@@ -525,6 +651,7 @@ class PoolScoreEngine:
         ``want_keys`` are recommend's (ops.topk_sections_prior): section s then equals
         recommend(k, categories=mask_s, prior_gain=...), keys included."""
         _no_cap("recommend_sections", group_cap)
+        _no_cursor("recommend_sections", after=after)
         masks = section_masks(sections)
         k, n_sec = int(k), len(masks)
         if not 1 <= n_sec <= 16 or k < 1 or n_sec * k > 64:
@@ -572,7 +699,7 @@ class PoolScoreEngine:
 
     def recommend_diverse(self, k: int, lam: float, pool: int = 64, exclude_history: bool = True,
                           user_block: Optional[int] = None, want_ild: bool = False, want_plain: bool = False,
-                          time_window=None, categories=None, prior_gain=None, group_cap=None):
+                          time_window=None, categories=None, prior_gain=None, group_cap=None, after=None):
         """recommend's lists re-ranked for diversity (ops.rerank_mmr, greedy MMR): the
         ``pool`` best news per distinct history are retrieved as recommend(pool) does,
         k of them are picked one at a time, each maximising lam * score - (1 - lam) *
@@ -587,6 +714,7 @@ class PoolScoreEngine:
         MMR re-ranks by the scores alone."""
         _no_prior("recommend_diverse", prior_gain)
         _no_cap("recommend_diverse", group_cap)
+        _no_cursor("recommend_diverse", after=after)
         q = self._queries(time_window, categories)
         idx, scores, ild, pscores = self._diverse_distinct(k, lam, pool, exclude_history, user_block, want_ild, q)
         k = int(k)
@@ -660,7 +788,8 @@ class PoolScoreEngine:
 
     def recommend_explained_filtered(self, k: int, time_window=None, categories=None, top: int = 3,
                                      lam: Optional[float] = None, pool: int = 64, exclude_history: bool = True,
-                                     user_block: Optional[int] = None, prior_gain=None, group_cap=None):
+                                     user_block: Optional[int] = None, prior_gain=None, group_cap=None,
+                                     after=None):
         """recommend_explained under recommend's catalogue filters ``time_window`` /
         ``categories``: the filtered lists are expanded to the impressions first and explained
         against each impression's own history.  Without a filter argument it is
@@ -669,6 +798,7 @@ class PoolScoreEngine:
         any lists, recommend's capped ones included."""
         _no_prior("recommend_explained", prior_gain)
         _no_cap("recommend_explained", group_cap)
+        _no_cursor("recommend_explained", after=after)
         q = self._queries(time_window, categories)
         if lam is None:
             idx, scores = self._recommend_distinct(int(k), exclude_history, user_block, q)

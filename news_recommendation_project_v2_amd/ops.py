@@ -229,10 +229,11 @@ def _check_inv_norm(cand_inv_norm: torch.Tensor, n_news: int, contiguous: bool =
 
 
 def _check_scan(what: str, users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor,
-                excl_idx: Optional[torch.Tensor], excl_off: Optional[torch.Tensor]):
+                excl_idx: Optional[torch.Tensor], excl_off: Optional[torch.Tensor], check_rows: bool = True):
     """Host checks of a scan of the whole table (topk_users, rank_targets): returns (n_users,
-    dim, n_news, ld, dt, excl_idx), the exclusion rows range-checked (one small sync) and an
-    empty list replaced by a one-slot dummy."""
+    dim, n_news, ld, dt, excl_idx), the exclusion rows range-checked (one small sync; not
+    without ``check_rows``: a pager's later calls with the lists of its first) and an empty
+    list replaced by a one-slot dummy."""
     if users.dtype != torch.float32 or users.dim() != 2 or not users.is_contiguous():
         raise _lib.NewsRecHIPError(f"{what}: users must be contiguous f32 [U, D]")
     n_users, dim = users.shape
@@ -247,11 +248,11 @@ def _check_scan(what: str, users: torch.Tensor, cand_table: torch.Tensor, cand_i
         _check_csr(excl_idx, excl_off, "excl")
         if excl_off.numel() != n_users + 1:
             raise _lib.NewsRecHIPError(f"{what}: excl_off must have U + 1 entries")
-        if excl_idx.numel():
+        if excl_idx.numel() and check_rows:
             lo, hi = (int(v) for v in torch.aminmax(excl_idx))
             if lo < 0 or hi >= n_news:
                 raise IndexError(f"{what}: excluded row {lo if lo < 0 else hi} is outside the {n_news} table rows")
-        else:  # no storage behind an empty tensor; the kernel never reads it
+        elif not excl_idx.numel():  # no storage behind an empty tensor; the kernel never reads it
             excl_idx = torch.zeros(1, dtype=torch.int32, device=users.device)
     return n_users, dim, n_news, ld, _dtype(cand_table, "cand_table"), excl_idx
 
@@ -484,6 +485,76 @@ def topk_users_prior(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_nor
     return topk_users(users, cand_table, cand_inv_norm, k, excl_idx=excl_idx, excl_off=excl_off, out=out,
                       workspace=workspace, _filter=(news_time, time_lo, time_hi, news_cat, cat_mask),
                       _prior=(news_prior, user_gain))
+
+
+def topk_users_after_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) -> int:
+    """nr_topk_users_after_workspace_bytes (include/newsrec_page.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_topk_users_after_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, k))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"topk_users_after: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, k = {k}; "
+            f"k in [1, {_lib.NR_TOPK_MAX}], N <= 2^22)")
+    return need
+
+
+def start_cursor(n: int, device):
+    """The cursor in front of the first row of ``n`` users' lists: (key f32 [n] = +inf,
+    row int32 [n] = -1).  topk_users_after from it is topk_users_after without a cursor."""
+    return (torch.full((n,), float("inf"), dtype=torch.float32, device=device),
+            torch.full((n,), -1, dtype=torch.int32, device=device))
+
+
+def _check_cursor(what: str, name: str, n_users: int, cursor) -> list:
+    """A cursor pair (key f32 [U], row int32 [U]) as the two pointers of the C call."""
+    if cursor is None:
+        return [None, None]
+    if (not isinstance(cursor, (tuple, list)) or len(cursor) != 2
+            or any(not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or t.numel() != n_users
+                   or not t.is_contiguous() for t, dt in zip(cursor, (torch.float32, torch.int32)))):
+        raise _lib.NewsRecHIPError(f"{what}: {name} must be (key contiguous {torch.float32} [{n_users}], "
+                                   f"row contiguous {torch.int32} [{n_users}])")
+    return [_ptr(cursor[0]), _ptr(cursor[1])]
+
+
+def topk_users_after(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int,
+                     after=None, want_next: bool = True, excl_idx: Optional[torch.Tensor] = None,
+                     excl_off: Optional[torch.Tensor] = None, news_time: Optional[torch.Tensor] = None,
+                     time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
+                     news_cat: Optional[torch.Tensor] = None, cat_mask: Optional[torch.Tensor] = None,
+                     news_prior: Optional[torch.Tensor] = None, user_gain: Optional[torch.Tensor] = None, out=None,
+                     workspace: Optional[torch.Tensor] = None, next_out=None, excl_checked: bool = False):
+    """topk_users_prior behind a cursor (nr_topk_users_after): the k best eligible rows that lie
+    strictly after ``after`` = (key f32 [U], row int32 [U]) in the order the retrieval selects in
+    (selection key descending, row ascending).  Returns (idx, scores, keys, next): the first
+    three as topk_users_prior returns them (keys == scores without a prior), ``next`` the cursor
+    behind the call's last row -- feed it back for the next k rows -- or the end cursor
+    (-inf, INT32_MAX) where fewer than k rows were left; None without ``want_next``.  Pages
+    are consecutive, disjoint slices of one ordering; inside a page the order is by score (by
+    key under a prior).  A cursor is opaque: selection keys, valid only with the same user
+    row, table, dtype, prior and gain; exclusion lists and filters may change between pages.
+    ``after`` = None (or start_cursor) starts the list.  ``out`` = (idx, scores, keys) and
+    ``next_out`` = (key, row) to write into; ``next_out`` may be ``after`` itself.
+    ``excl_checked`` promises that an earlier call range-checked these exclusion lists, and
+    saves their sync: a walk over several pages then never waits for the device."""
+    what = "topk_users_after"
+    dev = _dev(users, cand_table, cand_inv_norm, news_prior, user_gain, news_time, time_lo, time_hi, news_cat,
+               cat_mask, excl_idx, excl_off, workspace, *(out or ()), *(after or ()), *(next_out or ()))
+    n_users, dim, n_news, ld, dt, excl_idx = _check_scan(what, users, cand_table, cand_inv_norm, excl_idx, excl_off,
+                                                         check_rows=not excl_checked)
+    k = int(k)
+    pptr = _check_prior(what, n_users, n_news, news_prior, user_gain)
+    fptr = _check_filter(what, n_users, n_news, news_time, time_lo, time_hi, news_cat, cat_mask)
+    aptr = _check_cursor(what, "after", n_users, after)
+    nxt = next_out
+    if nxt is None and want_next:
+        nxt = (torch.empty(n_users, dtype=torch.float32, device=dev), torch.empty(n_users, dtype=torch.int32, device=dev))
+    nptr = _check_cursor(what, "next_out", n_users, nxt)
+    ws = grow_workspace(workspace, topk_users_after_workspace_bytes(cand_table.dtype, n_users, n_news, k), dev)
+    idx, scores, keys = _keyed_outputs(what, out, (n_users, k), dev)
+    _lib.call("nr_topk_users_after", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
+              _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, *pptr, *aptr, *nptr, k, _ptr(idx),
+              _ptr(scores), _ptr(keys), _ptr(ws), ws.numel(), _stream(dev))
+    return idx, scores, keys, (None if nxt is None else tuple(nxt))
 
 
 def topk_users_capped_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) -> int:

@@ -11,6 +11,7 @@ has no counterpart -- it only scores the candidates an impression lists).
     python scripts/recommend.py --synthetic --evaluate --as-of [--fresh 48] [--categories 0,3,7]
     python scripts/recommend.py --synthetic --sections "0,1;2;3,4,5" -k 4 [--as-of [--fresh 24]]
     python scripts/recommend.py --synthetic --prior popularity --prior-gain 0.2 [--prior-cold 1] [--evaluate]
+    python scripts/recommend.py --synthetic -k 256 --page 64
 
 Prints one JSON line per run and writes {out-dir}/recommendations.npy: an int32
 [I, K] array of rows of the split's news list (-1 where fewer than K are eligible).
@@ -64,6 +65,11 @@ per row of the news list (at most 1024 distinct ones).  The JSON line gains cap,
 evaluation.group_cap_metrics of the lists: max_group_count (<= C), at_cap_share and
 distinct_groups.  It composes with --as-of, --fresh, --categories and --prior*, and is refused
 with --sections, --diversify, --explain and --evaluate.
+--page P (1 .. 64) allows -k up to 1024 (include/newsrec_page.h): the list is fetched in
+ceil(K / P) cursor calls of P news, each continuing exactly where the one before ended, and
+ordered by score (by key under --prior) before it is written.  The JSON line gains page.  It
+composes with --as-of, --fresh, --categories, --prior* and --evaluate (whose --ks are ranks and
+never were bounded by 64), and is refused with --sections, --diversify, --explain and --cap.
 """
 from __future__ import annotations
 
@@ -236,7 +242,18 @@ def main():
     ap.add_argument("--cap", type=int, default=None, metavar="C", help="at most C news of one group in a list (1..64)")
     ap.add_argument("--cap-by", default=None, metavar="category|FILE.npy",
                     help="with --cap: the groups, the news' categories (default) or one label per row of the news list")
+    ap.add_argument("--page", type=int, default=None, metavar="P",
+                    help="fetch the list in cursor calls of P news (1..64): -k may then go up to 1024")
     args = ap.parse_args()
+    if args.page is not None:
+        if not 1 <= args.page <= 64:
+            ap.error("--page must be in 1 .. 64")
+        if not 1 <= args.k <= 1024:
+            ap.error("-k must be in 1 .. 1024 with --page")
+        for flag, on in (("--sections", args.sections is not None), ("--diversify", args.diversify is not None),
+                         ("--explain", args.explain is not None), ("--cap", args.cap is not None)):
+            if on:
+                ap.error(f"--page cannot be combined with {flag}")
     if args.cap_by is not None and args.cap is None:
         ap.error("--cap-by needs --cap")
     if args.cap is not None:
@@ -298,7 +315,8 @@ def main():
                                         dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
                                         **({} if args.diversify is None else
                                            {"diversify": args.diversify, "pool": args.pool}),
-                                        **({} if args.explain is None else {"explain": args.explain}), **flt, **pri, **caps)
+                                        **({} if args.explain is None else {"explain": args.explain}),
+                                        **({} if args.page is None else {"page": args.page}), **flt, **pri, **caps)
     ms = (time.perf_counter() - t0) * 1e3
     idx, scores = rec["news_index"], rec["scores"]
     args.out_dir.mkdir(parents=True, exist_ok=True)
@@ -310,6 +328,8 @@ def main():
             "news": int(out["news_embeddings"].shape[0]), "filled": float(have.mean()) if idx.size else 1.0,
             "mean_top1_score": float(scores[..., 0][have[..., 0]].mean()) if have[..., :1].any() else None,
             "ms": round(ms, 1), "out": str(path)}
+    if args.page is not None:
+        line["page"] = args.page
     if args.sections is not None:
         names = [sec.strip() for sec in args.sections.split(";")]
         sec_path = args.out_dir / "recommendations_sections.npz"
