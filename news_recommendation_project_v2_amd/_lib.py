@@ -25,7 +25,7 @@ HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CS
                INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
                INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h",
                INCLUDE / "newsrec_filter.h", INCLUDE / "newsrec_sections.h", INCLUDE / "newsrec_prior.h",
-               INCLUDE / "newsrec_caps.h", INCLUDE / "newsrec_page.h")
+               INCLUDE / "newsrec_caps.h", INCLUDE / "newsrec_page.h", INCLUDE / "newsrec_sliced.h")
 
 
 def hip_source_files() -> list:
@@ -206,6 +206,13 @@ PRIOR_SIGNATURES = {
                                     _p, _p, _p, _l, _p]),
 }
 
+# column-sliced pool+score (include/newsrec_sliced.h), bound by load() like SIGNATURES
+SLICED_SIGNATURES = {
+    "nr_slice_table": (_i, [_i, _l, _i, _i, _p, _l, _p, _i, _p]),
+    "nr_pool_score_sliced_workspace_bytes": (_l, [_i, _l, _l]),
+    "nr_pool_score_sliced": (_i, [_i, _i, _l, _i, _p, _l, _p, _l, _p, _p, _p, _p, _p, _l, _l, _p, _p, _l, _p]),
+}
+
 # per-group caps of retrieval (include/newsrec_caps.h), bound by load() like SIGNATURES:
 # nr_topk_users_prior's arguments with news_group and cap behind user_gain
 NR_CAP_GROUPS_MAX = 1024
@@ -284,7 +291,7 @@ def load() -> ctypes.CDLL:
     for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES,
                               **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES,
                               **FILTER_SIGNATURES, **SECTIONS_SIGNATURES, **PRIOR_SIGNATURES,
-                              **CAPS_SIGNATURES, **PAGE_SIGNATURES}.items():
+                              **CAPS_SIGNATURES, **PAGE_SIGNATURES, **SLICED_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

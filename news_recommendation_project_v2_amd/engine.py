@@ -28,6 +28,35 @@ from .data_utils import distinct_segments, lengths_to_offsets
 # and +4 KiB read per user row): break-even ~ 2 x 4 KiB / (33 x 2 KiB) ~ 0.12
 DEDUPE_MIN_SHARE = 0.15
 
+# The column-sliced pool+score (ops.pool_score(sliced=...)) gathers the same rows from slice
+# images whose L2 share is 1024 / W times today's, and pays for it with f32 user rows and
+# per-slice partial dots written and read once, the index arrays re-read per slice and the
+# history table's image rebuilt every step.  Measured on bf16 tables (DESIGN.md §3.1,
+# profiles/sliced), stage time against today's kernel on the same machine:
+#   MIND-large-dev (147 MB table), latent: W = 128 6.82 ms, W = 64 7.08 ms, today 7.17 ms
+#   MIND-large-dev, FinalAttention       : W = 128 10.04 ms, W = 64 9.37 ms, today 10.57 ms
+#   MIND-small-dev (87 MB table), latent : W = 128 1.375 ms, W = 64 1.47 ms, today 1.405 ms
+# W = 64 hits L2 more often (47 % against 34 %; 2.7 % today) but its launches run out of
+# instruction issue on 128-byte rows; FinalAttention's image rows are twice as wide, so there
+# it wins.  The smaller table's 2 % is within what another impression mix could undo, so the
+# rule switches bf16 tables of at least SLICED_MIN_TABLE_BYTES (one [N, 1024] table) and
+# leaves everything else -- f32 tables, which were not measured, included -- on today's
+# kernel.  A width of 0 turns the path off for that pooler.
+SLICED_W = 128        # latent and mean poolers
+SLICED_W_FINAL = 64   # FinalAttention
+SLICED_MIN_TABLE_BYTES = 128 << 20
+
+
+def sliced_width(n_news: int, dtype: torch.dtype, want_users: bool, deduped: bool, pooler: str = "latent") -> int:
+    """The slice width pool_score runs at (0: today's kernels): ``want_users`` and the
+    deduplicated-history path stay on today's kernels, and so does every table under
+    SLICED_MIN_TABLE_BYTES, which a single slice image of W columns no longer misses L2 for
+    often enough to pay for the extra passes."""
+    w = SLICED_W_FINAL if pooler == "final" else SLICED_W
+    if not w or want_users or deduped or dtype != torch.bfloat16:
+        return 0
+    return w if n_news * 1024 * 2 >= SLICED_MIN_TABLE_BYTES else 0
+
 
 def _may_repeat(hist_idx: np.ndarray, hist_len: np.ndarray) -> bool:
     """Cheap bound before the exact grouping: repeated histories share (length,
@@ -213,6 +242,8 @@ class PoolScoreEngine:
         self.hist_table = None
         self._ws = None
         self._users = None  # f32 [distinct histories, D], reused across steps
+        self._cand_image = self._hist_image = self._sliced_ws = None  # the sliced path's buffers, reused
+        self._cand_image_of = None
         self.news_time = None  # int32 [N] / uint8 [N] / f32 [N]: set_catalogue
         self.news_cat = None
         self.news_prior = None
@@ -227,7 +258,21 @@ class PoolScoreEngine:
         else:
             self.hist_src = self.cand_table
         self._check_rows()
+        self._cand_image = None
+        w = sliced_width(self.cand_table.shape[0], self.dtype, False, False, getattr(self, "pooler", "latent"))
+        if w:  # a layout of the loaded table, like its dtype conversion
+            self._candidate_image(w)
         return self
+
+    def _candidate_image(self, w: int) -> torch.Tensor:
+        """The candidate table's slice image of width ``w``, built once per loaded table (and
+        again should the table have been replaced or written to since)."""
+        t = self.cand_table
+        key = (w, t.data_ptr(), tuple(t.shape), t._version)
+        if getattr(self, "_cand_image", None) is None or self._cand_image_of != key:
+            self._cand_image = ops.slice_table(t, w)
+            self._cand_image_of = key
+        return self._cand_image
 
     def set_catalogue(self, news_time=None, news_cat=None, news_prior=None, news_group=None):
         """Per-news attributes for the catalogue filters of recommend, recommend_diverse,
@@ -367,7 +412,10 @@ class PoolScoreEngine:
         each DISTINCT history once (MIND repeats a user's history on every
         impression of that user) and scores the candidates against the stored
         user rows: same scores bit for bit, fewer gathered bytes once at least
-        DEDUPE_MIN_SHARE of the impressions repeat a history."""
+        DEDUPE_MIN_SHARE of the impressions repeat a history.  ``dedupe=False`` asks for the
+        fused per-impression pass those bits are defined by (pool_score_kernel), so it also keeps
+        pool_score off the column-sliced path, whose scores differ by f32 reassociation; the
+        automatic mode is free to take it (sliced_width) when the histories are not deduplicated."""
         dev = self.device
         if len(hist_len) != len(cand_len):
             raise ValueError("Number of rows should be consistent")  # data_model_helper.py:183-185
@@ -395,6 +443,7 @@ class PoolScoreEngine:
         self.n_cand = int(cand_len_a.sum())
         self.n_imp = len(cand_len)
         self.user_idx = None
+        self._fused_asked = dedupe is False
         self.shared_history_share = 0.0
         if dedupe is not False and self.n_imp and (dedupe or _may_repeat(hist_idx, hist_len)):
             group, first = distinct_segments(hist_idx, hist_len)
@@ -443,14 +492,36 @@ class PoolScoreEngine:
                                  f"for dimension 0 with size {table.shape[0]}")
 
     def pool_score(self, want_users: bool = False, scores: Optional[torch.Tensor] = None):
+        """(scores [C] f32, users [I, D] f32 or None) of the loaded impressions.  Deduplicated
+        histories and ``want_users`` run today's kernels; otherwise sliced_width decides between
+        today's fused kernel and the column-sliced path on the tables' slice images, whose scores
+        differ from the fused kernel's by f32 reassociation only; load_impressions(dedupe=False)
+        keeps the fused kernel.  Images and workspace are allocated once and reused across steps."""
         if self.user_idx is not None:  # distinct histories pooled once, then scored per impression
             users = self._pooled_users(self.uhist_idx, self.uhist_off)
             s = ops.score_users(users, self.user_idx, self.cand_table, self.cand_inv, self.cand_idx, self.cand_off,
                                 self.n_cand, scores=scores)
             return s, (users[self.user_idx.long()] if want_users else None)
+        w = 0 if getattr(self, "_fused_asked", False) else sliced_width(self.cand_table.shape[0], self.dtype,
+                                                                          want_users, False, self.pooler)
+        if not w:
+            return ops.pool_score(self.pooler, self.hist_table, self.cand_table, self.cand_inv, self.hist_idx,
+                                  self.hist_off, self.cand_idx, self.cand_off, self.n_cand, want_users=want_users,
+                                  scores=scores)
+        # the transformed table changes every step, so its image is rebuilt here (into the
+        # same buffer); hist_table itself stays row-major for every other reader
+        parts = 2 if self.pooler == "final" else 1
+        shape = (1024 // w, self.hist_table.shape[0], parts * w)
+        img = getattr(self, "_hist_image", None)
+        if img is not None and (tuple(img.shape) != shape or img.dtype != self.hist_table.dtype):
+            img = None
+        self._hist_image = ops.slice_table(self.hist_table, w, parts, out=img)
+        self._sliced_ws = ops.grow_workspace(
+            getattr(self, "_sliced_ws", None), max(ops.pool_score_sliced_workspace_bytes(w, self.n_imp, self.n_cand), 256), self.device)
         return ops.pool_score(self.pooler, self.hist_table, self.cand_table, self.cand_inv, self.hist_idx,
-                              self.hist_off, self.cand_idx, self.cand_off, self.n_cand, want_users=want_users,
-                              scores=scores)
+                              self.hist_off, self.cand_idx, self.cand_off, self.n_cand, scores=scores, sliced=w,
+                              hist_image=self._hist_image, cand_image=self._candidate_image(w),
+                              workspace=self._sliced_ws)
 
     def step(self, want_users: bool = False, scores: Optional[torch.Tensor] = None):
         """Full eval pass: transform + inverse norms + pool/score."""
@@ -579,7 +650,9 @@ class PoolScoreEngine:
         """The k best news of the WHOLE table per impression (ops.topk_users over the
         pooled users): (idx int32 [I, k], scores f32 [I, k]), score descending, ties by
         ascending row, (-1, -inf) where fewer than k rows are eligible; the scores are
-        pool_score's for that (impression, news) pair bit for bit.  ``exclude_history``
+        pool_score's for that (impression, news) pair bit for bit (today's kernel's,
+        ops.pool_score(sliced=False): the column-sliced path that pool_score takes on large
+        bf16 tables sums the dot per slice and differs by f32 reassociation).  ``exclude_history``
         leaves an impression's own history out of its list.  Distinct histories are
         pooled and searched once (the deduplicated CSR when load_impressions built it).
         ``user_block`` bounds the workspace by running the users in blocks of that many
@@ -753,7 +826,8 @@ class PoolScoreEngine:
         positions within the impression's history of the ``top`` clicks that contributed
         most to each listed news' score and their contributions (-1, -inf past the
         history's length or for a pad); with ``want_sum`` also f32 [I, K], every click's
-        contributions added up (pool_score's score of the pair); with ``want_matrix`` also
+        contributions added up (pool_score's score of the pair, up to the f32 order of the
+        sums: of today's kernel and of the column-sliced path alike); with ``want_matrix`` also
         f32 [len(hist_idx), K], all of them.  The pooler table and the inverse norms are
         computed when a step has not left them.  ``prior_gain`` is refused: a prior is no click's
         contribution."""

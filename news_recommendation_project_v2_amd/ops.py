@@ -278,14 +278,98 @@ def _outputs(what: str, spec, out, dev, real_slots: bool = False):
     return out, res
 
 
+SLICE_WIDTHS = (64, 128)  # the column-slice widths nr_pool_score_sliced is built for
+SLICE_W = 128             # the width ``sliced=True`` means (the engine's: engine.SLICED_W)
+
+
+def slice_width(sliced) -> int:
+    """``sliced`` of pool_score as a slice width: 0 for today's kernel (False / None / 0),
+    SLICE_W for True, else one of SLICE_WIDTHS."""
+    if sliced is None or sliced is False or (not isinstance(sliced, bool) and sliced == 0):
+        return 0
+    w = SLICE_W if sliced is True else int(sliced)
+    if w not in SLICE_WIDTHS:
+        raise _lib.NewsRecHIPError(f"sliced must be a bool or a slice width of {SLICE_WIDTHS}, got {sliced!r}")
+    return w
+
+
+def slice_table(table: torch.Tensor, slice_w: int, parts: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Slice-major image [1024 / slice_w, N, parts * slice_w] of a row-major [N, parts * 1024]
+    table (nr_slice_table): slice s of row r holds columns s * slice_w .. of each part.  A
+    bit-exact permutation, into ``out`` when given."""
+    dev = _dev(table, out)
+    if slice_w not in SLICE_WIDTHS or parts not in (1, 2):
+        raise _lib.NewsRecHIPError(f"slice_table: slice_w of {SLICE_WIDTHS}, parts 1 or 2")
+    ld = _rowmajor(table, "table")
+    n = table.shape[0]
+    if table.shape[1] != parts * 1024:
+        raise _lib.NewsRecHIPError(f"slice_table: table must be [N, {parts * 1024}]")
+    shape = (1024 // slice_w, n, parts * slice_w)
+    if out is None:
+        out = torch.empty(shape, dtype=table.dtype, device=dev)
+    if out.dtype != table.dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise _lib.NewsRecHIPError(f"slice_table: out must be contiguous {table.dtype} of shape {shape}")
+    if n:
+        _lib.call("nr_slice_table", _dtype(table, "table"), n, parts, slice_w, _ptr(table), ld, _ptr(out), 0,
+                  _stream(dev))
+    return out
+
+
+def unslice_table(image: torch.Tensor, parts: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The row-major [N, parts * 1024] table of a slice_table image (the inverse permutation)."""
+    dev = _dev(image, out)
+    if image.dim() != 3 or not image.is_contiguous() or parts not in (1, 2) or image.shape[2] % parts:
+        raise _lib.NewsRecHIPError("unslice_table: image must be a contiguous [S, N, parts * slice_w] tensor")
+    s, n, pw = image.shape
+    slice_w = pw // parts
+    if slice_w not in SLICE_WIDTHS or s * slice_w != 1024:
+        raise _lib.NewsRecHIPError(f"unslice_table: not an image of slice width {SLICE_WIDTHS}")
+    if out is None:
+        out = torch.empty((n, parts * 1024), dtype=image.dtype, device=dev)
+    if out.dtype != image.dtype or tuple(out.shape) != (n, parts * 1024):
+        raise _lib.NewsRecHIPError(f"unslice_table: out must be {image.dtype} of shape {(n, parts * 1024)}")
+    if n:
+        _lib.call("nr_slice_table", _dtype(image, "image"), n, parts, slice_w, _ptr(image), _rowmajor(out, "out"),
+                  _ptr(out), 1, _stream(dev))
+    return out
+
+
+def pool_score_sliced_workspace_bytes(slice_w: int, n_imp: int, n_cand: int) -> int:
+    """nr_pool_score_sliced_workspace_bytes; raises on arguments the entry refuses."""
+    need = int(_lib.load().nr_pool_score_sliced_workspace_bytes(slice_w, n_imp, n_cand))
+    if need < 0:
+        raise _lib.NewsRecHIPError(_lib.load().nr_last_error().decode() or "nr_pool_score_sliced_workspace_bytes")
+    return need
+
+
+def _check_image(image: torch.Tensor, table: torch.Tensor, slice_w: int, parts: int, name: str) -> None:
+    shape = (1024 // slice_w, table.shape[0], parts * slice_w)
+    if image.dtype != table.dtype or tuple(image.shape) != shape or not image.is_contiguous():
+        raise _lib.NewsRecHIPError(f"{name} must be the contiguous {table.dtype} slice_table image of shape {shape}")
+
+
 def pool_score(pooler: str, hist_table: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor,
                hist_idx: torch.Tensor, hist_off: torch.Tensor, cand_idx: torch.Tensor, cand_off: torch.Tensor,
-               n_cand: int, want_users: bool = False, scores: Optional[torch.Tensor] = None):
+               n_cand: int, want_users: bool = False, scores: Optional[torch.Tensor] = None, sliced=False,
+               hist_image: Optional[torch.Tensor] = None, cand_image: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None):
     """Fused history pooling + cosine scoring; returns (scores[C] f32, users[I, D] f32 or None).
 
     ``n_cand`` = cand_off[-1] (passed by the caller so no device sync is needed).
+
+    ``sliced`` (False: today's kernel; True: slice width SLICE_W; 64 or 128: that width)
+    runs nr_pool_score_sliced on the tables' slice images instead, at any size: the same
+    scores up to f32 reassociation (the dot is summed per slice), and not the bits that
+    recommend, explain and the rest restate -- those are today's kernel's.  ``hist_image`` /
+    ``cand_image`` are slice_table images of the two tables a caller keeps (built here when
+    absent), ``workspace`` a uint8 buffer of pool_score_sliced_workspace_bytes.  No
+    ``want_users`` on this path.
     """
-    dev = _dev(hist_table, cand_table, cand_inv_norm, hist_idx, hist_off, cand_idx, cand_off, scores)
+    dev = _dev(hist_table, cand_table, cand_inv_norm, hist_idx, hist_off, cand_idx, cand_off, scores, hist_image,
+               cand_image, workspace)
+    slice_w = slice_width(sliced)
+    if slice_w and want_users:
+        raise _lib.NewsRecHIPError("pool_score: the sliced path has no users output (sliced=False)")
     _check_csr(hist_idx, hist_off, "hist")
     _check_csr(cand_idx, cand_off, "cand")
     if hist_off.numel() != cand_off.numel():
@@ -308,6 +392,26 @@ def pool_score(pooler: str, hist_table: torch.Tensor, cand_table: torch.Tensor, 
         scores = torch.empty(n_cand, dtype=torch.float32, device=dev)
     # zero-element tensors report data_ptr() == 0: give the kernel a real (unread) slot
     scores_buf = scores if scores.numel() > 0 else torch.empty(1, dtype=torch.float32, device=dev)
+    if slice_w:
+        if n_imp == 0:
+            return scores, None
+        parts = 2 if pooler == "final" else 1
+        if hist_table.dim() != 2 or hist_table.shape[1] != parts * 1024 or tuple(cand_table.shape[1:]) != (1024,):
+            raise _lib.NewsRecHIPError(f"pool_score: the sliced path needs a [N, {parts * 1024}] history table and a "
+                                       "[N, 1024] candidate table")
+        if hist_image is None:
+            hist_image = slice_table(hist_table, slice_w, parts)
+        if cand_image is None:
+            cand_image = slice_table(cand_table, slice_w)
+        _check_image(hist_image, hist_table, slice_w, parts, "hist_image")
+        _check_image(cand_image, cand_table, slice_w, 1, "cand_image")
+        need = max(pool_score_sliced_workspace_bytes(slice_w, n_imp, n_cand), 256)
+        ws = grow_workspace(workspace, need, dev)
+        _lib.call("nr_pool_score_sliced", POOLERS[pooler], _dtype(cand_table, "cand_table"), dim, slice_w,
+                  _ptr(hist_image), hist_table.shape[0], _ptr(cand_image), cand_table.shape[0], _ptr(cand_inv_norm),
+                  _ptr(hist_idx), _ptr(hist_off), _ptr(cand_idx), _ptr(cand_off), n_imp, n_cand, _ptr(scores_buf),
+                  _ptr(ws), ws.numel(), _stream(dev))
+        return scores, None
     users = torch.empty((n_imp, dim), dtype=torch.float32, device=dev) if want_users else None
     _lib.call("nr_pool_score", POOLERS[pooler], _dtype(cand_table, "cand_table"), dim, _ptr(hist_table),
               _rowmajor(hist_table, "hist_table"), _ptr(cand_table), _rowmajor(cand_table, "cand_table"),
