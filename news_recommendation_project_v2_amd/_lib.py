@@ -19,13 +19,13 @@ INCLUDE = Path(__file__).resolve().parent.parent / "include"
 # translation units of libnewsrec_hip.so, in link order (also the hash order)
 HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip", "encoder.hip", "train.hip",
                "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip", "contrastive.hip", "topk.hip",
-               "fullrank.hip", "rerank.hip", "explain.hip", "sections.hip", "caps.hip")
+               "fullrank.hip", "rerank.hip", "explain.hip", "sections.hip", "caps.hip", "deep.hip")
 # the headers they include (every object is rebuilt when one changes), hashed after the sources
 HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CSRC / "nr_score_tile.h",
                INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
                INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h",
                INCLUDE / "newsrec_filter.h", INCLUDE / "newsrec_sections.h", INCLUDE / "newsrec_prior.h",
-               INCLUDE / "newsrec_caps.h", INCLUDE / "newsrec_page.h", INCLUDE / "newsrec_sliced.h")
+               INCLUDE / "newsrec_caps.h", INCLUDE / "newsrec_page.h", INCLUDE / "newsrec_sliced.h", INCLUDE / "newsrec_deep.h")
 
 
 def hip_source_files() -> list:
@@ -231,6 +231,13 @@ PAGE_SIGNATURES = {
                                  _l, _p, _p, _p, _p, _l, _p]),
 }
 
+# deep retrieval (include/newsrec_deep.h), bound by load() like SIGNATURES: nr_topk_users_after's
+# arguments, K up to NR_TOPK_DEEP_MAX from one walk over the table
+NR_TOPK_DEEP_MAX = 256
+DEEP_SIGNATURES = {
+    "nr_topk_users_deep_workspace_bytes": PAGE_SIGNATURES["nr_topk_users_after_workspace_bytes"],
+    "nr_topk_users_deep": PAGE_SIGNATURES["nr_topk_users_after"],
+}
 
 
 class ContrastiveSpec(ctypes.Structure):
@@ -291,7 +298,8 @@ def load() -> ctypes.CDLL:
     for name, (res, args) in {**SIGNATURES, **CONTRASTIVE_SIGNATURES, **TOPK_SIGNATURES,
                               **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES,
                               **FILTER_SIGNATURES, **SECTIONS_SIGNATURES, **PRIOR_SIGNATURES,
-                              **CAPS_SIGNATURES, **PAGE_SIGNATURES, **SLICED_SIGNATURES}.items():
+                              **CAPS_SIGNATURES, **PAGE_SIGNATURES, **SLICED_SIGNATURES,
+                              **DEEP_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

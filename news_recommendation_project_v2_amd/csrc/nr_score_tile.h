@@ -86,6 +86,13 @@ struct PriorArgs {
   const float* gsel = nullptr;
 };
 
+// The cursor as the stage-1 kernels with one take it (include/newsrec_page.h): [U] and [U].  The
+// AFTER = false instantiations never read it.
+struct AfterArgs {
+  const float* key = nullptr;
+  const int32_t* row = nullptr;
+};
+
 template <typename TI, bool PRIOR = false>
 struct ScoreTile {
   static constexpr int BK = 128 / (int)sizeof(TI);

@@ -91,10 +91,6 @@ int prior_gains_launch(int64_t U, const float* users, const float* gain, float* 
 // of the filter, so the rows above the cursor never reach the serial drain, and the drain
 // settles the tie on the row.  Both threads of a user hold its cursor in two registers; no LDS.
 // The instantiations without a cursor hold none of it.
-struct AfterArgs {
-  const float* key = nullptr;
-  const int32_t* row = nullptr;
-};
 template <typename TI, bool FILT, bool PRIOR, bool AFTER>
 __global__ __launch_bounds__(256) void topk_stage1_kernel(int64_t U, int64_t N, const TI* __restrict__ users,
                                                           const TI* __restrict__ tab, int64_t ldt,

@@ -158,7 +158,8 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
                               dtype=None, diversify: Optional[float] = None, pool: Optional[int] = None,
                               news_time=None, news_category=None, time_window=None, categories=None,
                               sections=None, prior=None, prior_gain=None, groups=None, group_cap=None,
-                              page: Optional[int] = None, explain: Optional[int] = None) -> dict:
+                              page: Optional[int] = None, walk: Optional[int] = None,
+                              explain: Optional[int] = None) -> dict:
     """The k news of the WHOLE table that the model recommends per impression:
     ``{"news_index": int32 [I, k], "scores": float32 [I, k]}`` on the host, score
     descending, ties by ascending news row, ``(-1, -inf)`` where fewer than k news are
@@ -222,8 +223,23 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     continuing exactly where the one before ended, and returned ordered by score (by key
     under a prior) descending, ties by ascending news row.  It composes with the catalogue
     filters and the prior, and is refused with ``sections``, ``diversify``, ``explain`` and
-    ``group_cap``.  Without ``page`` nothing changes: k > 64 is refused."""
-    if page is not None:
+    ``group_cap``.  Without ``page`` nothing changes: k > 64 is refused.
+
+    ``walk`` = W in 1 .. 256 lifts the limit on k to 1024 as ``page`` does, and returns the same
+    lists bit for bit (PoolScoreEngine.recommend_deep(walk=W), include/newsrec_deep.h): the list
+    is fetched in ceil(k / W) chained calls of W rows that each need one walk over the table,
+    where a page of 64 needs one per 64 rows.  ``walk`` and ``page`` are mutually exclusive, and
+    ``walk`` is refused with ``sections``, ``diversify``, ``explain`` and ``group_cap``."""
+    if walk is not None:
+        if page is not None:
+            raise ValueError("get_top_k_recommendations: walk and page are mutually exclusive")
+        if (sections is not None or diversify is not None or explain is not None or pool is not None
+                or group_cap is not None or groups is not None):
+            raise ValueError("get_top_k_recommendations: walk cannot be combined with sections, diversify, explain "
+                             "or group_cap")
+        from .engine import PAGE_MAX, check_deep
+        check_deep("get_top_k_recommendations", k, PAGE_MAX, walk)
+    elif page is not None:
         if (sections is not None or diversify is not None or explain is not None or pool is not None
                 or group_cap is not None or groups is not None):
             raise ValueError("get_top_k_recommendations: page cannot be combined with sections, diversify, explain "
@@ -276,9 +292,10 @@ def get_top_k_recommendations(history_rev_index: np.ndarray, history_len_list: n
     if time_window is not None or categories is not None or prior_gain is not None or group_cap is not None:
         eng.set_catalogue(news_time=news_time, news_cat=news_category, news_prior=prior, news_group=groups)
         flt = {"time_window": time_window, "categories": categories}
-    if page is not None:
-        idx, scores, keys = eng.recommend_deep(int(k), int(page), exclude_history=exclude_history,
-                                               prior_gain=prior_gain, want_keys=True, **flt)
+    if page is not None or walk is not None:
+        deep = {"page": int(page)} if walk is None else {"walk": int(walk)}
+        idx, scores, keys = eng.recommend_deep(int(k), exclude_history=exclude_history, prior_gain=prior_gain,
+                                               want_keys=True, **deep, **flt)
         res = {"news_index": _host(idx), "scores": _host(scores)}
         return {**res, "keys": _host(keys)} if prior_gain is not None else res
     if group_cap is not None:

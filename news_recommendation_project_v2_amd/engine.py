@@ -182,6 +182,7 @@ def check_groups(news_group, n_news: Optional[int]) -> np.ndarray:
 GROUPS_MAX = 1024  # NR_CAP_GROUPS_MAX (include/newsrec_caps.h)
 DEEP_MAX = 1024    # _lib.NR_DEEP_MAX: the longest list recommend_deep pages to
 PAGE_MAX = 64      # _lib.NR_TOPK_MAX: the rows of one cursor call
+WALK_MAX = 256     # _lib.NR_TOPK_DEEP_MAX: the rows of one deep call (one walk over the table)
 
 
 def _no_cursor(what: str, **given) -> None:
@@ -204,11 +205,16 @@ def check_cursor(after, n_imp: int):
     return np.ascontiguousarray(key, dtype=np.float32), np.ascontiguousarray(row, dtype=np.int32)
 
 
-def check_deep(what: str, k, page) -> None:
-    """The sizes of a paged list: 1 <= k <= DEEP_MAX rows in cursor calls of 1 <= page <= PAGE_MAX."""
-    for name, v, top in (("k", k, DEEP_MAX), ("page", page, PAGE_MAX)):
+def check_deep(what: str, k, page, walk=None) -> None:
+    """The sizes of a paged list: 1 <= k <= DEEP_MAX rows in cursor calls of 1 <= page <= PAGE_MAX,
+    or, with ``walk``, in one-walk calls of 1 <= walk <= WALK_MAX rows (``page`` then left alone)."""
+    for name, v, top in (("k", k, DEEP_MAX), ("page", page, PAGE_MAX)) + ((("walk", walk, WALK_MAX),) if walk is not None
+                                                                          else ()):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= top:
             raise ValueError(f"{what}: {name} = {v!r} must be an integer in 1 .. {top}")
+    if walk is not None and page != PAGE_MAX:
+        raise ValueError(f"{what}: walk = {walk!r} cannot be combined with page = {page!r} (walk sizes the calls; "
+                         "leave page at its default)")
 
 
 class _Queries:
@@ -583,8 +589,10 @@ class PoolScoreEngine:
             return q.sel
         return None if self.user_idx is None else self.user_idx.long()
 
-    def _paged_distinct(self, sizes, exclude_history: bool, user_block: Optional[int], q: Optional[_Queries] = None):
-        """Consecutive pages of ``sizes[p]`` rows (each 1 .. 64) per DISTINCT history, or with ``q``
+    def _paged_distinct(self, sizes, exclude_history: bool, user_block: Optional[int], q: Optional[_Queries] = None,
+                        deep: bool = False):
+        """Consecutive pages of ``sizes[p]`` rows (each 1 .. 64; with ``deep`` 1 .. 256, by
+        ops.topk_users_deep: one walk over the table per page) per DISTINCT history, or with ``q``
         per distinct query, by cursor calls (ops.topk_users_after) that start at the queries'
         cursors (``q.after``; the start of the list without).  Returns (idx, scores, keys), each
         [n_rows, sum(sizes)] with the pages side by side, and the cursor behind the last page
@@ -604,19 +612,21 @@ class PoolScoreEngine:
         if n_rows:
             users = self._pooled_users(hidx, hoff)
             blk = n_rows if not user_block else max(1, min(int(user_block), n_rows))
-            need = ops.topk_users_after_workspace_bytes(self.dtype, blk, self.cand_table.shape[0], max(sizes))
+            op, op_bytes = ((ops.topk_users_deep, ops.topk_users_deep_workspace_bytes) if deep else
+                            (ops.topk_users_after, ops.topk_users_after_workspace_bytes))
+            need = max(op_bytes(self.dtype, blk, self.cand_table.shape[0], k) for k in set(sizes))
             self._topk_ws = ops.grow_workspace(getattr(self, "_topk_ws", None), need, dev)
             for a, b, rows, eidx, eoff, flt in self._blocks(q, users, hidx, hoff, n_rows, blk, exclude_history):
                 at = (cur[0][a:b], cur[1][a:b])  # read by a call's first kernels, rewritten by its last
                 for p, k in enumerate(sizes):
-                    ops.topk_users_after(rows, self.cand_table, self.cand_inv, k, after=at, next_out=at, excl_idx=eidx,
-                                         excl_off=eoff, out=tuple(t[a:b] for t in pages[p]), workspace=self._topk_ws,
-                                         excl_checked=p > 0, **flt)
+                    op(rows, self.cand_table, self.cand_inv, k, after=at, next_out=at, excl_idx=eidx, excl_off=eoff,
+                       out=tuple(t[a:b] for t in pages[p]), workspace=self._topk_ws, excl_checked=p > 0, **flt)
         return tuple(torch.cat([pg[i] for pg in pages], dim=1) if len(pages) > 1 else pages[0][i]
                      for i in range(3)) + (cur,)
 
     def recommend_deep(self, k: int, page: int = 64, exclude_history: bool = True, user_block: Optional[int] = None,
-                       time_window=None, categories=None, prior_gain=None, want_keys: bool = False):
+                       time_window=None, categories=None, prior_gain=None, want_keys: bool = False,
+                       walk: Optional[int] = None):
         """recommend past 64 rows: the k best news (1 <= k <= 1024) per impression, fetched in
         ceil(k / page) cursor calls of ``page`` rows (1 .. 64; the last call asks for the
         remainder), each continuing where the one before ended (ops.topk_users_after): the
@@ -626,12 +636,18 @@ class PoolScoreEngine:
         score without ``prior_gain`` -- and returned as recommend returns it: (idx int32 [I, k],
         scores f32 [I, k]) and with ``want_keys`` the keys, (-1, -inf) where fewer than k rows
         are eligible.  The other arguments are recommend's (``group_cap`` is not taken).  For
-        k <= 64 with page = k it is recommend(k) bit for bit."""
-        check_deep("recommend_deep", k, page)
-        k, page = int(k), int(page)
+        k <= 64 with page = k it is recommend(k) bit for bit.
+
+        ``walk`` = W (1 .. 256; ``page`` left at its default) fetches the list in ceil(k / W)
+        chained calls of W rows that each keep their whole list over ONE walk of the table
+        (ops.topk_users_deep): 256 rows cost one users x table product instead of four, 1024
+        four instead of sixteen.  The result is the same bit for bit for every ``walk`` and
+        ``page``; the workspace grows to 4 KiB per distinct user (``user_block`` bounds it)."""
+        check_deep("recommend_deep", k, page, walk)
+        k, page = int(k), int(page if walk is None else walk)
         q = self._queries(time_window, categories, prior_gain)
         sizes = [page] * (k // page) + ([k % page] if k % page else [])
-        idx, scores, keys, _ = self._paged_distinct(sizes, exclude_history, user_block, q)
+        idx, scores, keys, _ = self._paged_distinct(sizes, exclude_history, user_block, q, deep=walk is not None)
         if len(sizes) > 1 and idx.shape[0]:
             # (key descending, row ascending) by two stable sorts: rows first, then keys
             by_row = torch.sort(idx, dim=1, stable=True).indices

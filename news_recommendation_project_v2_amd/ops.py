@@ -626,7 +626,8 @@ def topk_users_after(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_nor
                      time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
                      news_cat: Optional[torch.Tensor] = None, cat_mask: Optional[torch.Tensor] = None,
                      news_prior: Optional[torch.Tensor] = None, user_gain: Optional[torch.Tensor] = None, out=None,
-                     workspace: Optional[torch.Tensor] = None, next_out=None, excl_checked: bool = False):
+                     workspace: Optional[torch.Tensor] = None, next_out=None, excl_checked: bool = False,
+                     _what: str = "topk_users_after"):
     """topk_users_prior behind a cursor (nr_topk_users_after): the k best eligible rows that lie
     strictly after ``after`` = (key f32 [U], row int32 [U]) in the order the retrieval selects in
     (selection key descending, row ascending).  Returns (idx, scores, keys, next): the first
@@ -640,7 +641,7 @@ def topk_users_after(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_nor
     ``next_out`` = (key, row) to write into; ``next_out`` may be ``after`` itself.
     ``excl_checked`` promises that an earlier call range-checked these exclusion lists, and
     saves their sync: a walk over several pages then never waits for the device."""
-    what = "topk_users_after"
+    what = _what  # (topk_users_deep runs this body against its own entry and workspace)
     dev = _dev(users, cand_table, cand_inv_norm, news_prior, user_gain, news_time, time_lo, time_hi, news_cat,
                cat_mask, excl_idx, excl_off, workspace, *(out or ()), *(after or ()), *(next_out or ()))
     n_users, dim, n_news, ld, dt, excl_idx = _check_scan(what, users, cand_table, cand_inv_norm, excl_idx, excl_off,
@@ -653,12 +654,45 @@ def topk_users_after(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_nor
     if nxt is None and want_next:
         nxt = (torch.empty(n_users, dtype=torch.float32, device=dev), torch.empty(n_users, dtype=torch.int32, device=dev))
     nptr = _check_cursor(what, "next_out", n_users, nxt)
-    ws = grow_workspace(workspace, topk_users_after_workspace_bytes(cand_table.dtype, n_users, n_news, k), dev)
+    ws_bytes = topk_users_deep_workspace_bytes if what == "topk_users_deep" else topk_users_after_workspace_bytes
+    ws = grow_workspace(workspace, ws_bytes(cand_table.dtype, n_users, n_news, k), dev)
     idx, scores, keys = _keyed_outputs(what, out, (n_users, k), dev)
-    _lib.call("nr_topk_users_after", dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
+    _lib.call("nr_" + what, dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
               _ptr(cand_inv_norm), _ptr(excl_idx), _ptr(excl_off), *fptr, *pptr, *aptr, *nptr, k, _ptr(idx),
               _ptr(scores), _ptr(keys), _ptr(ws), ws.numel(), _stream(dev))
     return idx, scores, keys, (None if nxt is None else tuple(nxt))
+
+
+def topk_users_deep_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) -> int:
+    """nr_topk_users_deep_workspace_bytes (include/newsrec_deep.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_topk_users_deep_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, k))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"topk_users_deep: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, k = {k}; "
+            f"k in [1, {_lib.NR_TOPK_DEEP_MAX}], N <= 2^22)")
+    return need
+
+
+def topk_users_deep(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int,
+                    after=None, want_next: bool = True, excl_idx: Optional[torch.Tensor] = None,
+                    excl_off: Optional[torch.Tensor] = None, news_time: Optional[torch.Tensor] = None,
+                    time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
+                    news_cat: Optional[torch.Tensor] = None, cat_mask: Optional[torch.Tensor] = None,
+                    news_prior: Optional[torch.Tensor] = None, user_gain: Optional[torch.Tensor] = None, out=None,
+                    workspace: Optional[torch.Tensor] = None, next_out=None, excl_checked: bool = False):
+    """topk_users_after for k up to 256 from ONE walk over the table (nr_topk_users_deep): the
+    arguments and the result (idx, scores, keys, next) are topk_users_after's.  The rows are
+    exactly those of the ceil(k / 64) cursor pages topk_users_after would return from ``after``
+    (the last page asking for the remainder), ordered as one list by score (by key under a
+    prior), ties by ascending row; ``next`` is the cursor behind the last of those pages, so
+    deep calls chain like pages do.  The table is multiplied once instead of once per page; the
+    workspace holds 4 KiB per user and run of chunks (topk_users_deep_workspace_bytes).  For
+    k <= 64 it is topk_users_after bit for bit."""
+    return topk_users_after(users, cand_table, cand_inv_norm, k, after=after, want_next=want_next, excl_idx=excl_idx,
+                            excl_off=excl_off, news_time=news_time, time_lo=time_lo, time_hi=time_hi,
+                            news_cat=news_cat, cat_mask=cat_mask, news_prior=news_prior, user_gain=user_gain, out=out,
+                            workspace=workspace, next_out=next_out, excl_checked=excl_checked,
+                            _what="topk_users_deep")
 
 
 def topk_users_capped_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) -> int:

@@ -12,6 +12,7 @@ has no counterpart -- it only scores the candidates an impression lists).
     python scripts/recommend.py --synthetic --sections "0,1;2;3,4,5" -k 4 [--as-of [--fresh 24]]
     python scripts/recommend.py --synthetic --prior popularity --prior-gain 0.2 [--prior-cold 1] [--evaluate]
     python scripts/recommend.py --synthetic -k 256 --page 64
+    python scripts/recommend.py --synthetic -k 256 --walk 256
 
 Prints one JSON line per run and writes {out-dir}/recommendations.npy: an int32
 [I, K] array of rows of the split's news list (-1 where fewer than K are eligible).
@@ -70,6 +71,10 @@ ceil(K / P) cursor calls of P news, each continuing exactly where the one before
 ordered by score (by key under --prior) before it is written.  The JSON line gains page.  It
 composes with --as-of, --fresh, --categories, --prior* and --evaluate (whose --ks are ranks and
 never were bounded by 64), and is refused with --sections, --diversify, --explain and --cap.
+--walk W (1 .. 256) allows -k up to 1024 as --page does and writes the same arrays
+(include/newsrec_deep.h): the list is fetched in ceil(K / W) chained calls of W news that each
+need ONE walk over the table, where --page 64 needs one per 64 news.  The JSON line gains walk.
+It composes and is refused as --page is, and is refused with --page.
 """
 from __future__ import annotations
 
@@ -244,16 +249,23 @@ def main():
                     help="with --cap: the groups, the news' categories (default) or one label per row of the news list")
     ap.add_argument("--page", type=int, default=None, metavar="P",
                     help="fetch the list in cursor calls of P news (1..64): -k may then go up to 1024")
+    ap.add_argument("--walk", type=int, default=None, metavar="W",
+                    help="fetch the list in calls of W news (1..256) that need one walk over the table each: -k may "
+                         "then go up to 1024")
     args = ap.parse_args()
-    if args.page is not None:
-        if not 1 <= args.page <= 64:
-            ap.error("--page must be in 1 .. 64")
+    if args.page is not None and args.walk is not None:
+        ap.error("--walk cannot be combined with --page")
+    for name, size, top in (("--page", args.page, 64), ("--walk", args.walk, 256)):
+        if size is None:
+            continue
+        if not 1 <= size <= top:
+            ap.error(f"{name} must be in 1 .. {top}")
         if not 1 <= args.k <= 1024:
-            ap.error("-k must be in 1 .. 1024 with --page")
+            ap.error(f"-k must be in 1 .. 1024 with {name}")
         for flag, on in (("--sections", args.sections is not None), ("--diversify", args.diversify is not None),
                          ("--explain", args.explain is not None), ("--cap", args.cap is not None)):
             if on:
-                ap.error(f"--page cannot be combined with {flag}")
+                ap.error(f"{name} cannot be combined with {flag}")
     if args.cap_by is not None and args.cap is None:
         ap.error("--cap-by needs --cap")
     if args.cap is not None:
@@ -316,7 +328,8 @@ def main():
                                         **({} if args.diversify is None else
                                            {"diversify": args.diversify, "pool": args.pool}),
                                         **({} if args.explain is None else {"explain": args.explain}),
-                                        **({} if args.page is None else {"page": args.page}), **flt, **pri, **caps)
+                                        **({} if args.page is None else {"page": args.page}),
+                                        **({} if args.walk is None else {"walk": args.walk}), **flt, **pri, **caps)
     ms = (time.perf_counter() - t0) * 1e3
     idx, scores = rec["news_index"], rec["scores"]
     args.out_dir.mkdir(parents=True, exist_ok=True)
@@ -330,6 +343,8 @@ def main():
             "ms": round(ms, 1), "out": str(path)}
     if args.page is not None:
         line["page"] = args.page
+    if args.walk is not None:
+        line["walk"] = args.walk
     if args.sections is not None:
         names = [sec.strip() for sec in args.sections.split(";")]
         sec_path = args.out_dir / "recommendations_sections.npz"
