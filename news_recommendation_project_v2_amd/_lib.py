@@ -19,13 +19,15 @@ INCLUDE = Path(__file__).resolve().parent.parent / "include"
 # translation units of libnewsrec_hip.so, in link order (also the hash order)
 HIP_SOURCES = ("capi.hip", "gemm.hip", "pool_score.hip", "rowops.hip", "rank.hip", "encoder.hip", "train.hip",
                "metrics.hip", "comm.hip", "latent_train.hip", "final_train.hip", "contrastive.hip", "topk.hip",
-               "fullrank.hip", "rerank.hip", "explain.hip", "sections.hip", "caps.hip", "deep.hip")
+               "fullrank.hip", "rerank.hip", "explain.hip", "sections.hip", "caps.hip", "deep.hip",
+               "request.hip")
 # the headers they include (every object is rebuilt when one changes), hashed after the sources
 HIP_HEADERS = (CSRC / "nr_common.h", CSRC / "nr_rows.h", CSRC / "nr_train.h", CSRC / "nr_score_tile.h",
                INCLUDE / "newsrec.h", INCLUDE / "newsrec_contrastive.h", INCLUDE / "newsrec_topk.h",
                INCLUDE / "newsrec_fullrank.h", INCLUDE / "newsrec_rerank.h", INCLUDE / "newsrec_explain.h",
                INCLUDE / "newsrec_filter.h", INCLUDE / "newsrec_sections.h", INCLUDE / "newsrec_prior.h",
-               INCLUDE / "newsrec_caps.h", INCLUDE / "newsrec_page.h", INCLUDE / "newsrec_sliced.h", INCLUDE / "newsrec_deep.h")
+               INCLUDE / "newsrec_caps.h", INCLUDE / "newsrec_page.h", INCLUDE / "newsrec_sliced.h", INCLUDE / "newsrec_deep.h",
+               INCLUDE / "newsrec_request.h")
 
 
 def hip_source_files() -> list:
@@ -239,6 +241,15 @@ DEEP_SIGNATURES = {
     "nr_topk_users_deep": PAGE_SIGNATURES["nr_topk_users_after"],
 }
 
+# the request path of retrieval (include/newsrec_request.h), bound by load() like SIGNATURES:
+# nr_topk_users_after's arguments for at most NR_REQUEST_MAX_USERS users
+NR_REQUEST_MAX_USERS = 32
+REQUEST_SIGNATURES = {
+    "nr_topk_request_run_rows": (_l, [_l]),
+    "nr_topk_request_workspace_bytes": PAGE_SIGNATURES["nr_topk_users_after_workspace_bytes"],
+    "nr_topk_request": PAGE_SIGNATURES["nr_topk_users_after"],
+}
+
 
 class ContrastiveSpec(ctypes.Structure):
     """struct nr_contrastive_spec (include/newsrec_contrastive.h)."""
@@ -299,7 +310,7 @@ def load() -> ctypes.CDLL:
                               **FULLRANK_SIGNATURES, **RERANK_SIGNATURES, **EXPLAIN_SIGNATURES,
                               **FILTER_SIGNATURES, **SECTIONS_SIGNATURES, **PRIOR_SIGNATURES,
                               **CAPS_SIGNATURES, **PAGE_SIGNATURES, **SLICED_SIGNATURES,
-                              **DEEP_SIGNATURES}.items():
+                              **DEEP_SIGNATURES, **REQUEST_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -265,6 +265,7 @@ class PoolScoreEngine:
             self.hist_src = self.cand_table
         self._check_rows()
         self._cand_image = None
+        self._req_of = None  # prepare_requests builds its tables again
         w = sliced_width(self.cand_table.shape[0], self.dtype, False, False, getattr(self, "pooler", "latent"))
         if w:  # a layout of the loaded table, like its dtype conversion
             self._candidate_image(w)
@@ -726,6 +727,124 @@ class PoolScoreEngine:
         if sel is not None and out[0].shape[0]:
             return tuple(t[sel] for t in out)
         return out
+
+    # ------------------------------------------------------------ the request path
+    def prepare_requests(self):
+        """The tables recommend_request reads -- the transformed history table and the candidate
+        rows' inverse norms -- built once for the loaded tables and again only when ``cand_table``
+        or ``hist_src`` was replaced or written to (their data_ptr, shape and _version, as
+        _candidate_image keys its image).  They are the request path's own: recommend* keep
+        rebuilding theirs."""
+        if self.cand_table is None:
+            raise ValueError("prepare_requests: load_news first")
+        key = tuple((t.data_ptr(), tuple(t.shape), t._version) for t in (self.cand_table, self.hist_src))
+        if getattr(self, "_req_of", None) != key:
+            hist = getattr(self, "_req_hist", None)
+            inv = getattr(self, "_req_inv", None)
+            if inv is not None and inv.shape[0] != self.cand_table.shape[0]:
+                inv = None
+            self._req_of = None
+            self._req_hist = self.transform(out=hist if hist is not None and hist.shape[0] == self.hist_src.shape[0]
+                                            else None)
+            self._req_inv = ops.row_inv_norm(self.cand_table, 1e-8, out=inv)
+            self._req_of = key
+        return self
+
+    def _request_rows(self, what: str, arrays, n_rows: int) -> list:
+        """``arrays`` as int32 host arrays of rows below ``n_rows`` (IndexError otherwise, as
+        _check_rows raises)."""
+        out = []
+        for a in arrays:
+            a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+            if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)) or a.dtype == np.bool_:
+                raise ValueError(f"recommend_request: {what} must be 1-D integer arrays of news rows")
+            if a.size and (int(a.min()) < 0 or int(a.max()) >= n_rows):
+                bad = int(a.min()) if int(a.min()) < 0 else int(a.max())
+                raise IndexError(f"{what} index {bad} is out of bounds for dimension 0 with size {n_rows}")
+            out.append(np.ascontiguousarray(a, dtype=np.int32))
+        return out
+
+    def recommend_request(self, histories, k: int, exclude_history: bool = True, exclude=None, time_window=None,
+                          categories=None, prior_gain=None, want_keys: bool = False, after=None,
+                          want_cursor: bool = False):
+        """recommend for the readers of a request: ``histories`` is a sequence of 1 .. 32 integer
+        arrays of news rows (an empty array is a cold reader), and the result is recommend's for
+        impressions with these histories, bit for bit -- (idx int32 [R, k], scores f32 [R, k]),
+        with ``want_keys`` the keys, with ``want_cursor`` the (key, row) pair behind the lists --
+        with one value per reader wherever recommend takes one per impression.  Nothing of
+        load_impressions is needed or touched.  The per-news tables come from prepare_requests
+        (built once per loaded table); the readers are pooled (ops.pool_users) and searched by
+        ops.topk_request: one read of the table with the whole device busy, where recommend's
+        kernels are shaped for hundreds of thousands of users.  ``exclude`` is a sequence of
+        arrays of rows already shown, one per reader, left out like the history.  The pooled rows
+        and the workspace live on the engine across calls.  ``group_cap``, sections, ``walk`` and
+        ``page`` are recommend's and recommend_deep's; MMR and explanations take the returned
+        lists.  More than 32 readers: load_impressions and recommend."""
+        from . import _lib
+        if isinstance(histories, (str, bytes, np.ndarray, torch.Tensor)) or not hasattr(histories, "__len__"):
+            raise ValueError("recommend_request: histories must be a sequence of integer arrays, one per reader")
+        n = len(histories)
+        if n > _lib.NR_REQUEST_MAX_USERS:
+            raise ValueError(f"recommend_request: {n} histories (at most {_lib.NR_REQUEST_MAX_USERS}; "
+                             "load_impressions and recommend serve more)")
+        if n < 1:
+            raise ValueError("recommend_request: histories must hold at least one reader")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= PAGE_MAX:
+            raise ValueError(f"recommend_request: k = {k!r} must be an integer in 1 .. {PAGE_MAX}")
+        if self.cand_table is None:
+            raise ValueError("recommend_request: load_news first")
+        k, dev, n_news = int(k), self.device, self.cand_table.shape[0]
+        hists = self._request_rows("history", histories, self.hist_src.shape[0])
+        shown = [np.zeros(0, np.int32)] * n
+        if exclude is not None:
+            if isinstance(exclude, (str, bytes, np.ndarray, torch.Tensor)) or not hasattr(exclude, "__len__") \
+                    or len(exclude) != n:
+                raise ValueError(f"recommend_request: exclude must hold one array of rows per reader ({n})")
+            shown = self._request_rows("exclude", exclude, n_news)
+        flt = {}
+        if time_window is not None:
+            if self.news_time is None:
+                raise ValueError("time_window needs set_catalogue(news_time=...)")
+            i32 = np.iinfo(np.int32)
+            lo, hi = (np.clip(np.broadcast_to(np.asarray(v, dtype=np.int64), (n,)), i32.min, i32.max).astype(np.int32)
+                      for v in time_window)
+            flt.update(news_time=self.news_time, time_lo=_upload(lo, dev), time_hi=_upload(hi, dev))
+        if categories is not None:
+            if self.news_cat is None:
+                raise ValueError("categories needs set_catalogue(news_cat=...)")
+            m = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in np.asarray(categories).reshape(-1).tolist()],
+                         dtype=np.uint64).view(np.int64)
+            flt.update(news_cat=self.news_cat, cat_mask=_upload(np.broadcast_to(m, (n,)).copy(), dev))
+        if prior_gain is not None:
+            if getattr(self, "news_prior", None) is None:
+                raise ValueError("prior_gain needs set_catalogue(news_prior=...)")
+            flt.update(news_prior=self.news_prior, user_gain=_upload(check_gain(prior_gain, n), dev))
+        if any(t is not None and t.numel() != n_news for t in (flt.get("news_time"), flt.get("news_cat"),
+                                                                flt.get("news_prior"))):
+            raise ValueError("the catalogue attributes must have one entry per news")
+        cur = None
+        if after is not None:
+            key, row = check_cursor(after, n)
+            cur = (_upload(key, dev), _upload(row, dev))
+        self.prepare_requests()
+        hoff = lengths_to_offsets(np.array([len(h) for h in hists], dtype=np.int64))
+        hidx = np.concatenate(hists) if n else np.zeros(0, np.int32)
+        users = getattr(self, "_req_users", None)
+        if users is None:
+            users = self._req_users = torch.empty((_lib.NR_REQUEST_MAX_USERS, 1024), dtype=torch.float32, device=dev)
+        users = ops.pool_users(self.pooler, self._req_hist, _upload(hidx, dev), _upload(hoff, dev), out=users[:n])
+        eidx = eoff = None
+        if exclude_history or exclude is not None:
+            # a history row that the candidate table does not have excludes nothing
+            rows = [np.concatenate((h[h < n_news] if exclude_history else h[:0], s)) for h, s in zip(hists, shown)]
+            eoff = _upload(lengths_to_offsets(np.array([len(r) for r in rows], dtype=np.int64)), dev)
+            eidx = _upload(np.concatenate(rows).astype(np.int32), dev)
+        self._req_ws = ops.grow_workspace(getattr(self, "_req_ws", None),
+                                          ops.topk_request_workspace_bytes(self.dtype, n, n_news, k), dev)
+        idx, scores, keys, nxt = ops.topk_request(users, self.cand_table, self._req_inv, k, after=cur,
+                                                  want_next=want_cursor, excl_idx=eidx, excl_off=eoff,
+                                                  workspace=self._req_ws, excl_checked=True, **flt)
+        return (idx, scores) + ((keys,) if want_keys else ()) + ((nxt,) if want_cursor else ())
 
     def recommend_sections(self, k: int, sections, exclude_history: bool = True, user_block: Optional[int] = None,
                            time_window=None, prior_gain=None, want_keys: bool = False, group_cap=None, after=None):

@@ -654,7 +654,8 @@ def topk_users_after(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_nor
     if nxt is None and want_next:
         nxt = (torch.empty(n_users, dtype=torch.float32, device=dev), torch.empty(n_users, dtype=torch.int32, device=dev))
     nptr = _check_cursor(what, "next_out", n_users, nxt)
-    ws_bytes = topk_users_deep_workspace_bytes if what == "topk_users_deep" else topk_users_after_workspace_bytes
+    ws_bytes = {"topk_users_deep": topk_users_deep_workspace_bytes,
+                "topk_request": topk_request_workspace_bytes}.get(what, topk_users_after_workspace_bytes)
     ws = grow_workspace(workspace, ws_bytes(cand_table.dtype, n_users, n_news, k), dev)
     idx, scores, keys = _keyed_outputs(what, out, (n_users, k), dev)
     _lib.call("nr_" + what, dt, dim, n_users, _ptr(users), n_news, _ptr(cand_table), ld,
@@ -693,6 +694,40 @@ def topk_users_deep(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm
                             news_cat=news_cat, cat_mask=cat_mask, news_prior=news_prior, user_gain=user_gain, out=out,
                             workspace=workspace, next_out=next_out, excl_checked=excl_checked,
                             _what="topk_users_deep")
+
+
+def topk_request_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) -> int:
+    """nr_topk_request_workspace_bytes (include/newsrec_request.h); raises on a shape the entry refuses."""
+    need = int(_lib.load().nr_topk_request_workspace_bytes(_DT.get(dtype, -1), n_users, n_news, k))
+    if need < 0:
+        raise _lib.NewsRecHIPError(
+            f"topk_request: unsupported shape (dtype {dtype}, U = {n_users}, N = {n_news}, k = {k}; "
+            f"U in [1, {_lib.NR_REQUEST_MAX_USERS}] (topk_users_after takes more users), "
+            f"k in [1, {_lib.NR_TOPK_MAX}], N <= 2^22)")
+    return need
+
+
+def topk_request(users: torch.Tensor, cand_table: torch.Tensor, cand_inv_norm: torch.Tensor, k: int,
+                 after=None, want_next: bool = True, excl_idx: Optional[torch.Tensor] = None,
+                 excl_off: Optional[torch.Tensor] = None, news_time: Optional[torch.Tensor] = None,
+                 time_lo: Optional[torch.Tensor] = None, time_hi: Optional[torch.Tensor] = None,
+                 news_cat: Optional[torch.Tensor] = None, cat_mask: Optional[torch.Tensor] = None,
+                 news_prior: Optional[torch.Tensor] = None, user_gain: Optional[torch.Tensor] = None, out=None,
+                 workspace: Optional[torch.Tensor] = None, next_out=None, excl_checked: bool = False):
+    """topk_users_after for at most 32 users at the cost of one read of the table
+    (nr_topk_request): the arguments and the result (idx, scores, keys, next) are
+    topk_users_after's, bit for bit, and a cursor of either continues in the other.  One
+    workgroup per run of nr_topk_request_run_rows(N) table rows keeps the user rows in LDS and
+    streams the table past them, where topk_users_after's 128-user tiles would be padding.
+    ``out``, ``next_out`` and ``workspace`` (topk_request_workspace_bytes) let a caller hold
+    every buffer across calls.  More than 32 users: use topk_users_after."""
+    if users.dim() == 2 and users.shape[0] > _lib.NR_REQUEST_MAX_USERS:
+        raise _lib.NewsRecHIPError(f"topk_request: {users.shape[0]} users (at most {_lib.NR_REQUEST_MAX_USERS}; "
+                                   "topk_users_after takes more)")
+    return topk_users_after(users, cand_table, cand_inv_norm, k, after=after, want_next=want_next, excl_idx=excl_idx,
+                            excl_off=excl_off, news_time=news_time, time_lo=time_lo, time_hi=time_hi,
+                            news_cat=news_cat, cat_mask=cat_mask, news_prior=news_prior, user_gain=user_gain, out=out,
+                            workspace=workspace, next_out=next_out, excl_checked=excl_checked, _what="topk_request")
 
 
 def topk_users_capped_workspace_bytes(dtype: torch.dtype, n_users: int, n_news: int, k: int) -> int:
